@@ -24,10 +24,21 @@ Other BASELINE configs (builder-run lines, committed under profiles/): --config 
 (base --fix-mate-overlaps -q20 on a 300x contig).  --scale shrinks contig lengths for development.
 
 Prints ONE JSON line on rank 0 with the driver's fields plus `roofline` (dominant kernel,
-algorithmic bytes / HIP-event kernel time), `cpu_baseline` (the CPU oracle -- a literal port
+algorithmic bytes / HIP-event kernel time).  A plain run does only that: set-up, warm-up, the timed
+steps, the line.  With --full the line also carries `cpu_baseline` (the CPU oracle -- a literal port
 of the reference algorithm -- timed on a bounded sample of the same BAM on this box's host),
 `parity_checked` (device results of THIS run compared with the oracle on sampled windows; a mismatch
-makes the process exit non-zero) and `e2e` (the product CLI, file in page cache -> text to /dev/null).
+makes the process exit non-zero), `e2e` (the product CLI, file in page cache -> text to /dev/null)
+and the side measurements (`device_text`, `rerun_cached`, N > 1: `strong_one_contig`,
+`allreduce_option`, `collective`).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64, a fixed
+seeded sample of at most 64 MB): per-position counters for `depth base`, per-window / per-region
+statistics for configs 3 / 4, and the read counts of every run of the step.  The BAM is seeded, so
+the same arguments give the same inputs on every run and every build.
+
+The BAM of a plain run (config 2, one GPU) takes ~40 s to generate; build() leaves it in
+input_cache_dir() so that a plain run on a fresh process finds it there.
 """
 import argparse
 import hashlib
@@ -88,9 +99,30 @@ def workload(args, copies=1):
     raise SystemExit("unknown --config")
 
 
+def input_cache_dir():
+    return os.path.join(os.path.expanduser("~"), ".cache", "sbx-depth-bench")
+
+
 def bam_path(contigs, coverage, seed, level, codec, extra):
+    """The BAM of a workload: the copy build() left in input_cache_dir() when there is one, else one on tmpfs."""
     key = "%s_%g_%x_%d_%s_%s" % (contigs, coverage, seed, level, codec, " ".join(extra))
-    return os.path.join(tmp_dir(), "sbx_bench_%s.bam" % hashlib.sha1(key.encode()).hexdigest()[:12])
+    name = "sbx_bench_%s.bam" % hashlib.sha1(key.encode()).hexdigest()[:12]
+    cached = os.path.join(input_cache_dir(), name)
+    if all(os.path.exists(cached + s) for s in ("", ".bai", ".json")):
+        return cached
+    return os.path.join(tmp_dir(), name)
+
+
+def prepare_default_input():
+    """Generate the BAM of a plain run (the default arguments, one GPU) into input_cache_dir(); returns its path."""
+    args = parser().parse_args([])
+    contigs, coverage, seed, extra, _ = workload(args, 1)
+    path = bam_path(contigs, coverage, seed, args.level, args.codec, extra)
+    if os.path.dirname(path) != input_cache_dir():
+        os.makedirs(input_cache_dir(), exist_ok=True)
+        path = os.path.join(input_cache_dir(), os.path.basename(path))
+        generate(path, contigs, coverage, seed, args.level, args.codec, extra)
+    return path
 
 
 def make_room(keep, need_bytes):
@@ -119,9 +151,15 @@ def generate(path, contigs, coverage, seed, level, codec, extra):
     t0 = time.time()
     tmp_out = path + ".tmp%d" % os.getpid()
     env = dict(os.environ, GEN_TIMING="1")
-    r = subprocess.run([os.path.join(ROOT, "tools", "gen_bam"), "--out", tmp_out, "--contigs", contigs, "--coverage", str(coverage),
-                        "--seed", hex(seed), "--level", str(level), "--codec", codec] + list(extra),
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, check=True)
+    try:
+        r = subprocess.run([os.path.join(ROOT, "tools", "gen_bam"), "--out", tmp_out, "--contigs", contigs, "--coverage", str(coverage),
+                            "--seed", hex(seed), "--level", str(level), "--codec", codec] + list(extra),
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, check=True)
+    except subprocess.CalledProcessError:
+        for f in (tmp_out, tmp_out + ".bai"):      # (a full disk must not leave gigabytes behind)
+            if os.path.exists(f):
+                os.remove(f)
+        raise
     info = json.loads(r.stdout.decode().strip().splitlines()[-1])
     info["gen_seconds"] = time.time() - t0
     info["gen_phases"] = r.stderr.decode().strip().splitlines()[-1:] or [""]
@@ -456,33 +494,36 @@ class Job:
         """One pass of the hot path over this rank's share; returns the list of per-run statistics."""
         d, args, regions, ref_lengths = self.d, self.args, self.regions, self.ref_lengths
         sts = []
+        # what the pass hands out besides the counters left on the device: ("window", ref, first, n_reads, n_bases) /
+        # ("region", regions, n_reads, n_bases) -- kept for --dump-outputs
+        out = self.pass_outputs = []
         if my is not None:
             if regions is not None:
                 d.set_regions(self.shardmod.merge_regions(my))
                 sts.append(d.run())
                 if my:
-                    d.region_stats(my)
+                    out.append(("region", my) + d.region_stats(my)[:2])
             else:
                 for ref, beg, end in my:
                     sts.append(d.run_interval(ref, beg, end))
                     if args.config == 3:
                         n = (min(end, ref_lengths[ref]) // 1000) - beg // 1000
                         if n > 0:
-                            d.window_stats(ref, beg // 1000, n)
+                            out.append(("window", ref, beg // 1000) + d.window_stats(ref, beg // 1000, n)[:2])
                             self.window_rows += n
             return sts
         for b in plan:
             if b is None:
                 sts.append(d.run())
                 if regions is not None:
-                    d.region_stats(self.regions_arr)
+                    out.append(("region", self.regions_arr) + d.region_stats(self.regions_arr)[:2])
             else:
                 sts.append(d.run_batch(b[0], b[1]))
                 if args.config == 3:
                     for r in range(b[0], b[0] + b[1]):
                         n = ref_lengths[r] // 1000
                         if n:
-                            d.window_stats(r, 0, n)
+                            out.append(("window", r, 0) + d.window_stats(r, 0, n)[:2])
                             self.window_rows += n
         return sts
 
@@ -511,6 +552,61 @@ class Job:
             dist.all_reduce(r, op=dist.ReduceOp.SUM)
             reads, adm = float(r[0].item()), float(r[1].item())
         return {"my": my, "plan": plan, "kstats": ks, "elapsed": el, "sum_reads": reads, "sum_adm": adm}
+
+    def dump_outputs(self, out_dir, my, sts, max_bytes=64 * 10**6):
+        """--dump-outputs: what the LAST timed pass computed, as float64 arrays in out_dir/<name>.npy (<name>_rank<r>.npy when N > 1):
+        `run_counts` (reads, admitted reads) of every run of the pass, and for configs 2 / 5 the per-position counters, covered flags
+        and (ref, position) of fixed seeded 4096-position windows of what the pass left on the device, for configs 3 / 4 the per-window
+        / per-region read and base counts with their (ref, beg, end) -- every row when they fit, else a fixed seeded sample of rows.
+        Returns {name: shape}."""
+        import numpy as np
+        budget = (max_bytes - 10**6) // max(1, self.world)        # (1 MB left for the .npy headers)
+        rng = np.random.default_rng(0x5A4D00D0 + self.rank)
+        arrays = {"run_counts": np.array([[s["n_records"], s["n_admitted"]] for s in sts], dtype=np.float64)}
+        budget -= arrays["run_counts"].nbytes
+        d = self.d
+        if self.args.config in (2, 5):
+            # the intervals whose counters the pass left resident (as parity() picks them)
+            ivs = list(my)[-1:] if my is not None else [(r, 0, n) for r, n in enumerate(self.ref_lengths) if n > 0]
+            W, S = 4096, d.n_samples_eff
+            n_win = int(min(128, max(1, budget // (W * 8 * (S * 7 + 3)))))
+            if sum(e - b for _, b, e in ivs) <= n_win * W:
+                wins = [(r, a, min(e, a + W)) for r, b, e in ivs for a in range(b, e, W)]
+            else:      # the first and the last window, the rest random
+                wins = [(ivs[0][0], ivs[0][1], ivs[0][1] + W), (ivs[-1][0], ivs[-1][2] - W, ivs[-1][2])]
+                while len(wins) < n_win:
+                    r, b, e = ivs[int(rng.integers(len(ivs)))]
+                    a = int(rng.integers(b, max(b + 1, e - W)))
+                    wins.append((r, a, min(e, a + W)))
+            got = [d.base_counters(r, a, b, with_covered=True) for r, a, b in wins]
+            arrays["base_counters"] = np.concatenate([c for c, _ in got]).astype(np.float64)
+            arrays["base_covered"] = np.concatenate([v for _, v in got]).astype(np.float64)
+            arrays["base_positions"] = np.concatenate([np.stack([np.full(b - a, r), np.arange(a, b)], axis=1) for r, a, b in wins]).astype(np.float64)
+        elif self.pass_outputs:
+            where, reads, bases = [], [], []
+            for o in self.pass_outputs:
+                if o[0] == "window":
+                    _, r, first, nr, nb = o
+                    k = np.arange(first, first + len(nr))
+                    where.append(np.stack([np.full(len(k), r), k * 1000, (k + 1) * 1000], axis=1))
+                else:
+                    _, regs, nr, nb = o
+                    where.append(np.asarray(regs, dtype=np.int64).reshape(-1, 3))
+                reads.append(nr)
+                bases.append(nb)
+            where, reads, bases = np.concatenate(where), np.concatenate(reads), np.concatenate(bases)
+            keep = budget // (8 * (3 + reads.shape[1] + bases.shape[1]))
+            if len(where) > keep:
+                pick = np.sort(rng.choice(len(where), size=keep, replace=False))
+                where, reads, bases = where[pick], reads[pick], bases[pick]
+            kind = "window" if self.args.config == 3 else "region"
+            arrays.update({kind + "_bounds": where.astype(np.float64), kind + "_reads": reads.astype(np.float64),
+                           kind + "_bases": bases.astype(np.float64)})
+        os.makedirs(out_dir, exist_ok=True)
+        suffix = "_rank%d" % self.rank if self.world > 1 else ""
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+        return {name: list(a.shape) for name, a in arrays.items()}
 
     def device_text(self, steps, sync):
         """`depth base` prints text: one pass INCLUDING the formatting of every row (K6), the text left in HBM -- nothing crosses PCIe,
@@ -668,7 +764,7 @@ class Job:
         return par
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=int(os.environ.get("SBX_BENCH_STEPS", 150)),
@@ -683,6 +779,11 @@ def main():
     ap.add_argument("--coverage", type=float, default=30.0)
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--codec", default=os.environ.get("SBX_BENCH_CODEC", "zlib"))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the parity checks against the oracle, the end-to-end CLI runs and the side "
+                         "measurements; the options below apply to such a run")
     ap.add_argument("--cpu-sample-reads", type=int, default=int(os.environ.get("SBX_BENCH_CPU_READS", 10_000_000)))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
@@ -691,7 +792,11 @@ def main():
     ap.add_argument("--parity-windows", type=int, default=8)
     ap.add_argument("--no-full-parity", dest="full_parity", action="store_false",
                     help="skip the whole-share comparison of the device text with the oracle (configs 2 and 5)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = parser().parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -759,10 +864,15 @@ def main():
         # off, the re-run figure is a side field
         os.environ["SBX_RUNS_CACHE"] = "0"
     main_run = job.timed(sharded, args.warmup, args.steps, sync, red_dev)
+    dumped = None
+    if args.dump_outputs:
+        # before anything below runs the pass again
+        dumped = job.dump_outputs(args.dump_outputs, main_run["my"], main_run["kstats"][-1])
+        log("outputs of the last timed step written to %s" % args.dump_outputs)
     rerun_cached = None
     if args.config == 4 and world == 1:
         del os.environ["SBX_RUNS_CACHE"]
-        if not args.no_side_runs:
+        if args.full and not args.no_side_runs:
             rr = job.timed(sharded, 1, max(2, args.steps // 2), sync, red_dev)
             n_rr = max(2, args.steps // 2)
             rerun_cached = {"ms_per_step": round(rr["elapsed"] / n_rr * 1e3, 3), "value": round(rr["sum_reads"] / (rr["elapsed"] / n_rr) / 1e6, 3),
@@ -771,25 +881,29 @@ def main():
                                     "read-selection table): what a caller that asks twice pays, not what `depth region` pays"}
     my, plan, kstats, elapsed = main_run["my"], main_run["plan"], main_run["kstats"], main_run["elapsed"]
     sum_reads, sum_adm = main_run["sum_reads"], main_run["sum_adm"]
-    log("timed region done: %.1f ms per step; parity" % (elapsed / args.steps * 1e3))
+    log("timed region done: %.1f ms per step" % (elapsed / args.steps * 1e3))
     last = kstats[-1]
     # sharded: reads near a cut are seen by both neighbours, the job's reads are the file's
     total_reads = float(info["reads"]) if sharded else sum_reads
     total_admitted = sum_adm * (total_reads / sum_reads) if (sharded and sum_reads) else sum_adm
 
-    # ---- parity of THIS run's results at scale (every rank checks its own share) --------------------------------
-    par = job.parity(my, plan, args.parity_windows)
-    if dist:
-        okt = torch.tensor([1.0 if par["ok"] else 0.0, float(par["windows"])], dtype=torch.float64, device=red_dev)
-        allok = okt.clone()
-        dist.all_reduce(allok, op=dist.ReduceOp.MIN)
-        dist.all_reduce(okt, op=dist.ReduceOp.SUM)
-        par["ok_all_ranks"] = bool(allok[0].item() >= 1.0)
-        par["windows_all_ranks"] = int(okt[1].item())
-    parity_ok = par.get("ok_all_ranks", par["ok"])
+    # ---- --full: parity of THIS run's results at scale (every rank checks its own share) --------------------------------
+    par = None
+    parity_ok = True
+    if args.full:
+        log("parity")
+        par = job.parity(my, plan, args.parity_windows)
+        if dist:
+            okt = torch.tensor([1.0 if par["ok"] else 0.0, float(par["windows"])], dtype=torch.float64, device=red_dev)
+            allok = okt.clone()
+            dist.all_reduce(allok, op=dist.ReduceOp.MIN)
+            dist.all_reduce(okt, op=dist.ReduceOp.SUM)
+            par["ok_all_ranks"] = bool(allok[0].item() >= 1.0)
+            par["windows_all_ranks"] = int(okt[1].item())
+        parity_ok = par.get("ok_all_ranks", par["ok"])
 
     device_text = None
-    if world == 1 and args.config in (2, 5) and not args.no_side_runs:
+    if args.full and world == 1 and args.config in (2, 5) and not args.no_side_runs:
         try:
             device_text = job.device_text(max(3, args.steps // 4), sync)
         except Exception as e:      # a side measurement must not take the headline down
@@ -797,7 +911,7 @@ def main():
 
     # ---- N > 1: what the collective layer saw (so that a scaling record can be audited: RCCL with N ranks on N distinct devices) -----
     coll = None
-    if dist:
+    if args.full and dist:
         import socket
         props = torch.cuda.get_device_properties(dev_index)
         knames = {"huffman_decode": "ms_huffman", "lz77_resolve": "ms_lz77", "record_index": "ms_index", "decode_accumulate": "ms_accumulate"}
@@ -820,7 +934,7 @@ def main():
     # ---- N > 1, default mode, side measurements -------------------------------------------------------------------
     strong = None
     allred = None
-    if world > 1 and mode == "shard" and args.config in (2, 5) and not args.no_side_runs:
+    if args.full and world > 1 and mode == "shard" and args.config in (2, 5) and not args.no_side_runs:
         # (a) the config's single contig cut into N position slices: strong scaling
         contigs1, cov1, seed1, extra1, _ = workload(args, 1)
         path1 = bam_path(contigs1, cov1, seed1, args.level, args.codec, extra1)
@@ -946,12 +1060,12 @@ def main():
                                         "1.7 ms; SBX_K1A_BURST=22 (32-byte nontemporal bursts): 29.2 ms, 14.2 GB = 1.11 x algorithmic "
                                         "(DESIGN.md section 3, K1a; profiles/round3/call_l_stdout_summary.txt)")
         cpu = None
-        log("parity %s; cpu baseline" % par.get("ok"))
-        if not args.no_cpu_baseline:
-            cpu = cpu_baseline(path, min(args.cpu_sample_reads, int(info["reads"])), mode_args)
         e2e = None
-        log("cpu baseline done; e2e CLI")
-        if not args.no_e2e and world == 1:
+        if args.full and not args.no_cpu_baseline:
+            log("parity %s; cpu baseline" % par.get("ok"))
+            cpu = cpu_baseline(path, min(args.cpu_sample_reads, int(info["reads"])), mode_args)
+        if args.full and not args.no_e2e and world == 1:
+            log("e2e CLI")
             e2e = cli_e2e(path, mode_args, int(info["reads"]), pause=args.e2e_pause)
             if cpu and e2e.get("Mreads_per_s"):
                 e2e["vs_cpu_baseline"] = round(e2e["Mreads_per_s"] / cpu["value"], 1)
@@ -965,7 +1079,7 @@ def main():
                     "replicas": "every GPU runs the full workload (same seeded BAM), no data-path collective"}[mode]
         line = {
             "metric": "depth_%s_Mreads_per_s" % mode_args[0], "value": round(reads_per_s / 1e6, 3), "unit": "Mreads/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "full": args.full,
             "higher_is_better": True, "scaling": "strong" if mode == "strong" else "weak", "vs_baseline": None, "dtype": "u8/u32", "data": "synthetic",
             "config": {"workload": "%s on synthetic %dx coordinate-sorted BAM (%d contig(s), %d Mbp, %d reads of %d bp, BGZF %s level %d, "
                                    "ratio %.2f), compressed bytes resident in HBM" % (
@@ -989,6 +1103,7 @@ def main():
                      "bam_gen_phases": info.get("gen_phases"), "h2d_ms": round(max(s.get("ms_h2d", 0.0) for s in last), 1),
                      "runs_per_pass": len(last), "chain_runs": int(sum(s["n_runs"] for s in last)),
                      "window_rows_per_pass": job.window_rows // max(1, args.steps + args.warmup)},
+            "dumped_outputs": dumped,
         }
         if bad_frac:
             line["accounting_error"] = "roofline fraction outside (0, 1] for: " + ", ".join(bad_frac)
