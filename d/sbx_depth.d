@@ -74,6 +74,13 @@ extern (C) nothrow @nogc {
                           char* err, size_t errlen);
     int sbx_write_bam(const(char)* path, const(ubyte)* stream, size_t n, int level, int with_index, int device, char* err, size_t errlen);
     int sbx_build_index(const(char)* bam_path, const(char)* bai_path, int device, char* err, size_t errlen);
+    struct sbx_flagstat_counts {
+        ulong[2] reads; ulong[2] secondary; ulong[2] supplementary; ulong[2] dup; ulong[2] mapped; ulong[2] pair_all;
+        ulong[2] first; ulong[2] second; ulong[2] pair_good; ulong[2] pair_map; ulong[2] single; ulong[2] diff_chr;
+        ulong[2] diff_high;
+    }
+    int sbx_flagstat(const(char)* bam_path, int device, sbx_flagstat_counts* out_, char* err, size_t errlen);
+    int sbx_format_flagstat(const(sbx_flagstat_counts)* f, int tabular, char* buf, size_t cap, size_t* len);
     int sbx_inflate_blocks(const(ubyte)* comp, const(ulong)* comp_off, const(uint)* comp_len, const(uint)* isize,
                            uint n_blocks, ubyte* out_, const(ulong)* out_off, char* err, size_t errlen);
     sbx_ctx* sbx_open(const(char*)* bam_paths, int n_bams, int device, char* err, size_t errlen);

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -165,6 +165,32 @@ int sbx_write_bam(const char* path, const uint8_t* stream, size_t n, int level, 
  * of the record that straddles its last block boundary, the next one starts with it.
  * SBX_ENOTSORTED when the reads are not coordinate-sorted. */
 int sbx_build_index(const char* bam_path, const char* bai_path, int device, char* err, size_t errlen);
+
+/* `sambamba flagstat` (computeFlagStatistics, sambamba/flagstat.d:31-58): per counter [0] the QC-passed and [1] the QC-failed
+ * (flag 0x200) records, fields in the order of the printed lines (flagstat.d:131-143). */
+typedef struct {
+    uint64_t reads[2];
+    uint64_t secondary[2];
+    uint64_t supplementary[2];
+    uint64_t dup[2];
+    uint64_t mapped[2];
+    uint64_t pair_all[2];
+    uint64_t first[2];
+    uint64_t second[2];
+    uint64_t pair_good[2];
+    uint64_t pair_map[2];
+    uint64_t single[2];
+    uint64_t diff_chr[2];
+    uint64_t diff_high[2];
+} sbx_flagstat_counts;
+/* The counters of every record of a BAM, counted on the device.  Like sbx_build_index it streams the file in batches (the same
+ * batch loop) and needs neither a sort order nor a .bai.  SBX_EIO when the file cannot be read, SBX_EFORMAT for a broken BGZF
+ * stream, deflate stream or record chain, SBX_ENODEVICE without a device.  device: HIP ordinal or -1. */
+int sbx_flagstat(const char* bam_path, int device, sbx_flagstat_counts* out, char* err, size_t errlen);
+/* The 13 lines flagstat_main prints for `f` (flagstat.d:131-143; tabular != 0: the -b form), host only.  Percentages are computed
+ * as percent() does, in single precision (flagstat.d:66-72).  *len receives the length of the text (without the terminating zero,
+ * which is written too); SBX_ENOMEM when buf is null or cap is too small. */
+int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, size_t cap, size_t* len);
 
 /* ---- engine seam ------------------------------------------------------------ */
 

@@ -7,6 +7,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(HERE, "csrc", "libsbx_depth.so")
 _CLI_PATH = os.path.join(HERE, "csrc", "sbx-depth")
+_FLAGSTAT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-flagstat")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -74,6 +75,13 @@ ENOMEM = -8
 class Batch(C.Structure):
     _fields_ = [("first_ref", C.c_uint32), ("n_refs", C.c_uint32), ("est_bytes", C.c_uint64)]
 
+FLAGSTAT_FIELDS = ("reads", "secondary", "supplementary", "dup", "mapped", "pair_all", "first", "second", "pair_good", "pair_map",
+                   "single", "diff_chr", "diff_high")
+
+
+class Flagstat(C.Structure):
+    _fields_ = [(k, C.c_uint64 * 2) for k in FLAGSTAT_FIELDS]
+
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
 
 EXPORTS = [
@@ -82,7 +90,7 @@ EXPORTS = [
     "sbx_set_regions", "sbx_run", "sbx_depth_base_tile", "sbx_depth_region_stats", "sbx_depth_region_stats_from",
     "sbx_depth_window_stats",
     "sbx_format_base_rows", "sbx_stream_base_rows", "sbx_plan_batches", "sbx_run_batch", "sbx_last_run_stats", "sbx_tile_info", "sbx_next_active_range", "sbx_preload",
-    "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device",
+    "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
 ]
 
 _lib = None
@@ -94,6 +102,10 @@ def lib_path():
 
 def cli_path():
     return _CLI_PATH
+
+
+def flagstat_cli_path():
+    return _FLAGSTAT_CLI_PATH
 
 
 def lib():
@@ -150,6 +162,8 @@ def lib():
     L.sbx_bgzf_compress.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
     L.sbx_write_bam.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.sbx_build_index.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.sbx_flagstat.argtypes = [C.c_char_p, C.c_int, C.POINTER(Flagstat), C.c_char_p, C.c_size_t]
+    L.sbx_format_flagstat.argtypes = [C.POINTER(Flagstat), C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_depth_base_tile_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -164,7 +178,7 @@ def lib():
     # the structures above must have the layout the library was compiled with
     for name, ty in (("sbx_region", Region), ("sbx_header_info", HeaderInfo), ("sbx_region_stats", RegionStats),
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
-                     ("sbx_run_stats", RunStats), ("sbx_batch", Batch)):
+                     ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -220,6 +234,32 @@ def build_index(bam_path, bai_path=None, device=-1):
     rc = L.sbx_build_index(bam_path.encode(), (bai_path or bam_path + ".bai").encode(), device, err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
+
+
+def flagstat(path, device=-1):
+    """sbx_flagstat (`sambamba flagstat`): {counter: (QC-passed, QC-failed)} over every record of the BAM, counted on the device."""
+    L = lib()
+    f = Flagstat()
+    err = C.create_string_buffer(512)
+    rc = L.sbx_flagstat(path.encode(), device, C.byref(f), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: (int(getattr(f, k)[0]), int(getattr(f, k)[1])) for k in FLAGSTAT_FIELDS}
+
+
+def format_flagstat(counts, tabular=False):
+    """sbx_format_flagstat: the text `sambamba flagstat` prints for `counts` (as flagstat() returns them), host only."""
+    L = lib()
+    f = Flagstat()
+    for k in FLAGSTAT_FIELDS:
+        getattr(f, k)[0], getattr(f, k)[1] = counts[k]
+    n = C.c_size_t(0)
+    L.sbx_format_flagstat(C.byref(f), int(tabular), None, 0, C.byref(n))
+    buf = C.create_string_buffer(n.value + 1)
+    rc = L.sbx_format_flagstat(C.byref(f), int(tabular), buf, n.value + 1, C.byref(n))
+    if rc != 0:
+        raise SbxError(rc, "sbx_format_flagstat failed")
+    return buf.raw[:n.value].decode()
 
 
 def regex_search(pattern, text, options=""):

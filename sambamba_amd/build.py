@@ -1,4 +1,4 @@
-"""Build libsbx_depth.so (HIP kernels + C ABI) and the sbx-depth CLI for gfx950 with hipcc.
+"""Build libsbx_depth.so (HIP kernels + C ABI) and the sbx-depth / sbx-flagstat CLIs for gfx950 with hipcc.
 
 Usage: python -m sambamba_amd.build   (or sambamba_amd.build.build())
 Outputs are written in-tree (sambamba_amd/csrc/) so they travel with gpurun snapshots.
@@ -11,7 +11,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libsbx_depth.so")
 CLI = os.path.join(CSRC, "sbx-depth")
-SOURCES = ["inflate.hip", "index.hip", "depth.hip", "reduce.hip", "mates.hip", "format.hip", "deflate.hip", "engine.cpp"]
+FLAGSTAT_CLI = os.path.join(CSRC, "sbx-flagstat")
+SOURCES = ["inflate.hip", "index.hip", "depth.hip", "reduce.hip", "mates.hip", "format.hip", "deflate.hip", "flagstat.hip", "engine.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "sbx_depth.h")]
 
 
@@ -54,13 +55,14 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
-    cli_src = os.path.join(CSRC, "cli.cpp")
-    if os.path.exists(cli_src) and (force or _stale(CLI, [cli_src, LIB] + deps)):
-        cmd = [_hipcc(), "-O2", "-std=c++17", "-o", CLI, cli_src, "-L" + CSRC, "-lsbx_depth",
-               "-Wl,-rpath,$ORIGIN"]
-        if verbose:
-            print(" ".join(cmd))
-        subprocess.check_call(cmd)
+    for cli, src in ((CLI, "cli.cpp"), (FLAGSTAT_CLI, "flagstat_cli.cpp")):
+        cli_src = os.path.join(CSRC, src)
+        if os.path.exists(cli_src) and (force or _stale(cli, [cli_src, LIB] + deps)):
+            cmd = [_hipcc(), "-O2", "-std=c++17", "-o", cli, cli_src, "-L" + CSRC, "-lsbx_depth",
+                   "-Wl,-rpath,$ORIGIN"]
+            if verbose:
+                print(" ".join(cmd))
+            subprocess.check_call(cmd)
     return LIB
 
 

@@ -21,6 +21,7 @@
 #include "bai_parallel.hpp"
 #include "common.hpp"
 #include "deflate_core.hpp"
+#include "flagstat.hpp"
 #include "host_io.hpp"
 #include "kernels.hpp"
 
@@ -293,6 +294,10 @@ int guarded(sbx_ctx* c, F&& f) {
 void set_err(char* err, size_t n, const std::string& m) {
     if (err && n) snprintf(err, n, "%s", m.c_str());
 }
+
+// SBX_E* code of the last sbx_open of this thread that failed (sbx_open itself returns null and a message; the standalone entry
+// points built on it -- sbx_flagstat -- return the code)
+thread_local int t_open_code = SBX_OK;
 
 // ---- work list ---------------------------------------------------------------------------------------
 // virtual offset -> (file block, offset in the inflated stream of the file)
@@ -609,6 +614,7 @@ size_t sbx_abi_sizeof(const char* name) {
     if (n == "sbx_batch") return sizeof(sbx_batch);
     if (n == "sbx_run_stats") return sizeof(sbx_run_stats);
     if (n == "sbx_shard") return sizeof(sbx_shard);
+    if (n == "sbx_flagstat_counts") return sizeof(sbx_flagstat_counts);
     return 0;
 }
 
@@ -790,6 +796,8 @@ sbx_ctx* sbx_open(const char* const* bam_paths, int n_bams, int device, char* er
         return c.release();
     } catch (const std::exception& e) {
         set_err(err, errlen, e.what());
+        const Error* x = dynamic_cast<const Error*>(&e);
+        t_open_code = x ? x->code : SBX_EINVAL;
         if (c) for (sbx_ctx* m : c->members) sbx_close(m);
         if (c && c->stream) (void)hipStreamDestroy(c->stream);
         if (c && c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -1762,6 +1770,59 @@ int sbx_bgzf_compress(const uint8_t* in, size_t n, int level, int with_eof, int 
     }
 }
 
+// ---- index-mode passes: the record stream of one file in batches (sbx_build_index, sbx_flagstat) ---------------------------------
+extern "C++" {
+namespace {
+// Inflated bytes per batch: a batch holds its compressed bytes, its inflated bytes, the token streams and the descriptors -- about
+// five times its inflated size --, so the size follows the free device memory; SBX_INDEX_BATCH_BYTES overrides it (tests).
+uint64_t index_batch_bytes() {
+    uint64_t batch_u = 0;
+    if (const char* e = getenv("SBX_INDEX_BATCH_BYTES")) batch_u = strtoull(e, nullptr, 10);
+    if (!batch_u) {
+        size_t free_b = 0, total_b = 0;
+        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+        batch_u = std::max<uint64_t>(64ull << 20, (uint64_t)((double)free_b * 0.7 / 5.0));
+    }
+    return batch_u;
+}
+
+// The file of an index-mode context goes through the device in batches of whole BGZF blocks -- inflate, record chain, descriptors.
+// A batch ends in front of the record that straddles its last block boundary (ChainRun::open_end: the chain stops there and that
+// record is not described) and the next batch starts with that record, so every record of the file is described in exactly one
+// batch.  consume(nrec, base, next) is called once per batch: records [0, nrec) of c->d_desc / c->d_rec_ref are the batch's, their
+// rec_off count from U[0] = inflated offset `base` of the file, and `next` is the inflated offset behind the batch's last record.
+// It returns false to stop the pass (then so does this function); *n_batches receives the number of batches handed over.
+template <class Consume>
+bool for_each_record_batch(sbx_ctx* c, uint64_t batch_u, uint32_t* n_batches, Consume&& consume) {
+    const BlockTable& bt = c->blocks;
+    const size_t nbk = bt.size();
+    const uint64_t total = bt.out_off.back(), first = c->hdr.first_record_off;
+    uint64_t bu = batch_u;
+    *n_batches = 0;
+    for (uint64_t cur = first; cur < total;) {
+        const uint32_t b0 = (uint32_t)(std::upper_bound(bt.out_off.begin(), bt.out_off.end(), cur) - bt.out_off.begin()) - 1;
+        uint32_t b1 = (uint32_t)(std::lower_bound(bt.out_off.begin() + b0, bt.out_off.end(), bt.out_off[b0] + bu) - bt.out_off.begin());
+        b1 = std::min<uint32_t>(std::max(b1, b0 + 1), (uint32_t)nbk);
+        if (bt.out_off[b1] >= total) b1 = (uint32_t)nbk;          // (whatever follows holds no bytes: EOF blocks)
+        const bool last = b1 == nbk;
+        const std::vector<FileRun> runs{FileRun{b0, b1, cur, last ? total : bt.out_off[b1], !last}};
+        run_impl(c, {}, false, &runs);
+        const uint64_t nrec = c->primary_records;
+        const uint64_t base = bt.out_off[b0];            // work-list offsets count from the batch's first block
+        const uint64_t next = last ? total : c->index_straddler != kOffUnknown ? base + c->index_straddler : bt.out_off[b1];
+        if (!last && next == cur) {                      // not one whole record in the batch: a longer batch
+            bu *= 2;
+            continue;
+        }
+        ++*n_batches;
+        if (!consume(nrec, base, next)) return false;
+        cur = next;
+    }
+    return true;
+}
+}  // namespace
+}  // extern "C++"
+
 int sbx_build_index(const char* bam_path, const char* bai_path, int device, char* err, size_t errlen) {
     sbx_ctx* c = nullptr;
     try {
@@ -1775,21 +1836,12 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
         c->mode = SBX_MODE_BASE;
         c->fix_mate = false;
         // IndexBuilder is one pass over a stream of records (bai/indexing.d:262-316), and so is this: the file goes through the
-        // device in batches of whole BGZF blocks -- inflate, record chain, descriptors --, a batch ends in front of the record that
-        // straddles its last block boundary (ChainRun::open_end) and the next batch starts with that record.  The batch size follows
-        // the free device memory (a batch holds its compressed bytes, its inflated bytes, the token streams and the descriptors: about
-        // five times its inflated size); SBX_INDEX_BATCH_BYTES overrides it (tests).
+        // device in batches of whole BGZF blocks (for_each_record_batch).
         const BlockTable& bt = c->blocks;
         const size_t nbk = bt.size();
-        const uint64_t total = bt.out_off.back(), first = c->hdr.first_record_off;
+        const uint64_t total = bt.out_off.back();
         const uint64_t file_end_coff = nbk ? bt.comp_off[nbk - 1] + bt.comp_len[nbk - 1] + 8 : 0;
-        uint64_t batch_u = 0;
-        if (const char* e = getenv("SBX_INDEX_BATCH_BYTES")) batch_u = strtoull(e, nullptr, 10);
-        if (!batch_u) {
-            size_t free_b = 0, total_b = 0;
-            SBX_HIP(hipMemGetInfo(&free_b, &total_b));
-            batch_u = std::max<uint64_t>(64ull << 20, (uint64_t)((double)free_b * 0.7 / 5.0));
-        }
+        const uint64_t batch_u = index_batch_bytes();
         hipStream_t s = c->stream;
         const int n_ref = (int)c->hdr.refs.size();
         // What consumes the records of a batch: the device (bai_parallel.hpp -- one lane per record; only the run heads, about one
@@ -1832,24 +1884,7 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
                 SBX_HIP(hipMemsetAsync(d_scalars.p, 0, d_scalars.bytes(), s));
                 SBX_HIP(hipMemsetAsync(d_scalars.p + kBaiFirstVo, 0xFF, 8, s));
             }
-            uint64_t bu = batch_u;
-            n_batches = 0;
-            for (uint64_t cur = first; cur < total;) {
-                const uint32_t b0 = (uint32_t)(std::upper_bound(bt.out_off.begin(), bt.out_off.end(), cur) - bt.out_off.begin()) - 1;
-                uint32_t b1 = (uint32_t)(std::lower_bound(bt.out_off.begin() + b0, bt.out_off.end(), bt.out_off[b0] + bu) - bt.out_off.begin());
-                b1 = std::min<uint32_t>(std::max(b1, b0 + 1), (uint32_t)nbk);
-                if (bt.out_off[b1] >= total) b1 = (uint32_t)nbk;          // (whatever follows holds no bytes: EOF blocks)
-                const bool last = b1 == nbk;
-                const std::vector<FileRun> runs{FileRun{b0, b1, cur, last ? total : bt.out_off[b1], !last}};
-                run_impl(c, {}, false, &runs);
-                const uint64_t nrec = c->primary_records;
-                const uint64_t base = bt.out_off[b0];            // work-list offsets count from the batch's first block
-                const uint64_t next = last ? total : c->index_straddler != kOffUnknown ? base + c->index_straddler : bt.out_off[b1];
-                if (!last && next == cur) {                      // not one whole record in the batch: a longer batch
-                    bu *= 2;
-                    continue;
-                }
-                ++n_batches;
+            const bool whole = for_each_record_batch(c, batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
                 if (on_device) {
                     const uint64_t cap = nrec / 4 + 4096;
                     d_runs.ensure((size_t)cap);
@@ -1894,8 +1929,9 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
                         have_held = true;
                     }
                 }
-                cur = next;
-            }
+                return true;
+            });
+            if (!whole) return false;
             if (on_device) {
                 const size_t m = (size_t)n_ref + 1;
                 R.lin.resize(d_lin.n); R.lin_len.resize(m); R.meta_end.resize(m); R.n_mapped.resize(m); R.n_unmapped.resize(m);
@@ -1937,6 +1973,115 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
         if (c) sbx_close(c);
         return SBX_EINVAL;
     }
+}
+
+// `sambamba flagstat` (computeFlagStatistics, flagstat.d:31-58): one pass like sbx_build_index's -- index mode, no filter, no sort
+// order or index required -- with K8 (flagstat.hip) adding each batch's records to 26 device counters, read back once at the end.
+// Every record of the chain is counted, also one that index mode calls bad (refID out of range, lengths that disagree with
+// block_size) or one that starts beyond its contig: the reference reads nothing but the flags, mapq and the two reference ids.
+int sbx_flagstat(const char* bam_path, int device, sbx_flagstat_counts* out, char* err, size_t errlen) {
+    static_assert(sizeof(sbx_flagstat_counts) == 26 * sizeof(uint64_t), "sbx_flagstat_counts is the kernel's 26 counters");
+    sbx_ctx* c = nullptr;
+    try {
+        if (!bam_path || !out) throw Error(SBX_EINVAL, "null argument");
+        const double w0 = wall_now();
+        const char* one[1] = {bam_path};
+        char e2[512] = {0};
+        c = sbx_open(one, 1, device, e2, sizeof e2);
+        if (!c) throw Error(t_open_code != SBX_OK ? t_open_code : SBX_EIO, e2);
+        c->index_mode = true;
+        memset(&c->filter, 0, sizeof c->filter);         // no filter: every record is described
+        c->mode = SBX_MODE_BASE;
+        c->fix_mate = false;
+        hipStream_t s = c->stream;
+        DevBuf<unsigned long long> d_counts(26);
+        SBX_HIP(hipMemsetAsync(d_counts.p, 0, d_counts.bytes(), s));
+        const bool timing = getenv("SBX_TIMING") != nullptr;
+        const double w1 = wall_now();
+        EventTimer t_k;
+        double ms_inflate = 0, ms_index = 0, ms_k8 = 0;
+        uint64_t n_records = 0;
+        uint32_t n_batches = 0;
+        for_each_record_batch(c, index_batch_bytes(), &n_batches, [&](uint64_t nrec, uint64_t, uint64_t) -> bool {
+            t_k.start(s);
+            launch_flagstat(c->U(), c->d_desc.p, c->d_rec_ref.p, nrec, d_counts.p, s);
+            t_k.stop(s);
+            // (the next batch's K2 overwrites these descriptors, and may reallocate them, from the host side: K8 ends first)
+            SBX_HIP(hipStreamSynchronize(s));
+            if (timing) { ms_inflate += c->stats.ms_inflate; ms_index += c->stats.ms_index; ms_k8 += t_k.ms(); }
+            n_records += nrec;
+            return true;
+        });
+        sbx_flagstat_counts r{};
+        SBX_HIP(hipMemcpyAsync(&r, d_counts.p, sizeof r, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        if (r.reads[0] + r.reads[1] != n_records)
+            throw Error(SBX_EFORMAT, "internal error: flagstat counted " + std::to_string(r.reads[0] + r.reads[1]) + " of " +
+                                         std::to_string(n_records) + " records");
+        *out = r;
+        if (timing)
+            fprintf(stderr, "[sbx] flagstat: %llu records in %u batch(es): inflate %.2f ms, record index %.2f ms, flagstat kernel %.3f ms; "
+                            "open %.1f ms, pass %.1f ms (wall)\n", (unsigned long long)n_records, n_batches, ms_inflate, ms_index, ms_k8,
+                    (w1 - w0) * 1e3, (wall_now() - w1) * 1e3);
+        sbx_close(c);
+        return SBX_OK;
+    } catch (const Error& e) {
+        set_err(err, errlen, e.what());
+        if (c) sbx_close(c);
+        return e.code;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        if (c) sbx_close(c);
+        return SBX_EINVAL;
+    }
+}
+
+extern "C++" {
+namespace {
+// percent / percentStr of flagstat.d:66-72: to!float(a) / b is single precision, `* 100.0` double, returned as float
+void percent_str(uint64_t a, uint64_t b, char* buf, size_t n) {
+    if (b == 0) { snprintf(buf, n, "N/A"); return; }
+    const float p = (float)((double)((float)a / (float)b) * 100.0);
+    snprintf(buf, n, "%.2f%%", (double)p);
+}
+}  // namespace
+}  // extern "C++"
+
+int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, size_t cap, size_t* len) {
+    if (!f) return SBX_EINVAL;
+    std::string out;
+    char line[256], p0[32], p1[32];
+    auto param = [&](const char* what, const uint64_t* v) {
+        if (tabular) snprintf(line, sizeof line, "%s,%llu,%llu\n", what, (unsigned long long)v[0], (unsigned long long)v[1]);
+        else snprintf(line, sizeof line, "%llu + %llu %s\n", (unsigned long long)v[0], (unsigned long long)v[1], what);
+        out += line;
+    };
+    auto with_pct = [&](const char* what, const uint64_t* v, const uint64_t* total) {
+        percent_str(v[0], total[0], p0, sizeof p0);
+        percent_str(v[1], total[1], p1, sizeof p1);
+        if (tabular) snprintf(line, sizeof line, "%s,%llu:%s,%llu:%s\n", what, (unsigned long long)v[0], p0, (unsigned long long)v[1], p1);
+        else snprintf(line, sizeof line, "%llu + %llu %s (%s:%s)\n", (unsigned long long)v[0], (unsigned long long)v[1], what, p0, p1);
+        out += line;
+    };
+    // flagstat.d:131-143
+    param("in total (QC-passed reads + QC-failed reads)", f->reads);
+    param("secondary", f->secondary);
+    param("supplementary", f->supplementary);
+    param("duplicates", f->dup);
+    with_pct("mapped", f->mapped, f->reads);
+    param("paired in sequencing", f->pair_all);
+    param("read1", f->first);
+    param("read2", f->second);
+    with_pct("properly paired", f->pair_good, f->pair_all);
+    param("with itself and mate mapped", f->pair_map);
+    with_pct("singletons", f->single, f->pair_all);
+    param("with mate mapped to a different chr", f->diff_chr);
+    param("with mate mapped to a different chr (mapQ>=5)", f->diff_high);
+    if (len) *len = out.size();
+    if (!buf || out.size() + 1 > cap) return SBX_ENOMEM;
+    memcpy(buf, out.data(), out.size());
+    buf[out.size()] = 0;
+    return SBX_OK;
 }
 
 int sbx_write_bam(const char* path, const uint8_t* stream, size_t n, int level, int with_index, int device, char* err, size_t errlen) {

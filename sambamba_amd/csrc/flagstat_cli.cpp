@@ -1,0 +1,85 @@
+// flagstat_cli.cpp -- `sbx-flagstat`: the standalone `sambamba-flagstat` (flagstat_main, sambamba/flagstat.d:82-148) on top of the
+// C ABI of libsbx_depth.so.  The counting happens on the device (sbx_flagstat); this file parses the options and prints.
+//
+//   sbx-flagstat [-t N|--nthreads=N] [-p|--show-progress] [-b|--tabular] in.bam
+//
+// As with D's getopt, options may follow the file name.  -t only sizes the reference's decompression pool and is accepted and
+// ignored; so is -p (the device pass reports no progress).  The counters are printed only after the whole file was read
+// (flagstat.d:127-145): on any error stdout stays empty, the message goes to stderr and the exit status is 1.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/sbx_depth.h"
+
+namespace {
+
+void usage() {
+    fputs("Usage: sbx-flagstat [options] <input.bam>\n"
+          "\n"
+          "Counts the records of a BAM file by their flags, as `sambamba flagstat` does, on the GPU.\n"
+          "\n"
+          "Options: -t, --nthreads=N     accepted for compatibility; the GPU does the decompression\n"
+          "         -p, --show-progress  accepted for compatibility; no progress is drawn\n"
+          "         -b, --tabular        print comma-separated values\n",
+          stderr);
+}
+
+bool parse_count(const char* s) {
+    if (!s || !*s) return false;
+    char* end = nullptr;
+    strtoull(s, &end, 10);
+    return *end == 0 && s[0] != '-';
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    bool tabular = false;
+    std::vector<std::string> files;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--") {
+            for (++i; i < argc; ++i) files.push_back(argv[i]);
+            break;
+        }
+        if (a == "-b" || a == "--tabular") { tabular = true; continue; }
+        if (a == "-p" || a == "--show-progress") continue;
+        if (a == "-t" || a == "--nthreads") {
+            if (i + 1 >= argc) { fprintf(stderr, "Missing value for argument %s.\n", a.c_str()); return 1; }
+            if (!parse_count(argv[++i])) { fprintf(stderr, "Invalid number of threads: %s\n", argv[i]); return 1; }
+            continue;
+        }
+        if (a.compare(0, 11, "--nthreads=") == 0 || (a.size() > 2 && a.compare(0, 2, "-t") == 0)) {
+            const char* v = a[1] == '-' ? a.c_str() + 11 : a.c_str() + (a[2] == '=' ? 3 : 2);
+            if (!parse_count(v)) { fprintf(stderr, "Invalid number of threads: %s\n", v); return 1; }
+            continue;
+        }
+        if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "Unrecognized option %s\n", a.c_str()); return 1; }
+        files.push_back(a);
+    }
+    if (files.empty()) {
+        usage();
+        return 1;
+    }
+    sbx_flagstat_counts f;
+    char err[512] = {0};
+    if (sbx_flagstat(files[0].c_str(), -1, &f, err, sizeof err) != SBX_OK) {
+        fprintf(stderr, "%s\n", err);
+        return 1;
+    }
+    size_t n = 0;
+    sbx_format_flagstat(&f, tabular ? 1 : 0, nullptr, 0, &n);
+    std::vector<char> text(n + 1);
+    if (sbx_format_flagstat(&f, tabular ? 1 : 0, text.data(), text.size(), &n) != SBX_OK) {
+        fprintf(stderr, "cannot format the counters\n");
+        return 1;
+    }
+    if (fwrite(text.data(), 1, n, stdout) != n || fflush(stdout) != 0) {
+        fprintf(stderr, "error writing the output\n");
+        return 1;
+    }
+    return 0;
+}
