@@ -12,7 +12,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libsbx_depth.so")
 CLI = os.path.join(CSRC, "sbx-depth")
 FLAGSTAT_CLI = os.path.join(CSRC, "sbx-flagstat")
-SOURCES = ["inflate.hip", "index.hip", "depth.hip", "reduce.hip", "mates.hip", "format.hip", "deflate.hip", "flagstat.hip", "engine.cpp"]
+SOURCES = ["inflate.hip", "index.hip", "depth.hip", "reduce.hip", "mates.hip", "format.hip", "deflate.hip", "flagstat.hip", "engine.cpp",
+           "engine_worklist.cpp", "engine_run.cpp", "engine_stats.cpp", "engine_text.cpp", "engine_writer.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "sbx_depth.h")]
 
 

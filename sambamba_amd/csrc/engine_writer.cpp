@@ -1,0 +1,435 @@
+// engine_writer.cpp -- the write side and the passes over the record stream of one file: BGZF compression on the device
+// (sbx_bgzf_compress, sbx_write_bam), and the index-mode passes in batches (for_each_record_batch) behind sbx_build_index and
+// sbx_flagstat.
+#include <algorithm>
+#include <cstdlib>
+
+#include "bai_parallel.hpp"
+#include "bai_writer.hpp"
+#include "deflate_core.hpp"
+#include "engine_ctx.hpp"
+#include "flagstat.hpp"
+
+// ---- the write side: BGZF compression, BAM files, BAI ---------------------------------------------------------------
+namespace {
+const uint8_t kEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// compresses in[0, n) piece by piece on the device; sink(data, len) receives consecutive pieces of the BGZF stream
+template <class Sink>
+void bgzf_compress_stream(const uint8_t* in, size_t n, int level, Sink&& sink) {
+    Stream stream;
+    stream.create();
+    hipStream_t s = stream.get();
+    const size_t piece_blocks = 32768;
+    const size_t n_blocks_total = (n + kBgzfPayload - 1) / kBgzfPayload;
+    const uint32_t cap_blocks = (uint32_t)std::min<size_t>(piece_blocks, std::max<size_t>(1, n_blocks_total));
+    DevBuf<uint8_t> d_in((size_t)cap_blocks * kBgzfPayload + 64), d_slots((size_t)cap_blocks * kBgzfSlot), d_out((size_t)cap_blocks * kBgzfSlot);
+    DevBuf<uint16_t> d_tab(deflate_table_entries(cap_blocks));
+    DevBuf<uint8_t> d_work(deflate_work_bytes(cap_blocks));
+    DevBuf<uint32_t> d_len(cap_blocks + 1);
+    DevBuf<uint64_t> d_off((size_t)cap_blocks + 2);
+    std::vector<uint8_t> host;
+    const bool timing = getenv("SBX_TIMING") != nullptr;
+    EventTimer t_def, t_pack;
+    double ms_h2d = 0, ms_def = 0, ms_pack = 0, ms_d2h = 0;
+    uint64_t out_total = 0;
+    for (size_t done = 0; done < n;) {
+        const size_t bytes = std::min<size_t>(n - done, (size_t)cap_blocks * kBgzfPayload);
+        const uint32_t nb = (uint32_t)((bytes + kBgzfPayload - 1) / kBgzfPayload);
+        const double w0 = wall_now();
+        SBX_HIP(hipMemcpyAsync(d_in.p, in + done, bytes, hipMemcpyHostToDevice, s));
+        if (timing) SBX_HIP(hipStreamSynchronize(s));
+        const double w1 = wall_now();
+        t_def.start(s);
+        launch_bgzf_deflate(d_in.p, bytes, nb, level, d_slots.p, d_tab.p, d_work.p, d_len.p, s);
+        t_def.stop(s);
+        t_pack.start(s);
+        launch_count_scan(d_len.p, nb, d_off.p, nullptr, 0, s);
+        launch_pack_blocks(d_slots.p, d_len.p, d_off.p, nb, d_out.p, s);
+        t_pack.stop(s);
+        uint64_t total = 0;
+        SBX_HIP(hipMemcpyAsync(&total, d_off.p + nb, 8, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        const double w2 = wall_now();
+        host.resize((size_t)total);
+        SBX_HIP(hipMemcpy(host.data(), d_out.p, (size_t)total, hipMemcpyDeviceToHost));
+        if (timing) { ms_h2d += (w1 - w0) * 1e3; ms_def += t_def.ms(); ms_pack += t_pack.ms(); ms_d2h += (wall_now() - w2) * 1e3; out_total += total; }
+        sink(host.data(), (size_t)total);
+        done += bytes;
+    }
+    if (timing)
+        fprintf(stderr, "[sbx] bgzf_compress: %zu bytes -> %llu in %zu blocks: host -> device %.1f ms (pageable), deflate kernel %.1f ms (%.1f GB/s of input), "
+                        "scan + pack %.1f ms, device -> host %.1f ms\n", n, (unsigned long long)out_total, n_blocks_total, ms_h2d, ms_def,
+                ms_def > 0 ? (double)n / ms_def / 1e6 : 0.0, ms_pack, ms_d2h);
+}
+}  // namespace
+
+extern "C" {
+
+int sbx_bgzf_compress(const uint8_t* in, size_t n, int level, int with_eof, int device, uint8_t* out, size_t cap, size_t* out_len,
+                      char* err, size_t errlen) {
+    try {
+        if ((!in && n) || !out_len) throw Error(SBX_EINVAL, "null argument");
+        if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
+        require_device(device);
+        size_t pos = 0;
+        bgzf_compress_stream(in, n, level, [&](const uint8_t* p, size_t k) {
+            if (pos + k > cap || !out) { pos += k; return; }
+            memcpy(out + pos, p, k);
+            pos += k;
+        });
+        if (with_eof) {
+            if (out && pos + 28 <= cap) memcpy(out + pos, kEofBlock, 28);
+            pos += 28;
+        }
+        *out_len = pos;
+        if (pos > cap || !out) throw Error(SBX_ENOMEM, "output buffer too small for the BGZF stream");
+        return SBX_OK;
+    } catch (const Error& e) {
+        set_err(err, errlen, e.what());
+        return e.code;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return SBX_EINVAL;
+    }
+}
+
+// ---- index-mode passes: the record stream of one file in batches (sbx_build_index, sbx_flagstat) ---------------------------------
+extern "C++" {
+namespace {
+// Inflated bytes per batch: a batch holds its compressed bytes, its inflated bytes, the token streams and the descriptors -- about
+// five times its inflated size --, so the size follows the free device memory; SBX_INDEX_BATCH_BYTES overrides it (tests).
+uint64_t index_batch_bytes() {
+    uint64_t batch_u = 0;
+    if (const char* e = getenv("SBX_INDEX_BATCH_BYTES")) batch_u = strtoull(e, nullptr, 10);
+    if (!batch_u) {
+        size_t free_b = 0, total_b = 0;
+        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+        batch_u = std::max<uint64_t>(64ull << 20, (uint64_t)((double)free_b * 0.7 / 5.0));
+    }
+    return batch_u;
+}
+
+// The file of an index-mode context goes through the device in batches of whole BGZF blocks -- inflate, record chain, descriptors.
+// A batch ends in front of the record that straddles its last block boundary (ChainRun::open_end: the chain stops there and that
+// record is not described) and the next batch starts with that record, so every record of the file is described in exactly one
+// batch.  consume(nrec, base, next) is called once per batch: records [0, nrec) of c->d_desc / c->d_rec_ref are the batch's, their
+// rec_off count from U[0] = inflated offset `base` of the file, and `next` is the inflated offset behind the batch's last record.
+// It returns false to stop the pass (then so does this function); *n_batches receives the number of batches handed over.
+template <class Consume>
+bool for_each_record_batch(sbx_ctx* c, uint64_t batch_u, uint32_t* n_batches, Consume&& consume) {
+    const BlockTable& bt = c->blocks;
+    const size_t nbk = bt.size();
+    const uint64_t total = bt.out_off.back(), first = c->hdr.first_record_off;
+    uint64_t bu = batch_u;
+    *n_batches = 0;
+    for (uint64_t cur = first; cur < total;) {
+        const uint32_t b0 = (uint32_t)(std::upper_bound(bt.out_off.begin(), bt.out_off.end(), cur) - bt.out_off.begin()) - 1;
+        uint32_t b1 = (uint32_t)(std::lower_bound(bt.out_off.begin() + b0, bt.out_off.end(), bt.out_off[b0] + bu) - bt.out_off.begin());
+        b1 = std::min<uint32_t>(std::max(b1, b0 + 1), (uint32_t)nbk);
+        if (bt.out_off[b1] >= total) b1 = (uint32_t)nbk;          // (whatever follows holds no bytes: EOF blocks)
+        const bool last = b1 == nbk;
+        const std::vector<FileRun> runs{FileRun{b0, b1, cur, last ? total : bt.out_off[b1], !last}};
+        run_impl(c, {}, false, &runs);
+        const uint64_t nrec = c->primary_records;
+        const uint64_t base = bt.out_off[b0];            // work-list offsets count from the batch's first block
+        const uint64_t next = last ? total : c->index_straddler != kOffUnknown ? base + c->index_straddler : bt.out_off[b1];
+        if (!last && next == cur) {                      // not one whole record in the batch: a longer batch
+            bu *= 2;
+            continue;
+        }
+        ++*n_batches;
+        if (!consume(nrec, base, next)) return false;
+        cur = next;
+    }
+    return true;
+}
+}  // namespace
+}  // extern "C++"
+
+int sbx_build_index(const char* bam_path, const char* bai_path, int device, char* err, size_t errlen) {
+    sbx_ctx* c = nullptr;
+    try {
+        if (!bam_path || !bai_path) throw Error(SBX_EINVAL, "null argument");
+        const char* one[1] = {bam_path};
+        char e2[512] = {0};
+        c = sbx_open(one, 1, device, e2, sizeof e2);
+        if (!c) throw Error(SBX_EIO, e2);
+        c->index_mode = true;
+        memset(&c->filter, 0, sizeof c->filter);         // no filter: every record is described
+        c->mode = SBX_MODE_BASE;
+        c->fix_mate = false;
+        // IndexBuilder is one pass over a stream of records (bai/indexing.d:262-316), and so is this: the file goes through the
+        // device in batches of whole BGZF blocks (for_each_record_batch).
+        const BlockTable& bt = c->blocks;
+        const size_t nbk = bt.size();
+        const uint64_t total = bt.out_off.back();
+        const uint64_t file_end_coff = nbk ? bt.comp_off[nbk - 1] + bt.comp_len[nbk - 1] + 8 : 0;
+        const uint64_t batch_u = index_batch_bytes();
+        hipStream_t s = c->stream.get();
+        const int n_ref = (int)c->hdr.refs.size();
+        // What consumes the records of a batch: the device (bai_parallel.hpp -- one lane per record; only the run heads, about one
+        // record in fifty, and a few per-reference arrays come back) or, for input that formulation calls irregular (unsorted reads:
+        // the reference's error is worded by the serial builder; reads far beyond the end of their reference) and with
+        // SBX_BAI_HOST=1, IndexBuilder's loop restated on the host (bai_writer.hpp) over descriptors copied back record by record.
+        std::vector<uint8_t> bytes;
+        uint32_t n_batches = 0;
+        auto pass = [&](bool on_device) -> bool {
+            // serial consumer
+            VoffCursor vc(bt.coffset.data(), bt.out_off.data(), nbk, file_end_coff);
+            BaiBuilder bb(n_ref);
+            BaiRecord held;                 // the last record of the batch before: it ends where the next batch starts
+            bool have_held = false;
+            DevBuf<uint16_t> d_bins;
+            std::vector<RecDesc> desc;
+            std::vector<int32_t> ref;
+            std::vector<uint16_t> bins;
+            // device consumer
+            BaiHostResults R;
+            DevBuf<uint64_t> d_coff, d_ustart, d_lin, d_meta;      // d_meta: meta_end | n_mapped | n_unmapped, n_ref + 1 each
+            DevBuf<uint32_t> d_lin_off, d_lin_len;
+            DevBuf<unsigned long long> d_scalars;
+            DevBuf<BaiRun> d_runs;
+            DevBuf<BaiCarry> d_carry(1);
+            BaiCarry carry{-1, 0, 0, 0, 0};
+            uint64_t rec_base = 0;
+            if (on_device) {
+                R.lin_off.assign((size_t)n_ref + 1, 0);
+                for (int r = 0; r < n_ref; ++r) R.lin_off[(size_t)r + 1] = R.lin_off[(size_t)r] + bai_windows_for(c->hdr.refs[(size_t)r].length);
+                d_coff.alloc(nbk + 1); d_ustart.alloc(nbk + 2);
+                d_lin.alloc((size_t)R.lin_off[(size_t)n_ref] + 1); d_lin_off.alloc((size_t)n_ref + 2); d_lin_len.alloc((size_t)n_ref + 1);
+                d_meta.alloc(3 * ((size_t)n_ref + 1)); d_scalars.alloc(kBaiScalars);
+                if (nbk) SBX_HIP(hipMemcpyAsync(d_coff.p, bt.coffset.data(), nbk * 8, hipMemcpyHostToDevice, s));
+                SBX_HIP(hipMemcpyAsync(d_ustart.p, bt.out_off.data(), (nbk + 1) * 8, hipMemcpyHostToDevice, s));
+                SBX_HIP(hipMemcpyAsync(d_lin_off.p, R.lin_off.data(), ((size_t)n_ref + 1) * 4, hipMemcpyHostToDevice, s));
+                SBX_HIP(hipMemsetAsync(d_lin.p, 0xFF, d_lin.bytes(), s));
+                SBX_HIP(hipMemsetAsync(d_lin_len.p, 0, d_lin_len.bytes(), s));
+                SBX_HIP(hipMemsetAsync(d_meta.p, 0, d_meta.bytes(), s));
+                SBX_HIP(hipMemsetAsync(d_scalars.p, 0, d_scalars.bytes(), s));
+                SBX_HIP(hipMemsetAsync(d_scalars.p + kBaiFirstVo, 0xFF, 8, s));
+            }
+            const bool whole = for_each_record_batch(c, batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+                if (on_device) {
+                    const uint64_t cap = nrec / 4 + 4096;
+                    d_runs.ensure((size_t)cap);
+                    SBX_HIP(hipMemsetAsync(d_scalars.p + kBaiNumRuns, 0, 8, s));
+                    BaiArgs a{};
+                    a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.rec_base = rec_base;
+                    a.u_base = base; a.u_next = next;
+                    a.coff = d_coff.p; a.ustart = d_ustart.p; a.n_blocks = (uint32_t)nbk; a.file_end = file_end_coff;
+                    a.carry = carry; a.n_ref = n_ref;
+                    a.lin = d_lin.p; a.lin_off = d_lin_off.p; a.lin_len = d_lin_len.p;
+                    a.meta_end = d_meta.p; a.n_mapped = d_meta.p + (n_ref + 1); a.n_unmapped = d_meta.p + 2 * ((size_t)n_ref + 1);
+                    a.scalars = d_scalars.p; a.runs = d_runs.p; a.runs_cap = cap;
+                    launch_bai_records(a, d_carry.p, s);
+                    unsigned long long sc[kBaiScalars];
+                    SBX_HIP(hipMemcpyAsync(sc, d_scalars.p, sizeof sc, hipMemcpyDeviceToHost, s));
+                    SBX_HIP(hipMemcpyAsync(&carry, d_carry.p, sizeof carry, hipMemcpyDeviceToHost, s));
+                    SBX_HIP(hipStreamSynchronize(s));
+                    if (sc[kBaiIrregular] || sc[kBaiNumRuns] > cap) return false;
+                    const size_t at = R.runs.size(), nr = (size_t)sc[kBaiNumRuns];
+                    R.runs.resize(at + nr);
+                    if (nr) SBX_HIP(hipMemcpy(R.runs.data() + at, d_runs.p, nr * sizeof(BaiRun), hipMemcpyDeviceToHost));
+                    rec_base += nrec;
+                } else {
+                    d_bins.ensure((size_t)nrec + 1);
+                    launch_gather_bins(c->U(), c->d_desc.p, nrec, d_bins.p, s);
+                    desc.resize((size_t)nrec); ref.resize((size_t)nrec); bins.resize((size_t)nrec);
+                    SBX_HIP(hipStreamSynchronize(s));
+                    if (nrec) {
+                        SBX_HIP(hipMemcpy(desc.data(), c->d_desc.p, (size_t)nrec * sizeof(RecDesc), hipMemcpyDeviceToHost));
+                        SBX_HIP(hipMemcpy(ref.data(), c->d_rec_ref.p, (size_t)nrec * 4, hipMemcpyDeviceToHost));
+                        SBX_HIP(hipMemcpy(bins.data(), d_bins.p, (size_t)nrec * 2, hipMemcpyDeviceToHost));
+                    }
+                    for (uint64_t i = 0; i < nrec; ++i) {
+                        const uint64_t at = base + desc[(size_t)i].rec_off;
+                        if (have_held) { held.end_vo = vc.behind(at); bb.put(held); }
+                        held.ref_id = ref[(size_t)i];
+                        held.position = desc[(size_t)i].pos;
+                        held.end_position = desc[(size_t)i].end;
+                        held.bin = bins[(size_t)i];
+                        held.is_unmapped = (desc[(size_t)i].flag & 0x4) != 0;
+                        held.start_vo = vc.of_byte(at);
+                        have_held = true;
+                    }
+                }
+                return true;
+            });
+            if (!whole) return false;
+            if (on_device) {
+                const size_t m = (size_t)n_ref + 1;
+                R.lin.resize(d_lin.n); R.lin_len.resize(m); R.meta_end.resize(m); R.n_mapped.resize(m); R.n_unmapped.resize(m);
+                unsigned long long sc[kBaiScalars];
+                SBX_HIP(hipMemcpy(R.lin.data(), d_lin.p, d_lin.n * 8, hipMemcpyDeviceToHost));
+                SBX_HIP(hipMemcpy(R.lin_len.data(), d_lin_len.p, m * 4, hipMemcpyDeviceToHost));
+                SBX_HIP(hipMemcpy(R.meta_end.data(), d_meta.p, m * 8, hipMemcpyDeviceToHost));
+                SBX_HIP(hipMemcpy(R.n_mapped.data(), d_meta.p + m, m * 8, hipMemcpyDeviceToHost));
+                SBX_HIP(hipMemcpy(R.n_unmapped.data(), d_meta.p + 2 * m, m * 8, hipMemcpyDeviceToHost));
+                SBX_HIP(hipMemcpy(sc, d_scalars.p, sizeof sc, hipMemcpyDeviceToHost));
+                for (int k = 0; k < (int)kBaiScalars; ++k) R.scalars[k] = sc[k];
+                R.last = carry;
+                bytes = bai_assemble(n_ref, R);
+            } else {
+                if (have_held) { held.end_vo = vc.behind(total); bb.put(held); }
+                bytes = bb.finish();
+            }
+            return true;
+        };
+        const bool host_only = getenv("SBX_BAI_HOST") != nullptr;
+        bool on_device = !host_only;
+        if (on_device && !pass(true)) on_device = false;
+        if (!on_device) pass(false);
+        if (getenv("SBX_TIMING"))
+            fprintf(stderr, "[sbx] build_index: %u batch(es) of <= %llu inflated bytes, records consumed %s\n", n_batches, (unsigned long long)batch_u,
+                    on_device ? "on the device" : "by the serial builder on the host");
+        FILE* f = fopen(bai_path, "wb");
+        if (!f) throw Error(SBX_EIO, std::string("cannot write ") + bai_path);
+        const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + bai_path);
+        sbx_close(c);
+        return SBX_OK;
+    } catch (const Error& e) {
+        set_err(err, errlen, e.what());
+        if (c) sbx_close(c);
+        return e.code;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        if (c) sbx_close(c);
+        return SBX_EINVAL;
+    }
+}
+
+// `sambamba flagstat` (computeFlagStatistics, flagstat.d:31-58): one pass like sbx_build_index's -- index mode, no filter, no sort
+// order or index required -- with K8 (flagstat.hip) adding each batch's records to 26 device counters, read back once at the end.
+// Every record of the chain is counted, also one that index mode calls bad (refID out of range, lengths that disagree with
+// block_size) or one that starts beyond its contig: the reference reads nothing but the flags, mapq and the two reference ids.
+int sbx_flagstat(const char* bam_path, int device, sbx_flagstat_counts* out, char* err, size_t errlen) {
+    static_assert(sizeof(sbx_flagstat_counts) == 26 * sizeof(uint64_t), "sbx_flagstat_counts is the kernel's 26 counters");
+    sbx_ctx* c = nullptr;
+    try {
+        if (!bam_path || !out) throw Error(SBX_EINVAL, "null argument");
+        const double w0 = wall_now();
+        const char* one[1] = {bam_path};
+        char e2[512] = {0};
+        c = sbx_open(one, 1, device, e2, sizeof e2);
+        if (!c) throw Error(t_open_code != SBX_OK ? t_open_code : SBX_EIO, e2);
+        c->index_mode = true;
+        memset(&c->filter, 0, sizeof c->filter);         // no filter: every record is described
+        c->mode = SBX_MODE_BASE;
+        c->fix_mate = false;
+        hipStream_t s = c->stream.get();
+        DevBuf<unsigned long long> d_counts(26);
+        SBX_HIP(hipMemsetAsync(d_counts.p, 0, d_counts.bytes(), s));
+        const bool timing = getenv("SBX_TIMING") != nullptr;
+        const double w1 = wall_now();
+        EventTimer t_k;
+        double ms_inflate = 0, ms_index = 0, ms_k8 = 0;
+        uint64_t n_records = 0;
+        uint32_t n_batches = 0;
+        for_each_record_batch(c, index_batch_bytes(), &n_batches, [&](uint64_t nrec, uint64_t, uint64_t) -> bool {
+            t_k.start(s);
+            launch_flagstat(c->U(), c->d_desc.p, c->d_rec_ref.p, nrec, d_counts.p, s);
+            t_k.stop(s);
+            // (the next batch's K2 overwrites these descriptors, and may reallocate them, from the host side: K8 ends first)
+            SBX_HIP(hipStreamSynchronize(s));
+            if (timing) { ms_inflate += c->stats.ms_inflate; ms_index += c->stats.ms_index; ms_k8 += t_k.ms(); }
+            n_records += nrec;
+            return true;
+        });
+        sbx_flagstat_counts r{};
+        SBX_HIP(hipMemcpyAsync(&r, d_counts.p, sizeof r, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        if (r.reads[0] + r.reads[1] != n_records)
+            throw Error(SBX_EFORMAT, "internal error: flagstat counted " + std::to_string(r.reads[0] + r.reads[1]) + " of " +
+                                         std::to_string(n_records) + " records");
+        *out = r;
+        if (timing)
+            fprintf(stderr, "[sbx] flagstat: %llu records in %u batch(es): inflate %.2f ms, record index %.2f ms, flagstat kernel %.3f ms; "
+                            "open %.1f ms, pass %.1f ms (wall)\n", (unsigned long long)n_records, n_batches, ms_inflate, ms_index, ms_k8,
+                    (w1 - w0) * 1e3, (wall_now() - w1) * 1e3);
+        sbx_close(c);
+        return SBX_OK;
+    } catch (const Error& e) {
+        set_err(err, errlen, e.what());
+        if (c) sbx_close(c);
+        return e.code;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        if (c) sbx_close(c);
+        return SBX_EINVAL;
+    }
+}
+
+extern "C++" {
+namespace {
+// percent / percentStr of flagstat.d:66-72: to!float(a) / b is single precision, `* 100.0` double, returned as float
+void percent_str(uint64_t a, uint64_t b, char* buf, size_t n) {
+    if (b == 0) { snprintf(buf, n, "N/A"); return; }
+    const float p = (float)((double)((float)a / (float)b) * 100.0);
+    snprintf(buf, n, "%.2f%%", (double)p);
+}
+}  // namespace
+}  // extern "C++"
+
+int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, size_t cap, size_t* len) {
+    if (!f) return SBX_EINVAL;
+    std::string out;
+    char line[256], p0[32], p1[32];
+    auto param = [&](const char* what, const uint64_t* v) {
+        if (tabular) snprintf(line, sizeof line, "%s,%llu,%llu\n", what, (unsigned long long)v[0], (unsigned long long)v[1]);
+        else snprintf(line, sizeof line, "%llu + %llu %s\n", (unsigned long long)v[0], (unsigned long long)v[1], what);
+        out += line;
+    };
+    auto with_pct = [&](const char* what, const uint64_t* v, const uint64_t* total) {
+        percent_str(v[0], total[0], p0, sizeof p0);
+        percent_str(v[1], total[1], p1, sizeof p1);
+        if (tabular) snprintf(line, sizeof line, "%s,%llu:%s,%llu:%s\n", what, (unsigned long long)v[0], p0, (unsigned long long)v[1], p1);
+        else snprintf(line, sizeof line, "%llu + %llu %s (%s:%s)\n", (unsigned long long)v[0], (unsigned long long)v[1], what, p0, p1);
+        out += line;
+    };
+    // flagstat.d:131-143
+    param("in total (QC-passed reads + QC-failed reads)", f->reads);
+    param("secondary", f->secondary);
+    param("supplementary", f->supplementary);
+    param("duplicates", f->dup);
+    with_pct("mapped", f->mapped, f->reads);
+    param("paired in sequencing", f->pair_all);
+    param("read1", f->first);
+    param("read2", f->second);
+    with_pct("properly paired", f->pair_good, f->pair_all);
+    param("with itself and mate mapped", f->pair_map);
+    with_pct("singletons", f->single, f->pair_all);
+    param("with mate mapped to a different chr", f->diff_chr);
+    param("with mate mapped to a different chr (mapQ>=5)", f->diff_high);
+    if (len) *len = out.size();
+    if (!buf || out.size() + 1 > cap) return SBX_ENOMEM;
+    memcpy(buf, out.data(), out.size());
+    buf[out.size()] = 0;
+    return SBX_OK;
+}
+
+int sbx_write_bam(const char* path, const uint8_t* stream, size_t n, int level, int with_index, int device, char* err, size_t errlen) {
+    try {
+        if (!path || (!stream && n)) throw Error(SBX_EINVAL, "null argument");
+        if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
+        require_device(device);
+        FILE* f = fopen(path, "wb");
+        if (!f) throw Error(SBX_EIO, std::string("cannot write ") + path);
+        bool ok = true;
+        try {
+            bgzf_compress_stream(stream, n, level, [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
+        } catch (...) { fclose(f); throw; }
+        ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
+        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + path);
+    } catch (const Error& e) {
+        set_err(err, errlen, e.what());
+        return e.code;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return SBX_EINVAL;
+    }
+    if (with_index) return sbx_build_index(path, (std::string(path) + ".bai").c_str(), device, err, errlen);
+    return SBX_OK;
+}
+
+}  // extern "C"

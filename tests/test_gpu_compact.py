@@ -1,5 +1,5 @@
 """Region / window runs keep ONE word per position and sample -- {bases counted, depth} -- instead of the seven base counters
-(engine.cpp `compact_counters`, depth.hip write-out, reduce.hip k_range_reduce): what PerRegionPrinter / PerWindowPrinter print is a
+(engine_run.cpp `compact_counters`, depth.hip write-out, reduce.hip k_range_reduce): what PerRegionPrinter / PerWindowPrinter print is a
 sum over those two numbers (sambamba/depth.d:661-698,760-845,933-1077).  The form with the seven counters (SBX_COMPACT=0) is the
 witness: same text; and the C ABI says what it no longer holds after such a run."""
 import os

@@ -1,4 +1,4 @@
-"""The device work list (engine.cpp build_runs): with -L / sbx_run_interval only the BGZF block runs that hold the
+"""The device work list (engine_worklist.cpp build_runs): with -L / sbx_run_interval only the BGZF block runs that hold the
 merged BAI chunks are uploaded and inflated (RandomAccessManager.getChunks / getReads, randomaccessmanager.d:247-348),
 every run starting at a record boundary the index names -- results must not depend on how the file was cut."""
 import os
