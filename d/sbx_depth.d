@@ -81,6 +81,14 @@ extern (C) nothrow @nogc {
     }
     int sbx_flagstat(const(char)* bam_path, int device, sbx_flagstat_counts* out_, char* err, size_t errlen);
     int sbx_format_flagstat(const(sbx_flagstat_counts)* f, int tabular, char* buf, size_t cap, size_t* len);
+    struct sbx_sort_stats {
+        ulong n_records_in; ulong n_records_out; ulong inflated_bytes; ulong sorted_stream_bytes; ulong compressed_bytes;
+        uint key_bits; uint n_sort_passes; uint n_batches; uint reserved;
+        double ms_inflate; double ms_index; double ms_keys; double ms_sort; double ms_gather; double ms_deflate; double ms_total_wall;
+    }
+    int sbx_sort_bam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, int level, int with_index, int device,
+                     sbx_sort_stats* stats, char* err, size_t errlen);
+    int sbx_sort_header_text(const(char)* text, size_t n, char* out_, size_t cap, size_t* out_len);
     int sbx_inflate_blocks(const(ubyte)* comp, const(ulong)* comp_off, const(uint)* comp_len, const(uint)* isize,
                            uint n_blocks, ubyte* out_, const(ulong)* out_off, char* err, size_t errlen);
     sbx_ctx* sbx_open(const(char*)* bam_paths, int n_bams, int device, char* err, size_t errlen);

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -191,6 +191,27 @@ int sbx_flagstat(const char* bam_path, int device, sbx_flagstat_counts* out, cha
  * as percent() does, in single precision (flagstat.d:66-72).  *len receives the length of the text (without the terminating zero,
  * which is written too); SBX_ENOMEM when buf is null or cap is too small. */
 int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, size_t cap, size_t* len);
+
+/* `sambamba sort` in coordinate order (sambamba/sort.d, default mode): compareCoordinatesAndStrand applied by a stable sort -- ref_id -1
+ * last, ascending ref_id, ascending position (signed), forward strand first, ties in file order.  The input needs no sort order and no
+ * index.  Records are copied byte for byte; the header text is re-serialised with SO:coordinate (sbx_sort_header_text).  The whole
+ * file is sorted on the device: one whose inflated records do not fit next to one batch of the read pass is refused with SBX_ENOMEM.
+ * Milliseconds are device time of the kernels (inflate = K1, index = K2, keys = K9a + the copy into the record store, sort = K9b,
+ * gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index. */
+typedef struct {
+    uint64_t n_records_in, n_records_out;      /* out < in only with a filter */
+    uint64_t inflated_bytes, sorted_stream_bytes, compressed_bytes;
+    uint32_t key_bits, n_sort_passes, n_batches, reserved;    /* key_bits: width of the stretch of key bits in which records differ */
+    double ms_inflate, ms_index, ms_keys, ms_sort, ms_gather, ms_deflate, ms_total_wall;
+} sbx_sort_stats;
+/* filter == NULL: every record (not depth's default filter); otherwise only the records the filter admits are written.
+ * level as sbx_bgzf_compress.  with_index != 0: out_path + ".bai" too.  stats may be NULL.  SBX_EINVAL when out_path is the input. */
+int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* filter, int level, int with_index,
+                 int device, sbx_sort_stats* stats, char* err, size_t errlen);
+/* The output header text for an input header text (host only; what SamHeader.toSam prints after sort.d:294-298).  *out_len receives
+ * the length (without the terminating zero, also with SBX_ENOMEM when cap is too small); SBX_EFORMAT for a text the reference's
+ * parser throws on. */
+int sbx_sort_header_text(const char* text, size_t n, char* out, size_t cap, size_t* out_len);
 
 /* ---- engine seam ------------------------------------------------------------ */
 

@@ -8,6 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(HERE, "csrc", "libsbx_depth.so")
 _CLI_PATH = os.path.join(HERE, "csrc", "sbx-depth")
 _FLAGSTAT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-flagstat")
+_SORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sort")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -82,6 +83,11 @@ FLAGSTAT_FIELDS = ("reads", "secondary", "supplementary", "dup", "mapped", "pair
 class Flagstat(C.Structure):
     _fields_ = [(k, C.c_uint64 * 2) for k in FLAGSTAT_FIELDS]
 
+class SortStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_records_in", "n_records_out", "inflated_bytes", "sorted_stream_bytes", "compressed_bytes")] +
+                [(k, C.c_uint32) for k in ("key_bits", "n_sort_passes", "n_batches", "reserved")] +
+                [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_keys", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
+
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
 
 EXPORTS = [
@@ -91,6 +97,7 @@ EXPORTS = [
     "sbx_depth_window_stats",
     "sbx_format_base_rows", "sbx_stream_base_rows", "sbx_plan_batches", "sbx_run_batch", "sbx_last_run_stats", "sbx_tile_info", "sbx_next_active_range", "sbx_preload",
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
+    "sbx_sort_bam", "sbx_sort_header_text",
 ]
 
 _lib = None
@@ -106,6 +113,10 @@ def cli_path():
 
 def flagstat_cli_path():
     return _FLAGSTAT_CLI_PATH
+
+
+def sort_cli_path():
+    return _SORT_CLI_PATH
 
 
 def lib():
@@ -164,6 +175,8 @@ def lib():
     L.sbx_build_index.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_size_t]
     L.sbx_flagstat.argtypes = [C.c_char_p, C.c_int, C.POINTER(Flagstat), C.c_char_p, C.c_size_t]
     L.sbx_format_flagstat.argtypes = [C.POINTER(Flagstat), C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sbx_sort_bam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.POINTER(SortStats), C.c_char_p, C.c_size_t]
+    L.sbx_sort_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_depth_base_tile_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -178,7 +191,8 @@ def lib():
     # the structures above must have the layout the library was compiled with
     for name, ty in (("sbx_region", Region), ("sbx_header_info", HeaderInfo), ("sbx_region_stats", RegionStats),
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
-                     ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat)):
+                     ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
+                     ("sbx_sort_stats", SortStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -260,6 +274,36 @@ def format_flagstat(counts, tabular=False):
     if rc != 0:
         raise SbxError(rc, "sbx_format_flagstat failed")
     return buf.raw[:n.value].decode()
+
+
+def sort_bam(in_path, out_path, filter=None, level=-1, index=False, device=-1):
+    """sbx_sort_bam (`sambamba sort`, coordinate order): sorts in_path into out_path on the device; filter is a -F query string (None:
+    every record); index=True also writes out_path + ".bai".  Returns the fields of sbx_sort_stats as a dict."""
+    L = lib()
+    f = compile_filter(filter) if filter else None
+    st = SortStats()
+    err = C.create_string_buffer(512)
+    rc = L.sbx_sort_bam(in_path.encode(), out_path.encode(), C.byref(f) if f is not None else None, int(level), int(index), device,
+                        C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: getattr(st, k) for k, _ in SortStats._fields_ if k != "reserved"}
+
+
+def sort_header_text(text):
+    """sbx_sort_header_text: the header text `sambamba sort` writes for the input header text (str or bytes -> same type), host only."""
+    L = lib()
+    data = text if isinstance(text, bytes) else text.encode()
+    n = C.c_size_t(0)
+    rc = L.sbx_sort_header_text(data, len(data), None, 0, C.byref(n))
+    if rc not in (0, -8):
+        raise SbxError(rc, "malformed SAM header text")
+    buf = C.create_string_buffer(n.value + 1)
+    rc = L.sbx_sort_header_text(data, len(data), buf, n.value + 1, C.byref(n))
+    if rc != 0:
+        raise SbxError(rc, "sbx_sort_header_text failed")
+    out = buf.raw[:n.value]
+    return out if isinstance(text, bytes) else out.decode()
 
 
 def regex_search(pattern, text, options=""):

@@ -55,6 +55,7 @@ size_t sbx_abi_sizeof(const char* name) {
     if (n == "sbx_run_stats") return sizeof(sbx_run_stats);
     if (n == "sbx_shard") return sizeof(sbx_shard);
     if (n == "sbx_flagstat_counts") return sizeof(sbx_flagstat_counts);
+    if (n == "sbx_sort_stats") return sizeof(sbx_sort_stats);
     return 0;
 }
 

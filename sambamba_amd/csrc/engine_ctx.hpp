@@ -114,6 +114,7 @@ struct sbx_ctx {
     sbx_filter filter;
     std::vector<sbx_region> regions;
     bool index_mode = false;        // sbx_build_index: every record is described, no index / sort order / read group is required, no K3
+    bool filter_every = false;      // sbx_sort_bam with a filter (index mode): K2 asks the filter about every record (IndexArgs::filter_every)
     // read ownership of the next run (sbx_run_interval_owned): own_ref >= 0
     int32_t own_ref = -1;
     uint32_t own_beg = 0, own_end = 0;

@@ -195,6 +195,7 @@ static IndexArgs fill_index_args(sbx_ctx* c, const RefTable& refs, const RgTable
     a.tile_lo = c->d_tile_lo.p; a.tile_hi = c->d_tile_hi.p; a.stats = c->d_stats.p; a.flags = c->d_flag.p;
     a.scan_part = c->d_scan_part.p;
     a.own_ref = c->own_ref; a.own_beg = c->own_beg; a.own_end = c->own_end;
+    a.filter_every = c->filter_every ? 1u : 0u;
     return a;
 }
 

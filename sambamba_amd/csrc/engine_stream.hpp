@@ -1,0 +1,137 @@
+// engine_stream.hpp -- the two streaming loops engine_writer.cpp and engine_sort.cpp share: BGZF compression of a byte stream piece by
+// piece on the device (bgzf_compress_pieces: the source of a piece is a callback -- a copy from host memory for sbx_bgzf_compress /
+// sbx_write_bam, a gather on the device for sbx_sort_bam) and the index-mode pass over the records of a file in batches
+// (for_each_record_batch: sbx_build_index, sbx_flagstat, sbx_sort_bam).
+#pragma once
+#include <algorithm>
+#include <cstdlib>
+
+#include "deflate_core.hpp"
+#include "engine_ctx.hpp"
+
+namespace sbx {
+
+constexpr uint8_t kEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+constexpr size_t kBgzfPieceBlocks = 32768;      // BGZF blocks compressed per launch: a piece of the stream is at most this many payloads
+
+struct BgzfPieceTimes { double ms_fill = 0, ms_deflate = 0, ms_pack = 0, ms_d2h = 0; uint64_t out_bytes = 0; };
+
+// Compresses a stream of n bytes piece by piece on the device.  fill(d_in, done, bytes, s) puts bytes [done, done + bytes) of the stream
+// at d_in, in order on stream s; sink(data, len) receives consecutive pieces of the BGZF stream.  Blocks are cut every kBgzfPayload
+// bytes.  pinned: the compressed piece travels through pinned host memory.  times (may be null) accumulates; the wall-clock figures
+// (fill, device -> host) are taken only when `timing`, which synchronises after the fill.
+template <class Fill, class Sink>
+void bgzf_compress_pieces(size_t n, int level, bool pinned, bool timing, BgzfPieceTimes* times, Fill&& fill, Sink&& sink) {
+    Stream stream;
+    stream.create();
+    hipStream_t s = stream.get();
+    const size_t n_blocks_total = (n + kBgzfPayload - 1) / kBgzfPayload;
+    const uint32_t cap_blocks = (uint32_t)std::min<size_t>(kBgzfPieceBlocks, std::max<size_t>(1, n_blocks_total));
+    DevBuf<uint8_t> d_in((size_t)cap_blocks * kBgzfPayload + 64), d_slots((size_t)cap_blocks * kBgzfSlot), d_out((size_t)cap_blocks * kBgzfSlot);
+    DevBuf<uint16_t> d_tab(deflate_table_entries(cap_blocks));
+    DevBuf<uint8_t> d_work(deflate_work_bytes(cap_blocks));
+    DevBuf<uint32_t> d_len(cap_blocks + 1);
+    DevBuf<uint64_t> d_off((size_t)cap_blocks + 2);
+    std::vector<uint8_t> host;
+    PinnedBuf<uint8_t> host_pinned;
+    EventTimer t_def, t_pack;
+    for (size_t done = 0; done < n;) {
+        const size_t bytes = std::min<size_t>(n - done, (size_t)cap_blocks * kBgzfPayload);
+        const uint32_t nb = (uint32_t)((bytes + kBgzfPayload - 1) / kBgzfPayload);
+        const double w0 = wall_now();
+        fill(d_in.p, done, bytes, s);
+        if (timing) SBX_HIP(hipStreamSynchronize(s));
+        const double w1 = wall_now();
+        t_def.start(s);
+        launch_bgzf_deflate(d_in.p, bytes, nb, level, d_slots.p, d_tab.p, d_work.p, d_len.p, s);
+        t_def.stop(s);
+        t_pack.start(s);
+        launch_count_scan(d_len.p, nb, d_off.p, nullptr, 0, s);
+        launch_pack_blocks(d_slots.p, d_len.p, d_off.p, nb, d_out.p, s);
+        t_pack.stop(s);
+        uint64_t total = 0;
+        SBX_HIP(hipMemcpyAsync(&total, d_off.p + nb, 8, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        const double w2 = wall_now();
+        uint8_t* h;
+        if (pinned) { host_pinned.ensure((size_t)total + 1); h = host_pinned.p; }
+        else { host.resize((size_t)total); h = host.data(); }
+        SBX_HIP(hipMemcpy(h, d_out.p, (size_t)total, hipMemcpyDeviceToHost));
+        if (times) {
+            times->ms_deflate += t_def.ms(); times->ms_pack += t_pack.ms(); times->out_bytes += total;
+            if (timing) { times->ms_fill += (w1 - w0) * 1e3; times->ms_d2h += (wall_now() - w2) * 1e3; }
+        }
+        sink(h, (size_t)total);
+        done += bytes;
+    }
+}
+
+// compresses in[0, n) (host memory) piece by piece on the device; sink(data, len) receives consecutive pieces of the BGZF stream
+template <class Sink>
+void bgzf_compress_stream(const uint8_t* in, size_t n, int level, Sink&& sink) {
+    const bool timing = getenv("SBX_TIMING") != nullptr;
+    BgzfPieceTimes t;
+    bgzf_compress_pieces(n, level, false, timing, &t,
+                         [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t s) {
+                             SBX_HIP(hipMemcpyAsync(d_in, in + done, bytes, hipMemcpyHostToDevice, s));
+                         },
+                         sink);
+    if (timing)
+        fprintf(stderr, "[sbx] bgzf_compress: %zu bytes -> %llu in %zu blocks: host -> device %.1f ms (pageable), deflate kernel %.1f ms (%.1f GB/s of input), "
+                        "scan + pack %.1f ms, device -> host %.1f ms\n", n, (unsigned long long)t.out_bytes, (n + kBgzfPayload - 1) / kBgzfPayload,
+                t.ms_fill, t.ms_deflate, t.ms_deflate > 0 ? (double)n / t.ms_deflate / 1e6 : 0.0, t.ms_pack, t.ms_d2h);
+}
+
+// ---- index-mode passes: the record stream of one file in batches (sbx_build_index, sbx_flagstat, sbx_sort_bam) ------------------------
+// Inflated bytes per batch: a batch holds its compressed bytes, its inflated bytes, the token streams and the descriptors -- about
+// five times its inflated size --, so the size follows the free device memory less `reserved` bytes the caller keeps for itself;
+// SBX_INDEX_BATCH_BYTES overrides it (tests).
+inline uint64_t index_batch_bytes(uint64_t reserved = 0) {
+    uint64_t batch_u = 0;
+    if (const char* e = getenv("SBX_INDEX_BATCH_BYTES")) batch_u = strtoull(e, nullptr, 10);
+    if (!batch_u) {
+        size_t free_b = 0, total_b = 0;
+        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t avail = free_b > reserved ? free_b - reserved : 0;
+        batch_u = std::max<uint64_t>(64ull << 20, (uint64_t)((double)avail * 0.7 / 5.0));
+    }
+    return batch_u;
+}
+
+// The file of an index-mode context goes through the device in batches of whole BGZF blocks -- inflate, record chain, descriptors.
+// A batch ends in front of the record that straddles its last block boundary (ChainRun::open_end: the chain stops there and that
+// record is not described) and the next batch starts with that record, so every record of the file is described in exactly one
+// batch.  consume(nrec, base, next) is called once per batch: records [0, nrec) of c->d_desc / c->d_rec_ref are the batch's, their
+// rec_off count from U[0] = inflated offset `base` of the file, and `next` is the inflated offset behind the batch's last record.
+// It returns false to stop the pass (then so does this function); *n_batches receives the number of batches handed over.
+template <class Consume>
+bool for_each_record_batch(sbx_ctx* c, uint64_t batch_u, uint32_t* n_batches, Consume&& consume) {
+    const BlockTable& bt = c->blocks;
+    const size_t nbk = bt.size();
+    const uint64_t total = bt.out_off.back(), first = c->hdr.first_record_off;
+    uint64_t bu = batch_u;
+    *n_batches = 0;
+    for (uint64_t cur = first; cur < total;) {
+        const uint32_t b0 = (uint32_t)(std::upper_bound(bt.out_off.begin(), bt.out_off.end(), cur) - bt.out_off.begin()) - 1;
+        uint32_t b1 = (uint32_t)(std::lower_bound(bt.out_off.begin() + b0, bt.out_off.end(), bt.out_off[b0] + bu) - bt.out_off.begin());
+        b1 = std::min<uint32_t>(std::max(b1, b0 + 1), (uint32_t)nbk);
+        if (bt.out_off[b1] >= total) b1 = (uint32_t)nbk;          // (whatever follows holds no bytes: EOF blocks)
+        const bool last = b1 == nbk;
+        const std::vector<FileRun> runs{FileRun{b0, b1, cur, last ? total : bt.out_off[b1], !last}};
+        run_impl(c, {}, false, &runs);
+        const uint64_t nrec = c->primary_records;
+        const uint64_t base = bt.out_off[b0];            // work-list offsets count from the batch's first block
+        const uint64_t next = last ? total : c->index_straddler != kOffUnknown ? base + c->index_straddler : bt.out_off[b1];
+        if (!last && next == cur) {                      // not one whole record in the batch: a longer batch
+            bu *= 2;
+            continue;
+        }
+        ++*n_batches;
+        if (!consume(nrec, base, next)) return false;
+        cur = next;
+    }
+    return true;
+}
+
+}  // namespace sbx

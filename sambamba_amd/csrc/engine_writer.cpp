@@ -1,6 +1,6 @@
 // engine_writer.cpp -- the write side and the passes over the record stream of one file: BGZF compression on the device
-// (sbx_bgzf_compress, sbx_write_bam), and the index-mode passes in batches (for_each_record_batch) behind sbx_build_index and
-// sbx_flagstat.
+// (sbx_bgzf_compress, sbx_write_bam), and the index-mode passes in batches (for_each_record_batch, engine_stream.hpp) behind
+// sbx_build_index and sbx_flagstat.  (sbx_sort_bam, which is both, lives in engine_sort.cpp.)
 #include <algorithm>
 #include <cstdlib>
 
@@ -8,61 +8,8 @@
 #include "bai_writer.hpp"
 #include "deflate_core.hpp"
 #include "engine_ctx.hpp"
+#include "engine_stream.hpp"
 #include "flagstat.hpp"
-
-// ---- the write side: BGZF compression, BAM files, BAI ---------------------------------------------------------------
-namespace {
-const uint8_t kEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
-// compresses in[0, n) piece by piece on the device; sink(data, len) receives consecutive pieces of the BGZF stream
-template <class Sink>
-void bgzf_compress_stream(const uint8_t* in, size_t n, int level, Sink&& sink) {
-    Stream stream;
-    stream.create();
-    hipStream_t s = stream.get();
-    const size_t piece_blocks = 32768;
-    const size_t n_blocks_total = (n + kBgzfPayload - 1) / kBgzfPayload;
-    const uint32_t cap_blocks = (uint32_t)std::min<size_t>(piece_blocks, std::max<size_t>(1, n_blocks_total));
-    DevBuf<uint8_t> d_in((size_t)cap_blocks * kBgzfPayload + 64), d_slots((size_t)cap_blocks * kBgzfSlot), d_out((size_t)cap_blocks * kBgzfSlot);
-    DevBuf<uint16_t> d_tab(deflate_table_entries(cap_blocks));
-    DevBuf<uint8_t> d_work(deflate_work_bytes(cap_blocks));
-    DevBuf<uint32_t> d_len(cap_blocks + 1);
-    DevBuf<uint64_t> d_off((size_t)cap_blocks + 2);
-    std::vector<uint8_t> host;
-    const bool timing = getenv("SBX_TIMING") != nullptr;
-    EventTimer t_def, t_pack;
-    double ms_h2d = 0, ms_def = 0, ms_pack = 0, ms_d2h = 0;
-    uint64_t out_total = 0;
-    for (size_t done = 0; done < n;) {
-        const size_t bytes = std::min<size_t>(n - done, (size_t)cap_blocks * kBgzfPayload);
-        const uint32_t nb = (uint32_t)((bytes + kBgzfPayload - 1) / kBgzfPayload);
-        const double w0 = wall_now();
-        SBX_HIP(hipMemcpyAsync(d_in.p, in + done, bytes, hipMemcpyHostToDevice, s));
-        if (timing) SBX_HIP(hipStreamSynchronize(s));
-        const double w1 = wall_now();
-        t_def.start(s);
-        launch_bgzf_deflate(d_in.p, bytes, nb, level, d_slots.p, d_tab.p, d_work.p, d_len.p, s);
-        t_def.stop(s);
-        t_pack.start(s);
-        launch_count_scan(d_len.p, nb, d_off.p, nullptr, 0, s);
-        launch_pack_blocks(d_slots.p, d_len.p, d_off.p, nb, d_out.p, s);
-        t_pack.stop(s);
-        uint64_t total = 0;
-        SBX_HIP(hipMemcpyAsync(&total, d_off.p + nb, 8, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        const double w2 = wall_now();
-        host.resize((size_t)total);
-        SBX_HIP(hipMemcpy(host.data(), d_out.p, (size_t)total, hipMemcpyDeviceToHost));
-        if (timing) { ms_h2d += (w1 - w0) * 1e3; ms_def += t_def.ms(); ms_pack += t_pack.ms(); ms_d2h += (wall_now() - w2) * 1e3; out_total += total; }
-        sink(host.data(), (size_t)total);
-        done += bytes;
-    }
-    if (timing)
-        fprintf(stderr, "[sbx] bgzf_compress: %zu bytes -> %llu in %zu blocks: host -> device %.1f ms (pageable), deflate kernel %.1f ms (%.1f GB/s of input), "
-                        "scan + pack %.1f ms, device -> host %.1f ms\n", n, (unsigned long long)out_total, n_blocks_total, ms_h2d, ms_def,
-                ms_def > 0 ? (double)n / ms_def / 1e6 : 0.0, ms_pack, ms_d2h);
-}
-}  // namespace
 
 extern "C" {
 
@@ -95,58 +42,6 @@ int sbx_bgzf_compress(const uint8_t* in, size_t n, int level, int with_eof, int 
 }
 
 // ---- index-mode passes: the record stream of one file in batches (sbx_build_index, sbx_flagstat) ---------------------------------
-extern "C++" {
-namespace {
-// Inflated bytes per batch: a batch holds its compressed bytes, its inflated bytes, the token streams and the descriptors -- about
-// five times its inflated size --, so the size follows the free device memory; SBX_INDEX_BATCH_BYTES overrides it (tests).
-uint64_t index_batch_bytes() {
-    uint64_t batch_u = 0;
-    if (const char* e = getenv("SBX_INDEX_BATCH_BYTES")) batch_u = strtoull(e, nullptr, 10);
-    if (!batch_u) {
-        size_t free_b = 0, total_b = 0;
-        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
-        batch_u = std::max<uint64_t>(64ull << 20, (uint64_t)((double)free_b * 0.7 / 5.0));
-    }
-    return batch_u;
-}
-
-// The file of an index-mode context goes through the device in batches of whole BGZF blocks -- inflate, record chain, descriptors.
-// A batch ends in front of the record that straddles its last block boundary (ChainRun::open_end: the chain stops there and that
-// record is not described) and the next batch starts with that record, so every record of the file is described in exactly one
-// batch.  consume(nrec, base, next) is called once per batch: records [0, nrec) of c->d_desc / c->d_rec_ref are the batch's, their
-// rec_off count from U[0] = inflated offset `base` of the file, and `next` is the inflated offset behind the batch's last record.
-// It returns false to stop the pass (then so does this function); *n_batches receives the number of batches handed over.
-template <class Consume>
-bool for_each_record_batch(sbx_ctx* c, uint64_t batch_u, uint32_t* n_batches, Consume&& consume) {
-    const BlockTable& bt = c->blocks;
-    const size_t nbk = bt.size();
-    const uint64_t total = bt.out_off.back(), first = c->hdr.first_record_off;
-    uint64_t bu = batch_u;
-    *n_batches = 0;
-    for (uint64_t cur = first; cur < total;) {
-        const uint32_t b0 = (uint32_t)(std::upper_bound(bt.out_off.begin(), bt.out_off.end(), cur) - bt.out_off.begin()) - 1;
-        uint32_t b1 = (uint32_t)(std::lower_bound(bt.out_off.begin() + b0, bt.out_off.end(), bt.out_off[b0] + bu) - bt.out_off.begin());
-        b1 = std::min<uint32_t>(std::max(b1, b0 + 1), (uint32_t)nbk);
-        if (bt.out_off[b1] >= total) b1 = (uint32_t)nbk;          // (whatever follows holds no bytes: EOF blocks)
-        const bool last = b1 == nbk;
-        const std::vector<FileRun> runs{FileRun{b0, b1, cur, last ? total : bt.out_off[b1], !last}};
-        run_impl(c, {}, false, &runs);
-        const uint64_t nrec = c->primary_records;
-        const uint64_t base = bt.out_off[b0];            // work-list offsets count from the batch's first block
-        const uint64_t next = last ? total : c->index_straddler != kOffUnknown ? base + c->index_straddler : bt.out_off[b1];
-        if (!last && next == cur) {                      // not one whole record in the batch: a longer batch
-            bu *= 2;
-            continue;
-        }
-        ++*n_batches;
-        if (!consume(nrec, base, next)) return false;
-        cur = next;
-    }
-    return true;
-}
-}  // namespace
-}  // extern "C++"
-
 int sbx_build_index(const char* bam_path, const char* bai_path, int device, char* err, size_t errlen) {
     sbx_ctx* c = nullptr;
     try {

@@ -642,11 +642,17 @@ __device__ __forceinline__ Described describe_record(const uint8_t* p, const uin
     const int64_t fixed = 32 + (int64_t)l_name + 4 * (int64_t)n_cigar + ((int64_t)(l_seq < 0 ? 0 : l_seq) + 1) / 2 + (l_seq < 0 ? 0 : l_seq);
     const bool sane = l_seq >= 0 && bs >= fixed && ref_own >= -1 && ref_own < a.refs.n_ref_own;
     R.bad = !sane;
-    bool admit = sane && !(flag & 0x4) && ref >= 0;                       // read.d:256, unmapped reads cover nothing
+    // (sort -F: `filtered(reads, filter)`, sort.d:261-266, asks the filter about every read, mapped or not)
+    const bool covers = !(flag & 0x4) && ref >= 0;                        // read.d:256, unmapped reads cover nothing
+    bool admit = sane && (covers || a.filter_every);
     const uint8_t* const tags_end = kStaged ? tail_end : r + bs;
     const uint8_t* const tags = kStaged ? tail_end - (bs - fixed) : r + fixed;
     if (admit) admit = kSimpleFilter ? eval_filter_simple(a.filt, r, ref, pos, bmn, fnc, l_seq)
                                      : eval_filter(a.filt, r, ref, pos, bmn, fnc, l_seq, tags, tags_end);      // filtering.d:36-38
+    if (a.filter_every) {
+        d.pad = !sane ? kFilterBad : admit ? kFilterPass : kFilterReject;
+        admit = admit && covers;
+    }
     if (admit) {
         // basesCovered + shape of the CIGAR
         const uint8_t* cg = r + 32 + l_name;

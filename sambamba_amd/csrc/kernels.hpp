@@ -159,7 +159,11 @@ struct IndexArgs {
     unsigned long long* scan_part;  // kScanPartWords words of scratch for the multi-workgroup scans (nullptr: single-workgroup kernels)
     uint32_t* flags;                // [0] lowest block with an inconsistent chain (0xFFFFFFFF: none), [1] lowest block whose
                                     // inflate failed, [2] != 0: desc_cap was too small (nothing useful was written)
+    uint32_t filter_every;          // != 0 (sbx_sort_bam with -F): the filter is evaluated on EVERY well-formed record, also an unmapped
+                                    // one, and RecDesc::pad receives the verdict (kFilterPass / kFilterReject / kFilterBad)
 };
+// RecDesc::pad under IndexArgs::filter_every (0 otherwise)
+constexpr uint8_t kFilterReject = 0, kFilterPass = 1, kFilterBad = 2;
 constexpr uint32_t kScanPartWords = 4096;      // 16 M blocks / tiles per launch of the multi-workgroup scans
 void launch_index_blocks(const IndexArgs& a, hipStream_t stream);
 // parallel repair round: blocks not entered where their predecessor was left are walked again from there

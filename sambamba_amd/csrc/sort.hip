@@ -1,0 +1,353 @@
+// sort.hip -- K9: the device side of `sambamba sort` in coordinate order (sambamba/sort.d, default mode).
+//
+//   K9a  k_sort_keys      one lane per described record of a batch: the 64-bit key (sort_core.hpp) from rec_ref, RecDesc::pos and
+//                         RecDesc::flag, the record's length (block_size + 4, read from U at any byte address) and its offset in the
+//                         resident record store.  With -F the records the filter rejects (RecDesc::pad, written by K2) are compacted
+//                         away: ballot + prefix inside a wave, the waves of a workgroup through LDS, the workgroups through an
+//                         exclusive scan of their counts (k_sort_group_count) -- so the kept records stay in file order, which is what
+//                         makes the sort below stable with respect to the file.  The kernel also folds the keys into an OR and an AND
+//                         word: the bits in which two keys of the file differ are the only ones K9b has to sort.
+//   K9b  k_radix_hist /   stable LSD radix sort of (key, record number), 8 bits per pass.  A workgroup of four waves owns a tile of
+//        k_radix_scatter  4096 consecutive elements and takes them in sixteen rounds of 256.  Histogram: LDS atomics, one counter row
+//                         per tile, laid out [digit][tile] so that one exclusive scan (launch_count_scan) yields the first output
+//                         slot of every (digit, tile).  Scatter: inside a wave the lanes with the same digit find one another with
+//                         eight ballots (one per digit bit); the lane's rank among them is a popcount below its own lane, the lowest
+//                         of them publishes the count in the wave's row of LDS, and a lane's slot is the tile's running offset of its
+//                         digit + the counts of the waves in front + its rank -- input order, hence stable.  No atomics in the scatter.
+//   K9c  k_gather_records sixteen lanes per record: the record's bytes go from the store to their place in a piece of the sorted
+//                         stream.  Both ends sit at arbitrary byte addresses; the destination is brought to a 16-byte boundary with
+//                         a head of single bytes, the body moves 16 bytes per lane (aligned store, unaligned load -- gfx950 takes
+//                         global loads at any byte address), the tail is single bytes again.  A piece is a whole number of BGZF
+//                         payloads; a record that straddles a piece boundary is copied in part by both pieces.
+//
+// Bytes moved (n records, b bytes of records): K9a reads 36 n (descriptor, rec_ref) + 4 n scattered words of U and writes 20 n; a pass of
+// K9b reads 12 n twice (histogram: keys only, 8 n) and writes 12 n; the offsets read 8 n and write 8 n; K9c reads and writes b.
+#include "common.hpp"
+#include "sort.hpp"
+#include "sort_core.hpp"
+
+namespace sbx {
+
+namespace {
+
+__device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << (threadIdx.x & 63u)) - 1ull; }
+
+// ---- K9a -----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kSortKeysThreads) void k_sort_group_count(const RecDesc* __restrict__ desc, uint64_t n, uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t wcnt[kSortKeysThreads / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kSortKeysThreads + threadIdx.x;
+    const bool keep = i < n && desc[i].pad == kFilterPass;
+    const unsigned long long m = __ballot(keep);
+    if ((threadIdx.x & 63u) == 0) wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (uint32_t w = 0; w < kSortKeysThreads / 64; ++w) s += wcnt[w];
+        cnt[blockIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(kSortKeysThreads) void k_sort_keys(SortKeysArgs a, const uint64_t* __restrict__ group_base) {
+    __shared__ uint32_t wcnt[kSortKeysThreads / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t i = (uint64_t)blockIdx.x * kSortKeysThreads + threadIdx.x;
+    const bool live = i < a.n;
+    bool keep = live, bad = false;
+    uint64_t key = 0, rec_off = 0;
+    uint32_t len = 0;
+    if (live) {
+        const RecDesc d = a.desc[i];
+        const int32_t ref = a.rec_ref[i];
+        rec_off = d.rec_off;
+        if (a.use_filter) { keep = d.pad == kFilterPass; bad = d.pad == kFilterBad; }
+        else bad = ref < -1 || ref >= a.n_ref;
+        if (keep && !bad) {
+            uint32_t bs;
+            __builtin_memcpy(&bs, a.U + rec_off, 4);                 // block_size (records start at any byte)
+            len = bs + 4u;
+            // (the chain of K2 ends every record inside the batch; a record that would not is never copied)
+            bad = bs < 32u || bs > 0x7FFFFFF0u || rec_off + len > a.u_end;
+            key = sortc::sort_key(ref, d.pos, d.flag, a.n_ref);
+        }
+        keep = keep && !bad;
+    }
+    const unsigned long long m = __ballot(keep);
+    const unsigned long long mb = __ballot(bad);
+    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t before = 0;
+    for (uint32_t w = 0; w < wave; ++w) before += wcnt[w];
+    const uint64_t gbase = group_base ? group_base[blockIdx.x] : (uint64_t)blockIdx.x * kSortKeysThreads;
+    if (keep) {
+        const uint64_t at = a.out_base + gbase + before + (uint32_t)__popcll(m & lanemask_lt());
+        a.key[at] = key;
+        a.off[at] = (uint64_t)((int64_t)rec_off + a.store_delta);
+        a.len[at] = len;
+    }
+    // the wave's share of the accumulators
+    unsigned long long k_or = keep ? key : 0ull, k_and = keep ? key : ~0ull, bytes = keep ? len : 0ull;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        k_or |= __shfl_xor(k_or, d, 64);
+        k_and &= __shfl_xor(k_and, d, 64);
+        bytes += __shfl_xor(bytes, d, 64);
+    }
+    if (lane == 0) {
+        if (m) {
+            atomicOr(a.acc + kSortAccOr, k_or);
+            atomicAnd(a.acc + kSortAccAnd, k_and);
+            atomicAdd(a.acc + kSortAccKept, (unsigned long long)__popcll(m));
+            atomicAdd(a.acc + kSortAccBytes, bytes);
+        }
+        if (mb) atomicAdd(a.acc + kSortAccBad, (unsigned long long)__popcll(mb));
+    }
+}
+
+// ---- K9b -----------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kRadixThreads = 256, kRadixWaves = kRadixThreads / 64, kRadixRounds = kRadixTile / kRadixThreads;
+
+__global__ __launch_bounds__(256) void k_iota(uint32_t* __restrict__ v, uint64_t n) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) v[i] = (uint32_t)i;
+}
+
+__global__ __launch_bounds__(kRadixThreads) void k_radix_hist(const uint64_t* __restrict__ key, uint64_t n, uint32_t shift, uint32_t n_tiles,
+                                                              uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t t0 = (uint64_t)blockIdx.x * kRadixTile;
+#pragma unroll 4
+    for (uint32_t r = 0; r < kRadixRounds; ++r) {
+        const uint64_t i = t0 + r * kRadixThreads + threadIdx.x;
+        if (i < n) atomicAdd(&h[(uint32_t)(key[i] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+__global__ __launch_bounds__(kRadixThreads) void k_radix_scatter(const uint64_t* __restrict__ key_in, const uint32_t* __restrict__ val_in,
+                                                                 uint64_t* __restrict__ key_out, uint32_t* __restrict__ val_out, uint64_t n,
+                                                                 uint32_t shift, uint32_t n_tiles, const uint64_t* __restrict__ hist_base) {
+    __shared__ uint32_t off[256];                      // next output slot of every digit for this tile
+    __shared__ uint32_t wcount[kRadixWaves][256];      // this round's elements per wave and digit
+    const uint32_t t = threadIdx.x, wave = t >> 6;
+    off[t] = (uint32_t)hist_base[(size_t)t * n_tiles + blockIdx.x];
+#pragma unroll
+    for (uint32_t w = 0; w < kRadixWaves; ++w) wcount[w][t] = 0;
+    __syncthreads();
+    const uint64_t t0 = (uint64_t)blockIdx.x * kRadixTile;
+    const uint64_t lt = lanemask_lt();
+    for (uint32_t r = 0; r < kRadixRounds; ++r) {
+        const uint64_t i = t0 + r * kRadixThreads + t;
+        if (t0 + r * kRadixThreads >= n) break;        // (workgroup-uniform)
+        const bool live = i < n;
+        uint64_t k = 0;
+        uint32_t v = 0;
+        if (live) { k = key_in[i]; v = val_in[i]; }
+        const uint32_t digit = (uint32_t)(k >> shift) & 255u;
+        // the live lanes of the wave that hold the same digit
+        unsigned long long peers = __ballot(live);
+#pragma unroll
+        for (uint32_t b = 0; b < 8; ++b) {
+            const bool bit = (digit >> b) & 1u;
+            const unsigned long long bal = __ballot(bit);
+            peers &= bit ? bal : ~bal;
+        }
+        const uint32_t rank = (uint32_t)__popcll(peers & lt);
+        if (live && rank == 0) wcount[wave][digit] = (uint32_t)__popcll(peers);
+        __syncthreads();
+        if (live) {
+            uint32_t at = off[digit] + rank;
+            for (uint32_t w = 0; w < wave; ++w) at += wcount[w][digit];
+            key_out[at] = k;
+            val_out[at] = v;
+        }
+        __syncthreads();
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kRadixWaves; ++w) { s += wcount[w][t]; wcount[w][t] = 0; }
+        off[t] += s;
+        __syncthreads();
+    }
+}
+
+// ---- offsets of the sorted records ---------------------------------------------------------------------------------------------
+constexpr uint32_t kLenThreads = 256, kLenItems = kLenTile / kLenThreads;
+
+// sum of the values of the workgroup's threads; valid in every thread
+__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* wsum) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor((unsigned long long)v, d, 64);
+    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t s = 0;
+    for (uint32_t w = 0; w < blockDim.x / 64; ++w) s += wsum[w];
+    __syncthreads();
+    return s;
+}
+
+// exclusive prefix of v over the workgroup's threads (thread order); *total receives the sum
+__device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t* wsum, uint64_t* total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint64_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)incl, d, 64);
+        if ((int)lane >= d) incl += o;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (uint32_t w = 0; w < blockDim.x / 64; ++w) { const uint64_t x = wsum[w]; if (w < wave) before += x; all += x; }
+    __syncthreads();
+    *total = all;
+    return before + incl - v;
+}
+
+__global__ __launch_bounds__(kLenThreads) void k_len_tile_sum(const uint32_t* __restrict__ len, const uint32_t* __restrict__ perm, uint64_t n,
+                                                              uint64_t* __restrict__ tile_sum) {
+    __shared__ uint64_t wsum[kLenThreads / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * kLenTile + (uint64_t)threadIdx.x * kLenItems;
+    uint64_t s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kLenItems; ++k) if (i0 + k < n) s += len[perm[i0 + k]];
+    s = block_sum(s, wsum);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
+}
+
+// in place: x[i] = first + sum of x[j], j < i, for i in [0, m]; one workgroup
+__global__ __launch_bounds__(1024) void k_scan64(uint64_t* __restrict__ x, uint64_t m, uint64_t first) {
+    __shared__ uint64_t wsum[1024 / 64];
+    uint64_t carry = first;
+    for (uint64_t i0 = 0; i0 < m; i0 += 1024) {
+        const uint64_t i = i0 + threadIdx.x;
+        const uint64_t v = i < m ? x[i] : 0;
+        uint64_t total;
+        const uint64_t ex = block_exclusive(v, wsum, &total);
+        if (i < m) x[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) x[m] = carry;
+}
+
+__global__ __launch_bounds__(kLenThreads) void k_len_apply(const uint32_t* __restrict__ len, const uint32_t* __restrict__ perm, uint64_t n,
+                                                           const uint64_t* __restrict__ tile_base, uint64_t* __restrict__ out_off) {
+    __shared__ uint64_t wsum[kLenThreads / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * kLenTile + (uint64_t)threadIdx.x * kLenItems;
+    uint32_t l[kLenItems];
+    uint64_t s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kLenItems; ++k) { l[k] = i0 + k < n ? len[perm[i0 + k]] : 0u; s += l[k]; }
+    uint64_t total;
+    uint64_t run = tile_base[blockIdx.x] + block_exclusive(s, wsum, &total);
+#pragma unroll
+    for (uint32_t k = 0; k < kLenItems; ++k) {
+        if (i0 + k < n) out_off[i0 + k] = run;
+        run += l[k];
+        if (i0 + k + 1 == n) out_off[n] = run;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_piece_bounds(const uint64_t* __restrict__ out_off, uint64_t n, uint64_t piece_bytes, uint32_t n_bounds,
+                                                      uint32_t* __restrict__ rec) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_bounds) return;
+    const uint64_t target = (uint64_t)k * piece_bytes;
+    uint64_t lo = 0, hi = n;                    // the first i with out_off[i + 1] > target
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (out_off[mid + 1] > target) hi = mid; else lo = mid + 1;
+    }
+    rec[k] = (uint32_t)lo;
+}
+
+// ---- K9c -----------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kGatherThreads = 256, kGatherGroup = 16, kGatherRecs = kGatherThreads / kGatherGroup;
+struct __attribute__((packed, aligned(1))) Bytes16 { uint32_t w[4]; };
+
+__global__ __launch_bounds__(kGatherThreads) void k_gather_records(const uint8_t* __restrict__ store, const uint64_t* __restrict__ off,
+                                                                   const uint32_t* __restrict__ perm, const uint64_t* __restrict__ out_off,
+                                                                   uint64_t r0, uint64_t r1, uint64_t p0, uint64_t p1, uint8_t* __restrict__ dst) {
+    const uint32_t l = threadIdx.x % kGatherGroup;
+    const uint64_t i = r0 + (uint64_t)blockIdx.x * kGatherRecs + threadIdx.x / kGatherGroup;
+    if (i >= r1) return;
+    const uint64_t o = out_off[i], e = out_off[i + 1];
+    const uint64_t lo = o > p0 ? o : p0, hi = e < p1 ? e : p1;
+    if (lo >= hi) return;
+    const uint8_t* s = store + off[perm[i]] + (lo - o);
+    uint8_t* d = dst + (lo - p0);
+    uint64_t nb = hi - lo;
+    const uint32_t head = (uint32_t)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u);
+    const uint32_t h = head < nb ? head : (uint32_t)nb;
+    if (l < h) d[l] = s[l];
+    s += h; d += h; nb -= h;
+    const uint64_t chunks = nb >> 4;
+    for (uint64_t c = l; c < chunks; c += kGatherGroup) {
+        const Bytes16 x = *(const Bytes16*)(s + 16 * c);
+        *(uint4*)(d + 16 * c) = uint4{x.w[0], x.w[1], x.w[2], x.w[3]};
+    }
+    const uint32_t tail = (uint32_t)(nb & 15u);
+    if (l < tail) d[16 * chunks + l] = s[16 * chunks + l];
+}
+
+}  // namespace
+
+void launch_sort_keys(const SortKeysArgs& a, uint32_t* d_group_count, uint64_t* d_group_base, hipStream_t stream) {
+    if (!a.n) return;
+    const uint32_t groups = sort_keys_groups(a.n);
+    if (a.use_filter) {
+        hipLaunchKernelGGL(k_sort_group_count, dim3(groups), dim3(kSortKeysThreads), 0, stream, a.desc, a.n, d_group_count);
+        SBX_HIP(hipGetLastError());
+        launch_count_scan(d_group_count, groups, d_group_base, nullptr, 0, stream);
+    }
+    hipLaunchKernelGGL(k_sort_keys, dim3(groups), dim3(kSortKeysThreads), 0, stream, a, a.use_filter ? d_group_base : nullptr);
+    SBX_HIP(hipGetLastError());
+}
+
+void launch_iota(uint32_t* d_val, uint64_t n, hipStream_t stream) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_iota, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_val, n);
+    SBX_HIP(hipGetLastError());
+}
+
+void launch_radix_pass(const uint64_t* d_key_in, const uint32_t* d_val_in, uint64_t* d_key_out, uint32_t* d_val_out, uint64_t n, uint32_t shift,
+                       uint32_t* d_hist, uint64_t* d_hist_base, hipStream_t stream) {
+    if (!n) return;
+    const uint32_t tiles = radix_tiles(n);
+    hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(kRadixThreads), 0, stream, d_key_in, n, shift, tiles, d_hist);
+    SBX_HIP(hipGetLastError());
+    launch_count_scan(d_hist, tiles * 256u, d_hist_base, nullptr, 0, stream);
+    hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kRadixThreads), 0, stream, d_key_in, d_val_in, d_key_out, d_val_out, n, shift, tiles,
+                       d_hist_base);
+    SBX_HIP(hipGetLastError());
+}
+
+void launch_sorted_offsets(const uint32_t* d_len, const uint32_t* d_perm, uint64_t n, uint64_t first, uint64_t* d_tile_sum, uint64_t* d_out_off,
+                           hipStream_t stream) {
+    if (!n) return;
+    const uint32_t tiles = (uint32_t)len_tiles(n);
+    hipLaunchKernelGGL(k_len_tile_sum, dim3(tiles), dim3(kLenThreads), 0, stream, d_len, d_perm, n, d_tile_sum);
+    SBX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_scan64, dim3(1), dim3(1024), 0, stream, d_tile_sum, (uint64_t)tiles, first);
+    SBX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_len_apply, dim3(tiles), dim3(kLenThreads), 0, stream, d_len, d_perm, n, d_tile_sum, d_out_off);
+    SBX_HIP(hipGetLastError());
+}
+
+void launch_piece_bounds(const uint64_t* d_out_off, uint64_t n, uint64_t piece_bytes, uint32_t n_bounds, uint32_t* d_rec, hipStream_t stream) {
+    if (!n_bounds) return;
+    hipLaunchKernelGGL(k_piece_bounds, dim3((n_bounds + 255) / 256), dim3(256), 0, stream, d_out_off, n, piece_bytes, n_bounds, d_rec);
+    SBX_HIP(hipGetLastError());
+}
+
+void launch_gather_records(const uint8_t* d_store, const uint64_t* d_off, const uint32_t* d_perm, const uint64_t* d_out_off, uint64_t r0,
+                           uint64_t r1, uint64_t p0, uint64_t p1, uint8_t* d_dst, hipStream_t stream) {
+    if (r1 <= r0 || p1 <= p0) return;
+    const uint64_t groups = (r1 - r0 + kGatherRecs - 1) / kGatherRecs;
+    hipLaunchKernelGGL(k_gather_records, dim3((uint32_t)groups), dim3(kGatherThreads), 0, stream, d_store, d_off, d_perm, d_out_off, r0, r1, p0, p1,
+                       d_dst);
+    SBX_HIP(hipGetLastError());
+}
+
+}  // namespace sbx

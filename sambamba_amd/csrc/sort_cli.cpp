@@ -1,0 +1,125 @@
+// sort_cli.cpp -- `sbx-sort`: the command line of `sambamba-sort` (sort_main, sambamba/sort.d:495-576) on top of the C ABI of
+// libsbx_depth.so.  Reading, sorting and compressing happen on the device (sbx_sort_bam); this file parses the options.
+//
+//   sbx-sort [-o OUT|--out=OUT] [-l N|--compression-level=N] [-F FILTER|--filter=FILTER] in.bam
+//
+// Coordinate order only: -n / --sort-by-name, -N / --natural-sort, --sort-picard and -M / --match-mates are refused.  -m, --tmpdir,
+// -u, -t and -p are accepted and ignored: the file is sorted in device memory, there are no chunks on disk and no thread pool.  As with
+// D's getopt, options may follow the file name.  Without -o the output is the input with its extension replaced by "sorted.bam"
+// (setExtension, sort.d:535); an output that is the input is refused (protectFromOverwrite); like the reference's BamWriter, an
+// output whose name ends in ".bam" gets a "<out>.bai" next to it.  Errors: "sbx-sort: <message>" on stderr and exit status 1.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/sbx_depth.h"
+
+namespace {
+
+void usage() {
+    fputs("Usage: sbx-sort [options] <input.bam>\n"
+          "\n"
+          "Sorts a BAM file by coordinate, as `sambamba sort` does, on the GPU.\n"
+          "\n"
+          "Options: -o, --out=OUTPUTFILE\n"
+          "               output file name; if not provided, the result is written to a file with .sorted.bam extension\n"
+          "         -l, --compression-level=COMPRESSION_LEVEL\n"
+          "               level of compression for sorted BAM, from 0 to 9\n"
+          "         -F, --filter=FILTER\n"
+          "               keep only reads that satisfy FILTER\n"
+          "         -m, --memory-limit=LIMIT, --tmpdir=TMPDIR, -u, --uncompressed-chunks, -t, --nthreads=NTHREADS, -p, --show-progress\n"
+          "               accepted for compatibility; the file is sorted in GPU memory\n"
+          "         -n, --sort-by-name, -N, --natural-sort, --sort-picard, -M, --match-mates\n"
+          "               not supported: coordinate order only\n",
+          stderr);
+}
+
+int die(const std::string& m) {
+    fprintf(stderr, "sbx-sort: %s\n", m.c_str());
+    return 1;
+}
+
+// setExtension(path, "sorted.bam"): the extension of the last path component is replaced (appended when there is none)
+std::string with_sorted_extension(const std::string& path) {
+    const size_t slash = path.find_last_of('/');
+    const size_t dot = path.find_last_of('.');
+    const size_t name0 = slash == std::string::npos ? 0 : slash + 1;
+    const bool has_ext = dot != std::string::npos && dot > name0;
+    return (has_ext ? path.substr(0, dot) : path) + ".sorted.bam";
+}
+
+bool ends_with(const std::string& s, const char* t) {
+    const size_t n = strlen(t);
+    return s.size() >= n && s.compare(s.size() - n, n, t) == 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    std::string out, filter_str, level_str;
+    std::vector<std::string> files;
+    // long name, short name, takes a value; what: 0 ignored, 1 out, 2 level, 3 filter, 4 refused
+    struct Opt { const char* lng; char sht; bool value; int what; };
+    static const Opt opts[] = {
+        {"memory-limit", 'm', true, 0}, {"tmpdir", 0, true, 0}, {"out", 'o', true, 1}, {"sort-by-name", 'n', false, 4},
+        {"natural-sort", 'N', false, 4}, {"sort-picard", 0, false, 4}, {"match-mates", 'M', false, 4},
+        {"uncompressed-chunks", 'u', false, 0}, {"compression-level", 'l', true, 2}, {"show-progress", 'p', false, 0},
+        {"nthreads", 't', true, 0}, {"filter", 'F', true, 3},
+    };
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "--") {
+            for (++i; i < argc; ++i) files.push_back(argv[i]);
+            break;
+        }
+        if (a.size() < 2 || a[0] != '-') { files.push_back(a); continue; }
+        const Opt* o = nullptr;
+        std::string value;
+        bool have_value = false;
+        if (a[1] == '-') {
+            const size_t eq = a.find('=');
+            const std::string name = a.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
+            for (const Opt& k : opts) if (name == k.lng) o = &k;
+            if (eq != std::string::npos) { value = a.substr(eq + 1); have_value = true; }
+        } else {
+            for (const Opt& k : opts) if (k.sht && a[1] == k.sht) o = &k;
+            if (o && a.size() > 2) {
+                if (!o->value) o = nullptr;      // (bundled flags are not D getopt's default either)
+                else { value = a.substr(a[2] == '=' ? 3 : 2); have_value = true; }
+            }
+        }
+        if (!o) return die("Unrecognized option " + a);
+        const std::string shown = o->sht ? std::string("-") + o->sht + " / --" + o->lng : std::string("--") + o->lng;
+        if (o->what == 4) return die("option " + shown + " is not supported: sbx-sort sorts by coordinate only");
+        if (o->value && !have_value) {
+            if (i + 1 >= argc) return die("Missing value for argument " + a + ".");
+            value = argv[++i];
+        }
+        if (o->what == 1) out = value;
+        else if (o->what == 2) level_str = value;
+        else if (o->what == 3) filter_str = value;
+    }
+    if (files.empty()) {
+        usage();
+        return 1;
+    }
+    const std::string in = files[0];
+    int level = -1;
+    if (!level_str.empty()) {
+        char* end = nullptr;
+        const long v = strtol(level_str.c_str(), &end, 10);
+        if (*end || v < -1 || v > 9) return die("invalid compression level " + level_str);
+        level = (int)v;
+    }
+    if (out.empty()) out = with_sorted_extension(in);
+    char err[512] = {0};
+    sbx_filter filter;
+    const bool have_filter = !filter_str.empty();
+    if (have_filter && sbx_compile_filter(filter_str.c_str(), &filter, err, sizeof err) != SBX_OK) return die(err);
+    const int rc = sbx_sort_bam(in.c_str(), out.c_str(), have_filter ? &filter : nullptr, level, ends_with(out, ".bam") ? 1 : 0, -1, nullptr, err,
+                                sizeof err);
+    if (rc != SBX_OK) return die(err);
+    return 0;
+}

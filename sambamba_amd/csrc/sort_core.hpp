@@ -1,0 +1,153 @@
+// sort_core.hpp -- what `sambamba sort` (coordinate order) needs besides the kernels: the 64-bit sort key of a record, the digits a
+// radix sort has to look at, and the header text of the output.  The key functions are `__host__ __device__` (K9a, sort.hip, packs the
+// key with the very statement the CPU test checks: tests/native/sort_host.cpp); the header text is host code.
+//
+// Order (compareCoordinatesAndStrand, BioD bio/std/hts/bam/read.d:1632-1642, applied by a stable merge sort): ref_id -1 last, ascending
+// ref_id, ascending position as a signed number, forward strand in front of reverse strand, ties in file order.  Records with ref_id -1
+// compare equal to one another whatever their position and strand say.  All of it is the unsigned order of
+//     key = ref_id << 33 | (uint32)(position + 1) << 1 | strand,          key = n_ref << 33 for ref_id == -1
+// for every position >= -1 (what the format allows; a position below -1 wraps and sorts behind the others of its contig).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define SBX_SORT_HD __host__ __device__ __forceinline__
+#else
+#define SBX_SORT_HD inline
+#endif
+
+namespace sbx {
+namespace sortc {
+
+constexpr uint32_t kStrandBits = 1, kPosBits = 32, kRefShift = kStrandBits + kPosBits;
+constexpr uint32_t kDigitBits = 8;        // one pass of the radix sort (K9b)
+
+SBX_SORT_HD uint64_t sort_key(int32_t ref_id, int32_t pos, uint32_t flag, int32_t n_ref) {
+    if (ref_id < 0) return (uint64_t)(uint32_t)n_ref << kRefShift;       // all of them compare equal: they keep their file order
+    return (uint64_t)(uint32_t)ref_id << kRefShift | (uint64_t)(uint32_t)(pos + 1) << kStrandBits | ((flag >> 4) & 1u);
+}
+
+SBX_SORT_HD uint32_t bit_width64(uint64_t v) {
+    uint32_t n = 0;
+    while (v) { ++n; v >>= 1; }
+    return n;
+}
+
+// bits of the largest key a file with n_ref references whose records start at or below position max_pos can hold: the strand bit,
+// max_pos + 1, and n_ref (the id that stands for -1).  An upper bound from the header alone; the sort itself looks at the keys.
+SBX_SORT_HD uint32_t key_bits(int32_t n_ref, int64_t max_pos) {
+    if (n_ref > 0) return kRefShift + bit_width64((uint64_t)n_ref);
+    const uint64_t p = max_pos < -1 ? 0 : (uint64_t)(max_pos + 1);
+    return kStrandBits + bit_width64(p > 0xFFFFFFFFull ? 0xFFFFFFFFull : p);
+}
+
+// The passes of the LSD radix sort: `varying` has a bit set where two keys of the file differ (OR of the keys ^ AND of the keys).
+// Digits start at the lowest varying bit; a digit none of whose bits vary is skipped.  Returns the number of passes, their shifts
+// in shift[] (ascending; room for 8), and through *bits the width of the varying stretch.
+SBX_SORT_HD uint32_t plan_passes(uint64_t varying, uint32_t* shift, uint32_t* bits) {
+    *bits = 0;
+    if (!varying) return 0;
+    uint32_t lo = 0;
+    while (!((varying >> lo) & 1)) ++lo;
+    const uint32_t hi = bit_width64(varying);
+    *bits = hi - lo;
+    uint32_t n = 0;
+    for (uint32_t s = lo; s < hi; s += kDigitBits)
+        if ((varying >> s) & ((1u << kDigitBits) - 1)) shift[n++] = s;
+    return n;
+}
+
+}  // namespace sortc
+}  // namespace sbx
+
+// ---- host only ----
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+namespace sbx {
+namespace sortc {
+
+// The text SamHeader.toSam prints (BioD bio/std/hts/sam/header.d:626-656) for a header parsed from `text` (header.d:473-545) whose
+// sorting order was set to coordinate (sambamba/sort.d:294-298): "@HD\tVN:<version>\tSO:coordinate", the version being that of an @HD
+// line that is the first line of the input (1.3 otherwise); then the @SQ, @RG and @PG lines in order of first appearance -- a later
+// line with the same SN / ID is dropped -- each with only the fields header.d:216-254 declares, in the declared order, empty strings
+// and zero numbers left out; then the @CO lines.  Lines shorter than three characters are skipped.  false: a line does not start
+// with '@', is of no known type, or has a number field (LN, PI) that is not a number (the reference throws).
+inline bool sort_header_text(const char* text, size_t n, std::string* out, std::string* why) {
+    struct Decl { const char* prefix; std::vector<const char*> fields; const char* numeric; };
+    static const Decl kSq{"@SQ", {"SN", "LN", "AN", "AS", "DS", "M5", "SP", "UR", "AH"}, "LN"};
+    static const Decl kRg{"@RG", {"ID", "BC", "CN", "DS", "DT", "FO", "KS", "LB", "PG", "PI", "PL", "PU", "SM", "PM"}, "PI"};
+    static const Decl kPg{"@PG", {"ID", "PN", "CL", "PP", "VN"}, ""};
+    struct Line { std::string id, text; };
+    std::vector<Line> sq, rg, pg;
+    std::vector<std::string> comments;
+    std::string version = "1.3";
+    bool first = true;
+    // (a header text may be padded with zero bytes: the text ends at the first one)
+    for (size_t k = 0; k < n; ++k) if (!text[k]) { n = k; break; }
+    auto fail = [&](const std::string& m) { if (why) *why = m; return false; };
+    // value of field `key` of a line: the last occurrence wins (parse assigns field by field)
+    auto field = [](const std::string& line, const char* key) {
+        std::string v;
+        size_t p = 3;
+        while (p <= line.size()) {
+            size_t e = line.find('\t', p);
+            if (e == std::string::npos) e = line.size();
+            if (e - p >= 3 && line[p + 2] == ':' && line[p] == key[0] && line[p + 1] == key[1]) v = line.substr(p + 3, e - p - 3);
+            p = e + 1;
+        }
+        return v;
+    };
+    auto add = [&](std::vector<Line>& to, const Decl& d, const std::string& line) -> bool {
+        Line l;
+        l.text = d.prefix;
+        for (size_t k = 0; k < d.fields.size(); ++k) {
+            std::string v = field(line, d.fields[k]);
+            const bool numeric = d.fields[k][0] == d.numeric[0] && d.fields[k][1] == d.numeric[1];
+            if (numeric && !v.empty()) {
+                // to!uint / to!int: digits only (a sign for PI), printed back as a number
+                size_t i = (d.numeric[0] == 'P' && (v[0] == '-' || v[0] == '+')) ? 1 : 0;
+                if (i == v.size()) return false;
+                for (size_t j = i; j < v.size(); ++j) if (v[j] < '0' || v[j] > '9') return false;
+                const long long x = strtoll(v.c_str(), nullptr, 10);
+                v = x == 0 ? std::string() : std::to_string(x);
+            }
+            if (k == 0) l.id = v;
+            if (!v.empty()) { l.text += '\t'; l.text += d.fields[k]; l.text += ':'; l.text += v; }
+        }
+        for (const Line& o : to) if (o.id == l.id) return true;      // duplicate: the first line stays
+        to.push_back(l);
+        return true;
+    };
+    for (size_t p = 0; p <= n;) {
+        size_t e = p;
+        while (e < n && text[e] != '\n') ++e;
+        const std::string line(text + p, e - p);
+        p = e + 1;
+        if (line.size() < 3) continue;
+        if (first && line.compare(0, 3, "@HD") == 0) version = field(line, "VN");
+        if (line[0] != '@') return fail("Header lines must start with @");
+        const std::string ty = line.substr(1, 2);
+        bool ok = true;
+        if (ty == "SQ") ok = add(sq, kSq, line);
+        else if (ty == "RG") ok = add(rg, kRg, line);
+        else if (ty == "PG") ok = add(pg, kPg, line);
+        else if (ty == "HD") {}
+        else if (ty == "CO") comments.push_back(line.size() > 4 ? line.substr(4) : std::string());
+        else return fail("unknown header line type " + line.substr(0, 3));
+        if (!ok) return fail("malformed number in header line " + line);
+        first = false;
+    }
+    out->clear();
+    *out += "@HD\tVN:" + version + "\tSO:coordinate\n";
+    for (const auto* v : {&sq, &rg, &pg})
+        for (const Line& l : *v) { *out += l.text; *out += '\n'; }
+    for (const std::string& c : comments) { *out += "@CO\t"; *out += c; *out += '\n'; }
+    return true;
+}
+
+}  // namespace sortc
+}  // namespace sbx
