@@ -3,7 +3,9 @@
 //
 //   sbx-flagstat [-t N|--nthreads=N] [-p|--show-progress] [-b|--tabular] in.bam
 //
-// As with D's getopt, options may follow the file name.  -t only sizes the reference's decompression pool and is accepted and
+// As with D's getopt, options may follow the file name (cli_opts.hpp scans them); `--` ends the options.  Messages carry no prefix.
+// -t is validated in every spelling ("Invalid number of threads: V"); anything else that starts with `-` and is longer than one
+// character is "Unrecognized option X" -- a flag with text attached (`-bx`, `--tabular=1`) included; a lone `-` is a file.  -t only sizes the reference's decompression pool and is accepted and
 // ignored; so is -p (the device pass reports no progress).  The counters are printed only after the whole file was read
 // (flagstat.d:127-145): on any error stdout stays empty, the message goes to stderr and the exit status is 1.
 #include <cstdio>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "../../include/sbx_depth.h"
+#include "cli_opts.hpp"
 
 namespace {
 
@@ -39,26 +42,19 @@ bool parse_count(const char* s) {
 int main(int argc, char** argv) {
     bool tabular = false;
     std::vector<std::string> files;
+    static const sbx::OptSpec opts[] = {{"nthreads", 't', true, 't'}, {"show-progress", 'p', false, 'p'}, {"tabular", 'b', false, 'b'}};
     for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        if (a == "--") {
+        const sbx::OptToken t = sbx::next_opt(argc, argv, &i, opts);
+        if (t.kind == sbx::OptToken::Terminator) {
             for (++i; i < argc; ++i) files.push_back(argv[i]);
             break;
         }
-        if (a == "-b" || a == "--tabular") { tabular = true; continue; }
-        if (a == "-p" || a == "--show-progress") continue;
-        if (a == "-t" || a == "--nthreads") {
-            if (i + 1 >= argc) { fprintf(stderr, "Missing value for argument %s.\n", a.c_str()); return 1; }
-            if (!parse_count(argv[++i])) { fprintf(stderr, "Invalid number of threads: %s\n", argv[i]); return 1; }
-            continue;
-        }
-        if (a.compare(0, 11, "--nthreads=") == 0 || (a.size() > 2 && a.compare(0, 2, "-t") == 0)) {
-            const char* v = a[1] == '-' ? a.c_str() + 11 : a.c_str() + (a[2] == '=' ? 3 : 2);
-            if (!parse_count(v)) { fprintf(stderr, "Invalid number of threads: %s\n", v); return 1; }
-            continue;
-        }
-        if (a.size() > 1 && a[0] == '-') { fprintf(stderr, "Unrecognized option %s\n", a.c_str()); return 1; }
-        files.push_back(a);
+        if (t.kind == sbx::OptToken::Positional) { files.push_back(t.arg); continue; }       // (a lone `-` as well)
+        // a flag is its exact spelling: with text attached (`-bx`, `--tabular=1`) it is as unknown as `--bogus`
+        if (t.kind == sbx::OptToken::Unknown || (t.attached && !t.spec->takes_value)) { fprintf(stderr, "Unrecognized option %s\n", t.arg.c_str()); return 1; }
+        if (t.missing) { fprintf(stderr, "Missing value for argument %s.\n", t.arg.c_str()); return 1; }
+        if (t.spec->id == 'b') tabular = true;
+        else if (t.spec->id == 't' && !parse_count(t.value.c_str())) { fprintf(stderr, "Invalid number of threads: %s\n", t.value.c_str()); return 1; }
     }
     if (files.empty()) {
         usage();

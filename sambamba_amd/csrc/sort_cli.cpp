@@ -5,7 +5,8 @@
 //
 // Coordinate order only: -n / --sort-by-name, -N / --natural-sort, --sort-picard and -M / --match-mates are refused.  -m, --tmpdir,
 // -u, -t and -p are accepted and ignored: the file is sorted in device memory, there are no chunks on disk and no thread pool.  As with
-// D's getopt, options may follow the file name.  Without -o the output is the input with its extension replaced by "sorted.bam"
+// D's getopt, options may follow the file name (cli_opts.hpp scans them); `--` ends the options, an option that is not in the table is
+// "Unrecognized option X", and so is a short flag with text attached (`-ux`).  Without -o the output is the input with its extension replaced by "sorted.bam"
 // (setExtension, sort.d:535); an output that is the input is refused (protectFromOverwrite); like the reference's BamWriter, an
 // output whose name ends in ".bam" gets a "<out>.bai" next to it.  Errors: "sbx-sort: <message>" on stderr and exit status 1.
 #include <cstdio>
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "../../include/sbx_depth.h"
+#include "cli_opts.hpp"
 
 namespace {
 
@@ -60,46 +62,29 @@ bool ends_with(const std::string& s, const char* t) {
 int main(int argc, char** argv) {
     std::string out, filter_str, level_str;
     std::vector<std::string> files;
-    // long name, short name, takes a value; what: 0 ignored, 1 out, 2 level, 3 filter, 4 refused
-    struct Opt { const char* lng; char sht; bool value; int what; };
-    static const Opt opts[] = {
+    // long name, short name, takes a value, what it does: 0 ignored, 1 out, 2 level, 3 filter, 4 refused
+    static const sbx::OptSpec opts[] = {
         {"memory-limit", 'm', true, 0}, {"tmpdir", 0, true, 0}, {"out", 'o', true, 1}, {"sort-by-name", 'n', false, 4},
         {"natural-sort", 'N', false, 4}, {"sort-picard", 0, false, 4}, {"match-mates", 'M', false, 4},
         {"uncompressed-chunks", 'u', false, 0}, {"compression-level", 'l', true, 2}, {"show-progress", 'p', false, 0},
         {"nthreads", 't', true, 0}, {"filter", 'F', true, 3},
     };
     for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        if (a == "--") {
+        const sbx::OptToken t = sbx::next_opt(argc, argv, &i, opts);
+        if (t.kind == sbx::OptToken::Terminator) {       // `--` ends the options
             for (++i; i < argc; ++i) files.push_back(argv[i]);
             break;
         }
-        if (a.size() < 2 || a[0] != '-') { files.push_back(a); continue; }
-        const Opt* o = nullptr;
-        std::string value;
-        bool have_value = false;
-        if (a[1] == '-') {
-            const size_t eq = a.find('=');
-            const std::string name = a.substr(2, eq == std::string::npos ? std::string::npos : eq - 2);
-            for (const Opt& k : opts) if (name == k.lng) o = &k;
-            if (eq != std::string::npos) { value = a.substr(eq + 1); have_value = true; }
-        } else {
-            for (const Opt& k : opts) if (k.sht && a[1] == k.sht) o = &k;
-            if (o && a.size() > 2) {
-                if (!o->value) o = nullptr;      // (bundled flags are not D getopt's default either)
-                else { value = a.substr(a[2] == '=' ? 3 : 2); have_value = true; }
-            }
-        }
-        if (!o) return die("Unrecognized option " + a);
-        const std::string shown = o->sht ? std::string("-") + o->sht + " / --" + o->lng : std::string("--") + o->lng;
-        if (o->what == 4) return die("option " + shown + " is not supported: sbx-sort sorts by coordinate only");
-        if (o->value && !have_value) {
-            if (i + 1 >= argc) return die("Missing value for argument " + a + ".");
-            value = argv[++i];
-        }
-        if (o->what == 1) out = value;
-        else if (o->what == 2) level_str = value;
-        else if (o->what == 3) filter_str = value;
+        if (t.kind == sbx::OptToken::Positional) { files.push_back(t.arg); continue; }
+        // (bundled flags are not D getopt's default either: a short flag with text attached is no option at all)
+        if (t.kind == sbx::OptToken::Unknown || (t.attached && !t.spec->takes_value && t.arg[1] != '-')) return die("Unrecognized option " + t.arg);
+        const sbx::OptSpec& o = *t.spec;
+        const std::string shown = o.sht ? std::string("-") + o.sht + " / --" + o.lng : std::string("--") + o.lng;
+        if (o.id == 4) return die("option " + shown + " is not supported: sbx-sort sorts by coordinate only");
+        if (t.missing) return die("Missing value for argument " + t.arg + ".");
+        if (o.id == 1) out = t.value;
+        else if (o.id == 2) level_str = t.value;
+        else if (o.id == 3) filter_str = t.value;
     }
     if (files.empty()) {
         usage();

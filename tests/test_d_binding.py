@@ -125,7 +125,8 @@ def test_d_glue_covers_or_refuses_every_stateful_corner_of_the_compiled_host():
     (and the GPU tests pin against the oracle), the D glue either carries the same rule or hands the job back to the
     reference's CPU path (`return false`) -- never prints something else."""
     d = open(os.path.join(ROOT, "d", "sbx_depth.d")).read()
-    cli = open(os.path.join(ROOT, "sambamba_amd", "csrc", "cli.cpp")).read()
+    csrc = os.path.join(ROOT, "sambamba_amd", "csrc")      # the compiled host: cli.cpp and the cli_*.hpp it is made of
+    cli = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f == "cli.cpp" or (f.startswith("cli_") and f.endswith(".hpp")))
     body = d[d.index("bool sbxDepthRun("):]
     # the one refusal left (round 6: the two base-mode corners are printed on the host from the device's counters, as cli.cpp does)
     assert "o.mode == SBX_MODE_WINDOW && o.overlap != 0) return false" in body                            # window --overlap
