@@ -89,6 +89,16 @@ extern (C) nothrow @nogc {
     int sbx_sort_bam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, int level, int with_index, int device,
                      sbx_sort_stats* stats, char* err, size_t errlen);
     int sbx_sort_header_text(const(char)* text, size_t n, char* out_, size_t cap, size_t* out_len);
+    struct sbx_markdup_stats {
+        ulong n_records_in; ulong n_records_out; ulong n_end_pairs; ulong n_single_ends; ulong n_unmatched_pairs; ulong n_duplicates;
+        ulong inflated_bytes; ulong stream_bytes; ulong compressed_bytes;
+        uint n_sort_passes; uint n_batches;
+        double ms_inflate; double ms_index; double ms_ends; double ms_pairing; double ms_groups; double ms_gather; double ms_deflate;
+        double ms_total_wall;
+    }
+    int sbx_markdup(const(char)* in_path, const(char)* out_path, int remove_duplicates, int level, const(char)* pg_command_line, int device,
+                    sbx_markdup_stats* stats, char* err, size_t errlen);
+    int sbx_markdup_header_text(const(char)* text, size_t n, const(char)* pg_command_line, char* out_, size_t cap, size_t* out_len);
     int sbx_inflate_blocks(const(ubyte)* comp, const(ulong)* comp_off, const(uint)* comp_len, const(uint)* isize,
                            uint n_blocks, ubyte* out_, const(ulong)* out_off, char* err, size_t errlen);
     sbx_ctx* sbx_open(const(char*)* bam_paths, int n_bams, int device, char* err, size_t errlen);

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -212,6 +212,32 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
  * the length (without the terminating zero, also with SBX_ENOMEM when cap is too small); SBX_EFORMAT for a text the reference's
  * parser throws on. */
 int sbx_sort_header_text(const char* text, size_t n, char* out, size_t cap, size_t* out_len);
+
+/* `sambamba markdup` (sambamba/markdup.d): every record is written in input order, byte for byte except flag 0x400, which is set on
+ * the duplicates and cleared on every other record that is neither secondary nor supplementary; remove_duplicates != 0 drops the
+ * records whose resulting flag has 0x400.  Records with a reference id that are not unmapped, secondary or supplementary take part:
+ * pairs (both mates mapped; matched by read name and RG string, 1st with 2nd, 3rd with 4th occurrence in file order) are compared by
+ * library, the unclipped 5' coordinates and the strands of both ends, fragments by those of their one end; the best of a group (sum of
+ * base qualities >= 15; ties: first in the file) stays unmarked, and a fragment where a paired read lies is always marked.  The header
+ * text is re-serialised (sbx_markdup_header_text).  The whole file is resident on the device: one whose inflated records do not fit
+ * next to one batch of the read pass is refused with SBX_ENOMEM, more than 2^32 records with SBX_EUNSUPPORTED.  Milliseconds are
+ * device time (inflate = K1, index = K2, ends = K10a + the copy into the record store, pairing = hash sort + K10b, groups = K10c +
+ * K10d, gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call. */
+typedef struct {
+    uint64_t n_records_in, n_records_out;
+    uint64_t n_end_pairs, n_single_ends, n_unmatched_pairs, n_duplicates;   /* the reference's stderr figures */
+    uint64_t inflated_bytes, stream_bytes, compressed_bytes;
+    uint32_t n_sort_passes, n_batches;
+    double ms_inflate, ms_index, ms_ends, ms_pairing, ms_groups, ms_gather, ms_deflate, ms_total_wall;
+} sbx_markdup_stats;
+/* level as sbx_bgzf_compress.  pg_command_line: the CL field of the @PG line that is added (NULL: no @PG added).  stats may be NULL.
+ * SBX_EINVAL when out_path is the input.  On failure no output file is left behind. */
+int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates, int level,
+                const char* pg_command_line, int device, sbx_markdup_stats* stats, char* err, size_t errlen);
+/* The output header text for an input header text (host only): SamHeader.toSam of the input -- SO kept when it is unsorted, coordinate
+ * or queryname -- with "@PG ID:sambamba CL:<pg_command_line> PP:<last @PG> VN:1.0" added unless pg_command_line is NULL or an @PG
+ * with ID:sambamba exists.  Lengths and errors as sbx_sort_header_text. */
+int sbx_markdup_header_text(const char* text, size_t n, const char* pg_command_line, char* out, size_t cap, size_t* out_len);
 
 /* ---- engine seam ------------------------------------------------------------ */
 

@@ -9,6 +9,7 @@ _LIB_PATH = os.path.join(HERE, "csrc", "libsbx_depth.so")
 _CLI_PATH = os.path.join(HERE, "csrc", "sbx-depth")
 _FLAGSTAT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-flagstat")
 _SORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sort")
+_MARKDUP_CLI_PATH = os.path.join(HERE, "csrc", "sbx-markdup")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -88,6 +89,12 @@ class SortStats(C.Structure):
                 [(k, C.c_uint32) for k in ("key_bits", "n_sort_passes", "n_batches", "reserved")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_keys", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
 
+class MarkdupStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_records_in", "n_records_out", "n_end_pairs", "n_single_ends", "n_unmatched_pairs", "n_duplicates",
+                                           "inflated_bytes", "stream_bytes", "compressed_bytes")] +
+                [(k, C.c_uint32) for k in ("n_sort_passes", "n_batches")] +
+                [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_ends", "ms_pairing", "ms_groups", "ms_gather", "ms_deflate", "ms_total_wall")])
+
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
 
 EXPORTS = [
@@ -97,7 +104,7 @@ EXPORTS = [
     "sbx_depth_window_stats",
     "sbx_format_base_rows", "sbx_stream_base_rows", "sbx_plan_batches", "sbx_run_batch", "sbx_last_run_stats", "sbx_tile_info", "sbx_next_active_range", "sbx_preload",
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
-    "sbx_sort_bam", "sbx_sort_header_text",
+    "sbx_sort_bam", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
 ]
 
 _lib = None
@@ -117,6 +124,10 @@ def flagstat_cli_path():
 
 def sort_cli_path():
     return _SORT_CLI_PATH
+
+
+def markdup_cli_path():
+    return _MARKDUP_CLI_PATH
 
 
 def lib():
@@ -177,6 +188,8 @@ def lib():
     L.sbx_format_flagstat.argtypes = [C.POINTER(Flagstat), C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_sort_bam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.POINTER(SortStats), C.c_char_p, C.c_size_t]
     L.sbx_sort_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sbx_markdup.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(MarkdupStats), C.c_char_p, C.c_size_t]
+    L.sbx_markdup_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_depth_base_tile_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -192,7 +205,7 @@ def lib():
     for name, ty in (("sbx_region", Region), ("sbx_header_info", HeaderInfo), ("sbx_region_stats", RegionStats),
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
-                     ("sbx_sort_stats", SortStats)):
+                     ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -302,6 +315,36 @@ def sort_header_text(text):
     rc = L.sbx_sort_header_text(data, len(data), buf, n.value + 1, C.byref(n))
     if rc != 0:
         raise SbxError(rc, "sbx_sort_header_text failed")
+    out = buf.raw[:n.value]
+    return out if isinstance(text, bytes) else out.decode()
+
+
+def markdup(in_path, out_path, remove_duplicates=False, level=-1, command_line=None, device=-1):
+    """sbx_markdup (`sambamba markdup`): marks (remove_duplicates: removes) the duplicates of in_path into out_path on the device;
+    command_line is the CL field of the @PG line that is added (None: no @PG).  Returns the fields of sbx_markdup_stats as a dict."""
+    L = lib()
+    st = MarkdupStats()
+    err = C.create_string_buffer(512)
+    rc = L.sbx_markdup(in_path.encode(), out_path.encode(), int(bool(remove_duplicates)), int(level),
+                       command_line.encode() if command_line is not None else None, device, C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: getattr(st, k) for k, _ in MarkdupStats._fields_}
+
+
+def markdup_header_text(text, command_line=None):
+    """sbx_markdup_header_text: the header text `sambamba markdup` writes for the input header text (str or bytes -> same type), host only."""
+    L = lib()
+    data = text if isinstance(text, bytes) else text.encode()
+    cl = command_line.encode() if command_line is not None else None
+    n = C.c_size_t(0)
+    rc = L.sbx_markdup_header_text(data, len(data), cl, None, 0, C.byref(n))
+    if rc not in (0, -8):
+        raise SbxError(rc, "malformed SAM header text")
+    buf = C.create_string_buffer(n.value + 1)
+    rc = L.sbx_markdup_header_text(data, len(data), cl, buf, n.value + 1, C.byref(n))
+    if rc != 0:
+        raise SbxError(rc, "sbx_markdup_header_text failed")
     out = buf.raw[:n.value]
     return out if isinstance(text, bytes) else out.decode()
 

@@ -1,4 +1,4 @@
-// cli_opts.hpp -- the one argument scanner of sbx-depth, sbx-sort and sbx-flagstat.  It knows the forms D's getopt knows --
+// cli_opts.hpp -- the one argument scanner of sbx-depth, sbx-sort, sbx-flagstat and sbx-markdup.  It knows the forms D's getopt knows --
 // `--name=value`, `--name value`, `-Xvalue`, `-X=value`, `-X value`, options before or after the file names -- and classifies ONE
 // argument at a time.  It decides nothing: what an unknown option, a `--` or a flag with text attached MEANS is the policy of each
 // command line, stated where its loop handles the token.

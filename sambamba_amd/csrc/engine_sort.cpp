@@ -7,51 +7,10 @@
 // -- header bytes from the host, records gathered by K9c -- is produced in pieces of whole BGZF payloads that go straight into the
 // deflate kernels (bgzf_compress_pieces) and, through pinned memory, to the file.  The sorted stream never exists as a whole.
 //
+// The plan of the store, the copy into it and the writer are engine_store.hpp, shared with sbx_markdup.
 // What does not fit the device next to one batch of the read pass is refused with SBX_ENOMEM (an out-of-core merge is not built).
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include "engine_ctx.hpp"
-#include "engine_stream.hpp"
-#include "sort.hpp"
+#include "engine_store.hpp"
 #include "sort_core.hpp"
-
-namespace {
-
-// "BAM\1", l_text, text, the binary reference list
-std::vector<uint8_t> bam_header_bytes(const std::string& text, const std::vector<RefSeq>& refs) {
-    std::vector<uint8_t> h;
-    auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) h.push_back((uint8_t)(v >> (8 * k))); };
-    h.insert(h.end(), {'B', 'A', 'M', 1});
-    put32((uint32_t)text.size());
-    h.insert(h.end(), text.begin(), text.end());
-    put32((uint32_t)refs.size());
-    for (const RefSeq& r : refs) {
-        put32((uint32_t)r.name.size() + 1);
-        h.insert(h.end(), r.name.begin(), r.name.end());
-        h.push_back(0);
-        put32((uint32_t)r.length);
-    }
-    return h;
-}
-
-bool same_file(const char* a, const char* b) {
-    struct stat sa, sb;
-    if (stat(a, &sa) != 0 || stat(b, &sb) != 0) return false;
-    return sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
-}
-
-// a device array of the kept records that grows while the batches arrive (the number of records is not known in advance)
-template <class T>
-void grow_keeping(DevBuf<T>& b, size_t used, size_t want, hipStream_t s) {
-    if (want <= b.n) return;
-    DevBuf<T> nb(want + want / 2 + 1024);
-    if (used) SBX_HIP(hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, s));
-    SBX_HIP(hipStreamSynchronize(s));
-    b = std::move(nb);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -98,22 +57,8 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
         const uint64_t hlen = header.size();
 
-        // ---- device memory: the record store, the per-record arrays, one read batch, one output piece ----
-        const BlockTable& bt = c->blocks;
-        const uint64_t u_total = bt.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
-        const uint64_t store_bytes = u_total - u_first;
-        const uint64_t est_records = store_bytes / 160 + 4096;          // (as K2 sizes its descriptors; the arrays grow when it is more)
-        const uint64_t piece_bytes = std::min<uint64_t>(kBgzfPieceBlocks * (uint64_t)kBgzfPayload, store_bytes + hlen + kBgzfPayload);
-        const uint64_t out_reserve = piece_bytes * 3 + (8ull << 20);    // piece, slots, packed blocks (kBgzfSlot ~ kBgzfPayload)
-        const uint64_t fixed_need = store_bytes + est_records * 48;
-        size_t free_b = 0, total_b = 0;
-        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t min_batch = 5ull * (64ull << 20);
-        if (fixed_need + std::max(out_reserve, min_batch) > free_b)
-            throw Error(SBX_ENOMEM, "the file does not fit the device: sorting it needs " + std::to_string(fixed_need + std::max(out_reserve, min_batch)) +
-                                        " bytes of device memory (" + std::to_string(store_bytes) + " of inflated records resident), " +
-                                        std::to_string(free_b) + " are free; an out-of-core merge is not implemented");
-        const uint64_t batch_u = index_batch_bytes(fixed_need);
+        const StorePlan plan = plan_record_store(c, hlen, 48, "sorting");
+        const uint64_t u_total = plan.u_total, u_first = plan.u_first, store_bytes = plan.store_bytes, batch_u = plan.batch_u;
         hipStream_t s = c->stream.get();
         DevBuf<uint8_t> d_store((size_t)store_bytes + 64);
         DevBuf<uint64_t> d_key, d_off;
@@ -140,7 +85,7 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
             grow_keeping(d_len, (size_t)n_kept, want, s);
             if (use_filter) { d_group_count.ensure(sort_keys_groups(nrec) + 4); d_group_base.ensure(sort_keys_groups(nrec) + 4); }
             t_k.start(s);
-            if (next > cur) SBX_HIP(hipMemcpyAsync(d_store.p + (cur - u_first), c->U() + (cur - base), next - cur, hipMemcpyDeviceToDevice, s));
+            copy_batch_to_store(c, d_store.p, u_first, cur, base, next, s);
             SortKeysArgs a{};
             a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
             a.n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
@@ -177,7 +122,7 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         const uint32_t n_passes = n ? sortc::plan_passes(acc[kSortAccOr] ^ acc[kSortAccAnd], shifts, &key_bits) : 0;
         DevBuf<uint64_t> d_key2((size_t)n + 2);
         DevBuf<uint32_t> d_val((size_t)n + 2), d_val2((size_t)n + 2);
-        EventTimer t_sort, t_gather;
+        EventTimer t_sort;
         uint64_t* keys[2] = {d_key.p, d_key2.p};
         uint32_t* vals[2] = {d_val.p, d_val2.p};
         int at = 0;
@@ -195,56 +140,16 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         // the keys are done with: one of their buffers holds the output offsets
         uint64_t* d_out_off = d_key2.p;
         d_key.release();
-        uint64_t total = hlen;
-        const uint64_t piece_cap = kBgzfPieceBlocks * (uint64_t)kBgzfPayload;
-        std::vector<uint32_t> bounds;
-        {
-            DevBuf<uint64_t> d_tile_sum(len_tiles(n) + 2);
-            t_gather.start(s);
-            launch_sorted_offsets(d_len.p, d_perm, n, hlen, d_tile_sum.p, d_out_off, s);
-            t_gather.stop(s);
-            if (n) SBX_HIP(hipMemcpyAsync(&total, d_out_off + n, 8, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipStreamSynchronize(s));
-            st.ms_sort = t_sort.ms();
-            if (n) st.ms_gather += t_gather.ms();          // (the offsets are the gather's preparation)
-            if (total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the sorted records do not add up");
-            const uint32_t n_bounds = (uint32_t)((total + piece_cap - 1) / piece_cap) + 1;
-            bounds.assign(n_bounds, (uint32_t)n);
-            if (n) {
-                DevBuf<uint32_t> d_bounds(n_bounds);
-                launch_piece_bounds(d_out_off, n, piece_cap, n_bounds, d_bounds.p, s);
-                SBX_HIP(hipMemcpyAsync(bounds.data(), d_bounds.p, (size_t)n_bounds * 4, hipMemcpyDeviceToHost, s));
-                SBX_HIP(hipStreamSynchronize(s));
-            }
-        }
+        const OutputPlan out = plan_output(d_len.p, d_perm, n, hlen, d_out_off, s, &st.ms_gather);
+        const uint64_t total = out.total;
+        st.ms_sort = t_sort.ms();
+        if (total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the sorted records do not add up");
         d_len.release();
         const double w3 = wall_now();
 
         // ---- K9c + deflate, piece by piece ----
-        FILE* f = fopen(out_path, "wb");
-        if (!f) throw Error(SBX_EIO, std::string("cannot write ") + out_path);
-        out_created = true;
-        bool ok = true;
         BgzfPieceTimes bt_times;
-        try {
-            bgzf_compress_pieces((size_t)total, level, true, false, &bt_times,
-                                 [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
-                                     const uint64_t p0 = done, p1 = done + bytes;
-                                     const size_t k = (size_t)(p0 / piece_cap);
-                                     t_gather.start(ps);
-                                     if (p0 < hlen) {
-                                         const uint64_t he = std::min<uint64_t>(hlen, p1);
-                                         SBX_HIP(hipMemcpyAsync(d_in, header.data() + p0, he - p0, hipMemcpyHostToDevice, ps));
-                                     }
-                                     const uint64_t r0 = bounds[k], r1 = std::min<uint64_t>(n, (uint64_t)bounds[k + 1] + 1);
-                                     launch_gather_records(d_store.p, d_off.p, d_perm, d_out_off, r0, r1, p0, p1, d_in, ps);
-                                     t_gather.stop(ps);
-                                     st.ms_gather += t_gather.ms();
-                                 },
-                                 [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
-        } catch (...) { fclose(f); throw; }
-        ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
-        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + out_path);
+        write_permuted_bam(out_path, header, out, d_store.p, d_off.p, d_perm, d_out_off, n, level, &out_created, &st.ms_gather, &bt_times);
         const double w4 = wall_now();
         st.n_records_in = n_in; st.n_records_out = n;
         st.inflated_bytes = u_total; st.sorted_stream_bytes = total; st.compressed_bytes = bt_times.out_bytes + 28;

@@ -1,0 +1,148 @@
+// engine_store.hpp -- what sbx_sort_bam and sbx_markdup share around their kernels: the plan of the resident record store (1 x the
+// inflated records of the file next to one batch of the read pass), the copy of a batch into it, and the writer that turns
+// "header + records of the store in the order of a permutation" into a BGZF file piece by piece (offsets, piece bounds, K9c gather,
+// deflate).  The stream written never exists as a whole.
+#pragma once
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include "engine_ctx.hpp"
+#include "engine_stream.hpp"
+#include "sort.hpp"
+
+namespace sbx {
+
+// "BAM\1", l_text, text, the binary reference list
+inline std::vector<uint8_t> bam_header_bytes(const std::string& text, const std::vector<RefSeq>& refs) {
+    std::vector<uint8_t> h;
+    auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) h.push_back((uint8_t)(v >> (8 * k))); };
+    h.insert(h.end(), {'B', 'A', 'M', 1});
+    put32((uint32_t)text.size());
+    h.insert(h.end(), text.begin(), text.end());
+    put32((uint32_t)refs.size());
+    for (const RefSeq& r : refs) {
+        put32((uint32_t)r.name.size() + 1);
+        h.insert(h.end(), r.name.begin(), r.name.end());
+        h.push_back(0);
+        put32((uint32_t)r.length);
+    }
+    return h;
+}
+
+inline bool same_file(const char* a, const char* b) {
+    struct stat sa, sb;
+    if (stat(a, &sa) != 0 || stat(b, &sb) != 0) return false;
+    return sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+}
+
+// a device array of the kept records that grows while the batches arrive (the number of records is not known in advance)
+template <class T>
+void grow_keeping(DevBuf<T>& b, size_t used, size_t want, hipStream_t s) {
+    if (want <= b.n) return;
+    DevBuf<T> nb(want + want / 2 + 1024);
+    if (used) SBX_HIP(hipMemcpyAsync(nb.p, b.p, used * sizeof(T), hipMemcpyDeviceToDevice, s));
+    SBX_HIP(hipStreamSynchronize(s));
+    b = std::move(nb);
+}
+
+// ---- device memory: the record store, the per-record arrays, one read batch, one output piece ----
+struct StorePlan {
+    uint64_t u_total, u_first;      // inflated bytes of the file, offset of its first record
+    uint64_t store_bytes;           // the records
+    uint64_t est_records;           // (as K2 sizes its descriptors; the arrays grow when it is more)
+    uint64_t fixed_need;            // store + per-record arrays
+    uint64_t batch_u;               // inflated bytes per batch of the read pass
+};
+// hlen: bytes of the output header; per_record: bytes of per-record arrays the command keeps; doing: "sorting" (for the refusal).
+// SBX_ENOMEM when the file does not fit the device.
+inline StorePlan plan_record_store(sbx_ctx* c, uint64_t hlen, uint64_t per_record, const char* doing) {
+    StorePlan p{};
+    const BlockTable& bt = c->blocks;
+    p.u_total = bt.out_off.back();
+    p.u_first = std::min<uint64_t>(c->hdr.first_record_off, p.u_total);
+    p.store_bytes = p.u_total - p.u_first;
+    p.est_records = p.store_bytes / 160 + 4096;
+    const uint64_t piece_bytes = std::min<uint64_t>(kBgzfPieceBlocks * (uint64_t)kBgzfPayload, p.store_bytes + hlen + kBgzfPayload);
+    const uint64_t out_reserve = piece_bytes * 3 + (8ull << 20);    // piece, slots, packed blocks (kBgzfSlot ~ kBgzfPayload)
+    p.fixed_need = p.store_bytes + p.est_records * per_record;
+    size_t free_b = 0, total_b = 0;
+    SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t min_batch = 5ull * (64ull << 20);
+    if (p.fixed_need + std::max(out_reserve, min_batch) > free_b)
+        throw Error(SBX_ENOMEM, std::string("the file does not fit the device: ") + doing + " it needs " +
+                                    std::to_string(p.fixed_need + std::max(out_reserve, min_batch)) + " bytes of device memory (" +
+                                    std::to_string(p.store_bytes) + " of inflated records resident), " + std::to_string(free_b) +
+                                    " are free; an out-of-core merge is not implemented");
+    p.batch_u = index_batch_bytes(p.fixed_need);
+    return p;
+}
+
+// the records of a batch (for_each_record_batch: inflated offsets [cur, next), U[0] = offset `base`) go behind those of the batches before
+inline void copy_batch_to_store(sbx_ctx* c, uint8_t* d_store, uint64_t u_first, uint64_t cur, uint64_t base, uint64_t next, hipStream_t s) {
+    if (next > cur) SBX_HIP(hipMemcpyAsync(d_store + (cur - u_first), c->U() + (cur - base), next - cur, hipMemcpyDeviceToDevice, s));
+}
+
+// ---- the writer ----
+constexpr uint64_t kPieceCap = kBgzfPieceBlocks * (uint64_t)kBgzfPayload;
+struct OutputPlan {
+    uint64_t total = 0;             // bytes of the stream: header + records
+    std::vector<uint32_t> bounds;   // the first record that ends behind byte k * kPieceCap
+};
+// Offsets of the records d_perm[0, n) in the output stream (d_out_off[0, n], n + 2 words) and the records at the piece boundaries.
+// *ms_gather += device time of the offsets.
+inline OutputPlan plan_output(const uint32_t* d_len, const uint32_t* d_perm, uint64_t n, uint64_t hlen, uint64_t* d_out_off, hipStream_t s,
+                              double* ms_gather) {
+    OutputPlan p;
+    p.total = hlen;
+    EventTimer t;
+    DevBuf<uint64_t> d_tile_sum(len_tiles(n) + 2);
+    t.start(s);
+    launch_sorted_offsets(d_len, d_perm, n, hlen, d_tile_sum.p, d_out_off, s);
+    t.stop(s);
+    if (n) SBX_HIP(hipMemcpyAsync(&p.total, d_out_off + n, 8, hipMemcpyDeviceToHost, s));
+    SBX_HIP(hipStreamSynchronize(s));
+    if (n) *ms_gather += t.ms();                        // (the offsets are the gather's preparation)
+    const uint32_t n_bounds = (uint32_t)((p.total + kPieceCap - 1) / kPieceCap) + 1;
+    p.bounds.assign(n_bounds, (uint32_t)n);
+    if (n) {
+        DevBuf<uint32_t> d_bounds(n_bounds);
+        launch_piece_bounds(d_out_off, n, kPieceCap, n_bounds, d_bounds.p, s);
+        SBX_HIP(hipMemcpyAsync(p.bounds.data(), d_bounds.p, (size_t)n_bounds * 4, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+    }
+    return p;
+}
+
+// K9c + deflate, piece by piece, into out_path (+ the EOF block).  *out_created is set as soon as the file exists (the caller
+// removes it when the call fails).
+inline void write_permuted_bam(const char* out_path, const std::vector<uint8_t>& header, const OutputPlan& plan, const uint8_t* d_store,
+                               const uint64_t* d_off, const uint32_t* d_perm, const uint64_t* d_out_off, uint64_t n, int level, bool* out_created,
+                               double* ms_gather, BgzfPieceTimes* bt_times) {
+    const uint64_t hlen = header.size();
+    FILE* f = fopen(out_path, "wb");
+    if (!f) throw Error(SBX_EIO, std::string("cannot write ") + out_path);
+    *out_created = true;
+    bool ok = true;
+    EventTimer t_gather;
+    try {
+        bgzf_compress_pieces((size_t)plan.total, level, true, false, bt_times,
+                             [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
+                                 const uint64_t p0 = done, p1 = done + bytes;
+                                 const size_t k = (size_t)(p0 / kPieceCap);
+                                 t_gather.start(ps);
+                                 if (p0 < hlen) {
+                                     const uint64_t he = std::min<uint64_t>(hlen, p1);
+                                     SBX_HIP(hipMemcpyAsync(d_in, header.data() + p0, he - p0, hipMemcpyHostToDevice, ps));
+                                 }
+                                 const uint64_t r0 = plan.bounds[k], r1 = std::min<uint64_t>(n, (uint64_t)plan.bounds[k + 1] + 1);
+                                 launch_gather_records(d_store, d_off, d_perm, d_out_off, r0, r1, p0, p1, d_in, ps);
+                                 t_gather.stop(ps);
+                                 *ms_gather += t_gather.ms();
+                             },
+                             [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
+    } catch (...) { fclose(f); throw; }
+    ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
+    if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + out_path);
+}
+
+}  // namespace sbx

@@ -70,57 +70,65 @@ SBX_SORT_HD uint32_t plan_passes(uint64_t varying, uint32_t* shift, uint32_t* bi
 namespace sbx {
 namespace sortc {
 
-// The text SamHeader.toSam prints (BioD bio/std/hts/sam/header.d:626-656) for a header parsed from `text` (header.d:473-545) whose
-// sorting order was set to coordinate (sambamba/sort.d:294-298): "@HD\tVN:<version>\tSO:coordinate", the version being that of an @HD
-// line that is the first line of the input (1.3 otherwise); then the @SQ, @RG and @PG lines in order of first appearance -- a later
-// line with the same SN / ID is dropped -- each with only the fields header.d:216-254 declares, in the declared order, empty strings
-// and zero numbers left out; then the @CO lines.  Lines shorter than three characters are skipped.  false: a line does not start
-// with '@', is of no known type, or has a number field (LN, PI) that is not a number (the reference throws).
-inline bool sort_header_text(const char* text, size_t n, std::string* out, std::string* why) {
+// A SAM header text as SamHeader's constructor reads it (BioD bio/std/hts/sam/header.d:473-545) and SamHeader.toSam prints it back
+// (header.d:626-656): the version and sorting order of an @HD line that is the first line of the input (1.3 and none otherwise);
+// the @SQ, @RG and @PG lines in order of first appearance -- a later line with the same SN / ID is dropped -- each with only the
+// fields header.d:216-254 declares, in the declared order, empty strings and zero numbers left out; the @CO lines.  Lines shorter
+// than three characters are skipped.  Shared by `sort` (below) and `markdup` (markdup_core.hpp).
+struct HeaderLine { std::string id, text; };
+struct ParsedHeader {
+    std::string version = "1.3", sorting_order;      // sorting_order: the SO field as written ("" when there is none)
+    std::vector<HeaderLine> sq, rg, pg;
+    std::vector<std::string> rg_library;             // LB of every line of rg ("" when absent)
+    std::vector<std::string> comments;
+};
+
+// value of field `key` of a header line: the last occurrence wins (parse assigns field by field)
+inline std::string header_field(const std::string& line, const char* key) {
+    std::string v;
+    size_t p = 3;
+    while (p <= line.size()) {
+        size_t e = line.find('\t', p);
+        if (e == std::string::npos) e = line.size();
+        if (e - p >= 3 && line[p + 2] == ':' && line[p] == key[0] && line[p + 1] == key[1]) v = line.substr(p + 3, e - p - 3);
+        p = e + 1;
+    }
+    return v;
+}
+
+// false: a line does not start with '@', is of no known type, or has a number field (LN, PI) that is not a number (the reference throws).
+inline bool parse_header(const char* text, size_t n, ParsedHeader* out, std::string* why) {
     struct Decl { const char* prefix; std::vector<const char*> fields; const char* numeric; };
     static const Decl kSq{"@SQ", {"SN", "LN", "AN", "AS", "DS", "M5", "SP", "UR", "AH"}, "LN"};
     static const Decl kRg{"@RG", {"ID", "BC", "CN", "DS", "DT", "FO", "KS", "LB", "PG", "PI", "PL", "PU", "SM", "PM"}, "PI"};
     static const Decl kPg{"@PG", {"ID", "PN", "CL", "PP", "VN"}, ""};
-    struct Line { std::string id, text; };
-    std::vector<Line> sq, rg, pg;
-    std::vector<std::string> comments;
-    std::string version = "1.3";
+    ParsedHeader& h = *out;
+    h = ParsedHeader();
     bool first = true;
     // (a header text may be padded with zero bytes: the text ends at the first one)
     for (size_t k = 0; k < n; ++k) if (!text[k]) { n = k; break; }
     auto fail = [&](const std::string& m) { if (why) *why = m; return false; };
-    // value of field `key` of a line: the last occurrence wins (parse assigns field by field)
-    auto field = [](const std::string& line, const char* key) {
-        std::string v;
-        size_t p = 3;
-        while (p <= line.size()) {
-            size_t e = line.find('\t', p);
-            if (e == std::string::npos) e = line.size();
-            if (e - p >= 3 && line[p + 2] == ':' && line[p] == key[0] && line[p + 1] == key[1]) v = line.substr(p + 3, e - p - 3);
-            p = e + 1;
-        }
-        return v;
-    };
-    auto add = [&](std::vector<Line>& to, const Decl& d, const std::string& line) -> bool {
-        Line l;
+    // 0: malformed number, 1: added, 2: duplicate (the first line stays)
+    auto add = [&](std::vector<HeaderLine>& to, const Decl& d, const std::string& line) -> int {
+        HeaderLine l;
         l.text = d.prefix;
         for (size_t k = 0; k < d.fields.size(); ++k) {
-            std::string v = field(line, d.fields[k]);
+            std::string v = header_field(line, d.fields[k]);
             const bool numeric = d.fields[k][0] == d.numeric[0] && d.fields[k][1] == d.numeric[1];
             if (numeric && !v.empty()) {
                 // to!uint / to!int: digits only (a sign for PI), printed back as a number
                 size_t i = (d.numeric[0] == 'P' && (v[0] == '-' || v[0] == '+')) ? 1 : 0;
-                if (i == v.size()) return false;
-                for (size_t j = i; j < v.size(); ++j) if (v[j] < '0' || v[j] > '9') return false;
+                if (i == v.size()) return 0;
+                for (size_t j = i; j < v.size(); ++j) if (v[j] < '0' || v[j] > '9') return 0;
                 const long long x = strtoll(v.c_str(), nullptr, 10);
                 v = x == 0 ? std::string() : std::to_string(x);
             }
             if (k == 0) l.id = v;
             if (!v.empty()) { l.text += '\t'; l.text += d.fields[k]; l.text += ':'; l.text += v; }
         }
-        for (const Line& o : to) if (o.id == l.id) return true;      // duplicate: the first line stays
+        for (const HeaderLine& o : to) if (o.id == l.id) return 2;
         to.push_back(l);
-        return true;
+        return 1;
     };
     for (size_t p = 0; p <= n;) {
         size_t e = p;
@@ -128,24 +136,36 @@ inline bool sort_header_text(const char* text, size_t n, std::string* out, std::
         const std::string line(text + p, e - p);
         p = e + 1;
         if (line.size() < 3) continue;
-        if (first && line.compare(0, 3, "@HD") == 0) version = field(line, "VN");
+        if (first && line.compare(0, 3, "@HD") == 0) { h.version = header_field(line, "VN"); h.sorting_order = header_field(line, "SO"); }
         if (line[0] != '@') return fail("Header lines must start with @");
         const std::string ty = line.substr(1, 2);
-        bool ok = true;
-        if (ty == "SQ") ok = add(sq, kSq, line);
-        else if (ty == "RG") ok = add(rg, kRg, line);
-        else if (ty == "PG") ok = add(pg, kPg, line);
+        int ok = 1;
+        if (ty == "SQ") ok = add(h.sq, kSq, line);
+        else if (ty == "RG") { ok = add(h.rg, kRg, line); if (ok == 1) h.rg_library.push_back(header_field(line, "LB")); }
+        else if (ty == "PG") ok = add(h.pg, kPg, line);
         else if (ty == "HD") {}
-        else if (ty == "CO") comments.push_back(line.size() > 4 ? line.substr(4) : std::string());
+        else if (ty == "CO") h.comments.push_back(line.size() > 4 ? line.substr(4) : std::string());
         else return fail("unknown header line type " + line.substr(0, 3));
         if (!ok) return fail("malformed number in header line " + line);
         first = false;
     }
-    out->clear();
-    *out += "@HD\tVN:" + version + "\tSO:coordinate\n";
-    for (const auto* v : {&sq, &rg, &pg})
-        for (const Line& l : *v) { *out += l.text; *out += '\n'; }
-    for (const std::string& c : comments) { *out += "@CO\t"; *out += c; *out += '\n'; }
+    return true;
+}
+
+// toSam with the sorting order `so` ("": no SO field)
+inline std::string serialise_header(const ParsedHeader& h, const std::string& so) {
+    std::string out = "@HD\tVN:" + h.version + (so.empty() ? std::string() : "\tSO:" + so) + "\n";
+    for (const auto* v : {&h.sq, &h.rg, &h.pg})
+        for (const HeaderLine& l : *v) { out += l.text; out += '\n'; }
+    for (const std::string& c : h.comments) { out += "@CO\t"; out += c; out += '\n'; }
+    return out;
+}
+
+// The header of the sorted file: the sorting order was set to coordinate (sambamba/sort.d:294-298).
+inline bool sort_header_text(const char* text, size_t n, std::string* out, std::string* why) {
+    ParsedHeader h;
+    if (!parse_header(text, n, &h, why)) return false;
+    *out = serialise_header(h, "coordinate");
     return true;
 }
 
