@@ -99,6 +99,15 @@ extern (C) nothrow @nogc {
     int sbx_markdup(const(char)* in_path, const(char)* out_path, int remove_duplicates, int level, const(char)* pg_command_line, int device,
                     sbx_markdup_stats* stats, char* err, size_t errlen);
     int sbx_markdup_header_text(const(char)* text, size_t n, const(char)* pg_command_line, char* out_, size_t cap, size_t* out_len);
+    struct sbx_merge_stats {
+        ulong n_records_in; ulong n_records_out; ulong n_records_rewritten; long bytes_grown;
+        ulong inflated_bytes; ulong merged_stream_bytes; ulong compressed_bytes;
+        uint n_inputs; uint key_bits; uint n_sort_passes; uint n_batches;
+        double ms_inflate; double ms_index; double ms_rewrite; double ms_sort; double ms_gather; double ms_deflate; double ms_total_wall;
+    }
+    int sbx_merge_bam(const(char)* out_path, const(char*)* in_paths, int n_inputs, const(sbx_filter)* filter, int level, int with_index,
+                      int device, sbx_merge_stats* stats, char* err, size_t errlen);
+    int sbx_merge_header_text(const(char*)* texts, const(size_t)* lens, int n, char* out_, size_t cap, size_t* out_len);
     int sbx_inflate_blocks(const(ubyte)* comp, const(ulong)* comp_off, const(uint)* comp_len, const(uint)* isize,
                            uint n_blocks, ubyte* out_, const(ulong)* out_off, char* err, size_t errlen);
     sbx_ctx* sbx_open(const(char*)* bam_paths, int n_bams, int device, char* err, size_t errlen);

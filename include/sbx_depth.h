@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -238,6 +238,40 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
  * or queryname -- with "@PG ID:sambamba CL:<pg_command_line> PP:<last @PG> VN:1.0" added unless pg_command_line is NULL or an @PG
  * with ID:sambamba exists.  Lengths and errors as sbx_sort_header_text. */
 int sbx_markdup_header_text(const char* text, size_t n, const char* pg_command_line, char* out, size_t cap, size_t* out_len);
+
+/* `sambamba merge` (sambamba/merge.d) for coordinate-sorted inputs: the headers are merged as SamHeaderMerger does (sbx_merge_header_text),
+ * every record gets its reference ids renumbered into the merged dictionary -- ref_id AND next_ref_id; the reference renumbers only
+ * ref_id -- and the value of its RG:Z / PG:Z tag replaced when the merged header renamed that id, and the records of all inputs are
+ * sorted by coordinate with sbx_sort_bam's stable sort: ties (same reference, position and strand) come out lower input first, then
+ * in file order.  The inputs are not assumed to BE sorted: the output is sorted whatever the records say.  filter is applied to the
+ * records as they are in their input.  All inputs are resident on the device: what does not fit next to one batch of the read pass is
+ * refused with SBX_ENOMEM, more than 2^32 records and inputs sorted by read name with SBX_EUNSUPPORTED, fewer than two inputs, more
+ * than SBX_MERGE_MAX_INPUTS, or an output that is one of the inputs with SBX_EINVAL.  n_records_rewritten: records in which a
+ * reference id or a tag value changed; bytes_grown: bytes of the records written minus bytes of the same records as read.
+ * Milliseconds are device time (inflate = K1, index = K2, rewrite = K11 or, for an input nothing changes in, K9a + the copy into
+ * the record store, sort = K9b, gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of
+ * the call without the index.
+ * How closely a record is checked depends on whether its input is rewritten.  An input with a renumbered reference or a renamed id
+ * goes through K11, which checks the fixed part and every aux field against block_size and refuses the call with SBX_EFORMAT.  An
+ * input nothing changes in is copied and checked as sbx_sort_bam checks a record: block_size against the batch, ref_id against the
+ * input's dictionary (with a filter: the verdict of the filter pass); a malformed aux field is copied as it is.  Which of the two
+ * an input gets depends on the other inputs' headers.  SBX_MERGE_FORCE_REWRITE=1 sends every input through K11. */
+#define SBX_MERGE_MAX_INPUTS 1024
+typedef struct {
+    uint64_t n_records_in, n_records_out;      /* summed over the inputs; out < in only with a filter */
+    uint64_t n_records_rewritten;
+    int64_t bytes_grown;
+    uint64_t inflated_bytes, merged_stream_bytes, compressed_bytes;
+    uint32_t n_inputs, key_bits, n_sort_passes, n_batches;
+    double ms_inflate, ms_index, ms_rewrite, ms_sort, ms_gather, ms_deflate, ms_total_wall;
+} sbx_merge_stats;
+/* filter, level, with_index, stats as sbx_sort_bam.  On failure no output file is left behind. */
+int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_inputs, const sbx_filter* filter, int level, int with_index,
+                  int device, sbx_merge_stats* stats, char* err, size_t errlen);
+/* The merged header text for n header texts in input order (host only).  Lengths as sbx_sort_header_text; SBX_EFORMAT for a text the
+ * reference's parser throws on, SBX_EINVAL when the sorting orders forbid the merge or one reference name has two lengths,
+ * SBX_EUNSUPPORTED for queryname.  The message of a refusal is written to out when it fits. */
+int sbx_merge_header_text(const char* const* texts, const size_t* lens, int n, char* out, size_t cap, size_t* out_len);
 
 /* ---- engine seam ------------------------------------------------------------ */
 

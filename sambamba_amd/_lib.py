@@ -10,6 +10,7 @@ _CLI_PATH = os.path.join(HERE, "csrc", "sbx-depth")
 _FLAGSTAT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-flagstat")
 _SORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sort")
 _MARKDUP_CLI_PATH = os.path.join(HERE, "csrc", "sbx-markdup")
+_MERGE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-merge")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -95,6 +96,12 @@ class MarkdupStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_sort_passes", "n_batches")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_ends", "ms_pairing", "ms_groups", "ms_gather", "ms_deflate", "ms_total_wall")])
 
+class MergeStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_records_in", "n_records_out", "n_records_rewritten")] + [("bytes_grown", C.c_int64)] +
+                [(k, C.c_uint64) for k in ("inflated_bytes", "merged_stream_bytes", "compressed_bytes")] +
+                [(k, C.c_uint32) for k in ("n_inputs", "key_bits", "n_sort_passes", "n_batches")] +
+                [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_rewrite", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
+
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
 
 EXPORTS = [
@@ -105,6 +112,7 @@ EXPORTS = [
     "sbx_format_base_rows", "sbx_stream_base_rows", "sbx_plan_batches", "sbx_run_batch", "sbx_last_run_stats", "sbx_tile_info", "sbx_next_active_range", "sbx_preload",
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
     "sbx_sort_bam", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
+    "sbx_merge_bam", "sbx_merge_header_text",
 ]
 
 _lib = None
@@ -128,6 +136,10 @@ def sort_cli_path():
 
 def markdup_cli_path():
     return _MARKDUP_CLI_PATH
+
+
+def merge_cli_path():
+    return _MERGE_CLI_PATH
 
 
 def lib():
@@ -190,6 +202,9 @@ def lib():
     L.sbx_sort_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_markdup.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(MarkdupStats), C.c_char_p, C.c_size_t]
     L.sbx_markdup_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sbx_merge_bam.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.POINTER(MergeStats),
+                                C.c_char_p, C.c_size_t]
+    L.sbx_merge_header_text.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_depth_base_tile_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -205,7 +220,7 @@ def lib():
     for name, ty in (("sbx_region", Region), ("sbx_header_info", HeaderInfo), ("sbx_region_stats", RegionStats),
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
-                     ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats)):
+                     ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -565,3 +580,35 @@ class Depth:
         self._check(self._L.sbx_depth_base_tile(self._ctx, ref_id, beg, end, out.ctypes.data,
                                                 cov.ctypes.data if with_covered else None))
         return (out, cov) if with_covered else out
+
+
+def merge(out_path, inputs, filter=None, level=-1, index=False, device=-1):
+    """sbx_merge_bam (`sambamba merge`): merges the coordinate-sorted BAMs `inputs` into out_path on the device; filter is a -F query
+    string (None: every record); index=True also writes out_path + ".bai".  Returns the fields of sbx_merge_stats as a dict."""
+    L = lib()
+    f = compile_filter(filter) if filter else None
+    st = MergeStats()
+    err = C.create_string_buffer(512)
+    paths = (C.c_char_p * max(1, len(inputs)))(*[p.encode() for p in inputs])
+    rc = L.sbx_merge_bam(out_path.encode(), paths, len(inputs), C.byref(f) if f is not None else None, int(level), int(index), device,
+                         C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: getattr(st, k) for k, _ in MergeStats._fields_}
+
+
+def merge_header_text(texts):
+    """sbx_merge_header_text: the header text `sambamba merge` writes for the header texts of its inputs, in input order (str or bytes
+    -> the type of the first), host only.  A refusal raises SbxError with the reference's message."""
+    L = lib()
+    data = [t if isinstance(t, bytes) else t.encode() for t in texts]
+    arr = (C.c_char_p * max(1, len(data)))(*data)
+    lens = (C.c_size_t * max(1, len(data)))(*[len(d) for d in data])
+    n = C.c_size_t(0)
+    first = L.sbx_merge_header_text(arr, lens, len(data), None, 0, C.byref(n))
+    buf = C.create_string_buffer(n.value + 1)
+    rc = L.sbx_merge_header_text(arr, lens, len(data), buf, n.value + 1, C.byref(n))
+    if first not in (0, -8) or rc != 0:
+        raise SbxError(rc if rc != 0 else first, buf.raw[:n.value].decode())
+    out = buf.raw[:n.value]
+    return out if not texts or isinstance(texts[0], bytes) else out.decode()

@@ -57,6 +57,7 @@ size_t sbx_abi_sizeof(const char* name) {
     if (n == "sbx_flagstat_counts") return sizeof(sbx_flagstat_counts);
     if (n == "sbx_sort_stats") return sizeof(sbx_sort_stats);
     if (n == "sbx_markdup_stats") return sizeof(sbx_markdup_stats);
+    if (n == "sbx_merge_stats") return sizeof(sbx_merge_stats);
     return 0;
 }
 

@@ -88,7 +88,7 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
             copy_batch_to_store(c, d_store.p, u_first, cur, base, next, s);
             SortKeysArgs a{};
             a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
-            a.n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
+            a.n_ref = n_ref; a.key_n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
             a.store_delta = (int64_t)base - (int64_t)u_first;
             a.out_base = n_kept;
             a.key = d_key.p; a.off = d_off.p; a.len = d_len.p; a.acc = d_acc.p;
@@ -118,31 +118,16 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         Stream stream;
         stream.create();
         s = stream.get();
-        uint32_t shifts[8], key_bits = 0;
-        const uint32_t n_passes = n ? sortc::plan_passes(acc[kSortAccOr] ^ acc[kSortAccAnd], shifts, &key_bits) : 0;
-        DevBuf<uint64_t> d_key2((size_t)n + 2);
-        DevBuf<uint32_t> d_val((size_t)n + 2), d_val2((size_t)n + 2);
-        EventTimer t_sort;
-        uint64_t* keys[2] = {d_key.p, d_key2.p};
-        uint32_t* vals[2] = {d_val.p, d_val2.p};
-        int at = 0;
-        {
-            DevBuf<uint32_t> d_hist(radix_hist_entries(n) + 4);
-            DevBuf<uint64_t> d_hist_base(radix_hist_entries(n) + 4);
-            t_sort.start(s);
-            launch_iota(vals[0], n, s);
-            for (uint32_t p = 0; p < n_passes; ++p, at ^= 1)
-                launch_radix_pass(keys[at], vals[at], keys[at ^ 1], vals[at ^ 1], n, shifts[p], d_hist.p, d_hist_base.p, s);
-            t_sort.stop(s);
-            SBX_HIP(hipStreamSynchronize(s));
-        }
-        const uint32_t* d_perm = vals[at];
+        ResidentOrder order;
+        sort_resident(d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
+        const uint32_t* d_perm = order.perm;
+        const uint32_t key_bits = order.key_bits, n_passes = order.n_passes;
         // the keys are done with: one of their buffers holds the output offsets
-        uint64_t* d_out_off = d_key2.p;
+        uint64_t* d_out_off = order.key2.p;
         d_key.release();
         const OutputPlan out = plan_output(d_len.p, d_perm, n, hlen, d_out_off, s, &st.ms_gather);
         const uint64_t total = out.total;
-        st.ms_sort = t_sort.ms();
+        st.ms_sort = order.ms_sort;
         if (total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the sorted records do not add up");
         d_len.release();
         const double w3 = wall_now();

@@ -1,5 +1,6 @@
-// engine_store.hpp -- what sbx_sort_bam and sbx_markdup share around their kernels: the plan of the resident record store (1 x the
-// inflated records of the file next to one batch of the read pass), the copy of a batch into it, and the writer that turns
+// engine_store.hpp -- what sbx_sort_bam, sbx_markdup and sbx_merge_bam share around their kernels: the plan of the resident record store (1 x the
+// inflated records of the file next to one batch of the read pass), the copy of a batch into it, K9b over the keys of the resident
+// records (sort and merge), and the writer that turns
 // "header + records of the store in the order of a permutation" into a BGZF file piece by piece (offsets, piece bounds, K9c gather,
 // deflate).  The stream written never exists as a whole.
 #pragma once
@@ -9,6 +10,7 @@
 #include "engine_ctx.hpp"
 #include "engine_stream.hpp"
 #include "sort.hpp"
+#include "sort_core.hpp"
 
 namespace sbx {
 
@@ -53,14 +55,12 @@ struct StorePlan {
     uint64_t fixed_need;            // store + per-record arrays
     uint64_t batch_u;               // inflated bytes per batch of the read pass
 };
-// hlen: bytes of the output header; per_record: bytes of per-record arrays the command keeps; doing: "sorting" (for the refusal).
-// SBX_ENOMEM when the file does not fit the device.
-inline StorePlan plan_record_store(sbx_ctx* c, uint64_t hlen, uint64_t per_record, const char* doing) {
+// store_bytes: the records that stay resident (for several inputs: their sum, plus what rewriting may add); hlen: bytes of the output
+// header; per_record: bytes of per-record arrays the command keeps; doing: "sorting" (for the refusal); what: "the file does" / "the files do".
+// SBX_ENOMEM when they do not fit the device.
+inline StorePlan plan_store_bytes(uint64_t store_bytes, uint64_t hlen, uint64_t per_record, const char* doing, const char* what) {
     StorePlan p{};
-    const BlockTable& bt = c->blocks;
-    p.u_total = bt.out_off.back();
-    p.u_first = std::min<uint64_t>(c->hdr.first_record_off, p.u_total);
-    p.store_bytes = p.u_total - p.u_first;
+    p.store_bytes = store_bytes;
     p.est_records = p.store_bytes / 160 + 4096;
     const uint64_t piece_bytes = std::min<uint64_t>(kBgzfPieceBlocks * (uint64_t)kBgzfPayload, p.store_bytes + hlen + kBgzfPayload);
     const uint64_t out_reserve = piece_bytes * 3 + (8ull << 20);    // piece, slots, packed blocks (kBgzfSlot ~ kBgzfPayload)
@@ -69,17 +69,56 @@ inline StorePlan plan_record_store(sbx_ctx* c, uint64_t hlen, uint64_t per_recor
     SBX_HIP(hipMemGetInfo(&free_b, &total_b));
     const uint64_t min_batch = 5ull * (64ull << 20);
     if (p.fixed_need + std::max(out_reserve, min_batch) > free_b)
-        throw Error(SBX_ENOMEM, std::string("the file does not fit the device: ") + doing + " it needs " +
+        throw Error(SBX_ENOMEM, std::string(what) + " not fit the device: " + doing + " it needs " +
                                     std::to_string(p.fixed_need + std::max(out_reserve, min_batch)) + " bytes of device memory (" +
                                     std::to_string(p.store_bytes) + " of inflated records resident), " + std::to_string(free_b) +
                                     " are free; an out-of-core merge is not implemented");
     p.batch_u = index_batch_bytes(p.fixed_need);
     return p;
 }
+// one input: the store holds its inflated records
+inline StorePlan plan_record_store(sbx_ctx* c, uint64_t hlen, uint64_t per_record, const char* doing) {
+    const uint64_t u_total = c->blocks.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
+    StorePlan p = plan_store_bytes(u_total - u_first, hlen, per_record, doing, "the file does");
+    p.u_total = u_total;
+    p.u_first = u_first;
+    return p;
+}
 
 // the records of a batch (for_each_record_batch: inflated offsets [cur, next), U[0] = offset `base`) go behind those of the batches before
 inline void copy_batch_to_store(sbx_ctx* c, uint8_t* d_store, uint64_t u_first, uint64_t cur, uint64_t base, uint64_t next, hipStream_t s) {
     if (next > cur) SBX_HIP(hipMemcpyAsync(d_store + (cur - u_first), c->U() + (cur - base), next - cur, hipMemcpyDeviceToDevice, s));
+}
+
+// ---- K9b over the keys of the resident records ----
+struct ResidentOrder {
+    DevBuf<uint64_t> key2;          // the second key buffer; free for the output offsets once the sort is done
+    DevBuf<uint32_t> val, val2;
+    const uint32_t* perm = nullptr; // [n] record numbers in key order, equal keys in the order they had (one of val / val2)
+    uint32_t key_bits = 0, n_passes = 0;
+    double ms_sort = 0;
+};
+// Stable radix sort of d_key[0, n) (n + 2 words; overwritten) over the key bits that vary: `varying` = OR of the keys ^ AND of the keys.
+inline void sort_resident(uint64_t* d_key, uint64_t n, uint64_t varying, hipStream_t s, ResidentOrder* o) {
+    uint32_t shifts[8];
+    o->n_passes = n ? sortc::plan_passes(varying, shifts, &o->key_bits) : 0;
+    o->key2 = DevBuf<uint64_t>((size_t)n + 2);
+    o->val = DevBuf<uint32_t>((size_t)n + 2);
+    o->val2 = DevBuf<uint32_t>((size_t)n + 2);
+    EventTimer t_sort;
+    uint64_t* keys[2] = {d_key, o->key2.p};
+    uint32_t* vals[2] = {o->val.p, o->val2.p};
+    int at = 0;
+    DevBuf<uint32_t> d_hist(radix_hist_entries(n) + 4);
+    DevBuf<uint64_t> d_hist_base(radix_hist_entries(n) + 4);
+    t_sort.start(s);
+    launch_iota(vals[0], n, s);
+    for (uint32_t p = 0; p < o->n_passes; ++p, at ^= 1)
+        launch_radix_pass(keys[at], vals[at], keys[at ^ 1], vals[at ^ 1], n, shifts[p], d_hist.p, d_hist_base.p, s);
+    t_sort.stop(s);
+    SBX_HIP(hipStreamSynchronize(s));
+    o->perm = vals[at];
+    o->ms_sort = t_sort.ms();
 }
 
 // ---- the writer ----

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kSortKeysThreads) void k_sort_keys(SortKeysArgs a, 
             len = bs + 4u;
             // (the chain of K2 ends every record inside the batch; a record that would not is never copied)
             bad = bs < 32u || bs > 0x7FFFFFF0u || rec_off + len > a.u_end;
-            key = sortc::sort_key(ref, d.pos, d.flag, a.n_ref);
+            key = sortc::sort_key(ref, d.pos, d.flag, a.key_n_ref);
         }
         keep = keep && !bad;
     }

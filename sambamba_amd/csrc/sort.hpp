@@ -13,7 +13,8 @@ struct SortKeysArgs {
     const int32_t* rec_ref;
     uint64_t n;                     // records of the batch
     uint64_t u_end;                 // no record of the batch ends behind this offset of U
-    int32_t n_ref;
+    int32_t n_ref;                  // reference ids of the file are in [-1, n_ref)
+    int32_t key_n_ref;              // the id that stands for -1 in the key: n_ref for one file, the size of the merged dictionary in sbx_merge_bam
     uint32_t use_filter;            // != 0: only records with RecDesc::pad == kFilterPass take part (IndexArgs::filter_every)
     int64_t store_delta;            // a record's offset in the record store = rec_off + store_delta
     uint64_t out_base;              // records kept of the batches before

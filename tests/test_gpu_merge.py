@@ -1,0 +1,346 @@
+"""sbx_merge_bam / sbx-merge (`sambamba merge` on the device) against the Python restatement (tests/merge_ref.py): the inflated
+output is compared byte for byte.  Inputs are a few thousand records at most, built with tests/bamgen.py."""
+import ctypes as C
+import os
+import random
+import struct
+import subprocess
+
+import pytest
+
+from tests import bamgen
+from tests import merge_ref as ref
+from tests import sort_ref
+from tests.flagstat_ref import inflate
+from tests.util import scan_bgzf
+
+pytestmark = pytest.mark.gpu
+
+POOL = [("chr1", 100000), ("chr2", 80000), ("chr3", 60000), ("chr4", 50000), ("chrM", 16000), ("alt", 9000)]
+SEQ = "ACGTACGTAC"
+
+
+def text_of(refs, rg=(), pg=(), so="coordinate", co=()):
+    t = "@HD\tVN:1.6\tSO:%s\n" % so + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
+    t += "".join("@RG\tID:%s\tSM:%s\n" % g for g in rg)
+    t += "".join("@PG\tID:%s\tPN:%s%s\n" % (i, pn, "\tPP:" + pp if pp else "") for i, pn, pp in pg)
+    return t + "".join("@CO\t%s\n" % c for c in co)
+
+
+def records(n, n_ref, seed, rgs=(), pgs=(), sort=True, mapq=None):
+    """n records over n_ref references: placed ones with a mate somewhere, unplaced ones, random RG / PG tags among other fields."""
+    rng = random.Random(seed)
+    out = []
+    for i in range(n):
+        tags = b""
+        parts = []
+        if rgs and rng.random() < 0.8:
+            parts.append(bamgen.tag_z("RG", rng.choice(rgs)))
+        if pgs and rng.random() < 0.5:
+            parts.append(bamgen.tag_z("PG", rng.choice(pgs)))
+        if rng.random() < 0.6:
+            parts.append(bamgen.tag_i("NM", rng.randrange(5)))
+        if rng.random() < 0.3:
+            parts.append(bamgen.tag_bytes("ZB", bytes(rng.randrange(256) for _ in range(rng.randrange(0, 9)))))
+        rng.shuffle(parts)
+        tags = b"".join(parts)
+        q = rng.choice((0, 10, 29, 30, 60)) if mapq is None else mapq
+        if n_ref == 0 or rng.random() < 0.07:
+            out.append(bamgen.make_record(-1, -1, "", SEQ[:rng.randrange(4, 11)], 30, name="u%d_%d" % (seed, i), mapq=0, flag=0x4, tags=tags))
+            continue
+        r = rng.randrange(n_ref)
+        seq = SEQ[:rng.randrange(4, 11)]
+        out.append(bamgen.make_record(r, rng.choice((0, 5, 100, 100, rng.randrange(9000))), "%dM" % len(seq), seq, 30, name="r%d_%d" % (seed, i),
+                                      mapq=q, flag=(0x10 if rng.random() < 0.5 else 0) | 0x1, tags=tags,
+                                      next_ref=rng.choice((-1, r, rng.randrange(n_ref))), next_pos=rng.randrange(9000)))
+    if sort:
+        out.sort(key=lambda b: sort_ref.record_key(b, n_ref))
+    return out
+
+
+def write(path, refs, recs, text=None, **kw):
+    bamgen.write_bam(path, refs, recs, text=text if text is not None else text_of(refs), write_index=False, **kw)
+    return path
+
+
+def cli(args, env=None):
+    from sambamba_amd import merge_cli_path
+    return subprocess.run([merge_cli_path()] + list(args), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                          env=dict(os.environ, **env) if env else None)
+
+
+def check_file(path, want):
+    raw = open(path, "rb").read()
+    assert raw[-28:] == bamgen.EOF_BLOCK
+    _, _, _, isize, _, _ = scan_bgzf(path)
+    assert all(int(x) <= 0xFF00 for x in isize)
+    got = inflate(path)
+    assert len(got) == len(want)
+    assert got == want
+    for r in sort_ref.split_stream(got)[3]:
+        assert struct.unpack_from("<i", r, 0)[0] + 4 == len(r)
+
+
+def check(paths, tmp_path, flt=None, keep=None, tag="o", with_cli=True, env=None):
+    """API (and CLI) against the restatement; returns (the API's stats, the expected stream)."""
+    import sambamba_amd
+    want = ref.expected(paths, keep)
+    out_api = str(tmp_path / (tag + ".api.bam"))
+    st = sambamba_amd.merge(out_api, paths, filter=flt)
+    check_file(out_api, want)
+    assert not os.path.exists(out_api + ".bai")
+    n_want = len(sort_ref.split_stream(want)[3])
+    assert st["n_records_out"] == n_want and st["merged_stream_bytes"] == len(want) and st["n_inputs"] == len(paths)
+    assert st["compressed_bytes"] == os.path.getsize(out_api)
+    if with_cli:
+        out_cli = str(tmp_path / (tag + ".cli.bam"))
+        r = cli(([] if not flt else ["-F", flt]) + [out_cli] + list(paths), env=env)
+        assert r.returncode == 0, r.stderr
+        check_file(out_cli, want)
+        assert os.path.exists(out_cli + ".bai")
+    return st, want
+
+
+@pytest.mark.parametrize("n_inputs", [2, 3])
+def test_one_dictionary_no_renames(tmp_path, n_inputs, monkeypatch):
+    import sambamba_amd
+    refs = POOL[:3]
+    text = text_of(refs, rg=[("g1", "s1")], pg=[("bwa", "bwa", None)], co=["same header"])
+    paths = [write(str(tmp_path / ("in%d.bam" % k)), refs, records(1500 + 37 * k, 3, 10 + k, rgs=["g1"], pgs=["bwa"]), text=text) for k in range(n_inputs)]
+    st, want = check(paths, tmp_path)
+    assert st["n_records_rewritten"] == 0 and st["bytes_grown"] == 0
+    # the merge is the sort of the concatenation
+    parts = [sort_ref.split_stream(inflate(p)) for p in paths]
+    cat = inflate(paths[0]) + b"".join(b"".join(p[3]) for p in parts[1:])
+    h_want, _, _, recs_want = sort_ref.split_stream(want)
+    assert sort_ref.split_stream(sort_ref.expected_stream(cat))[3] == recs_want
+    # ... and the rewriting kernel gives the same bytes as the plain copy
+    monkeypatch.setenv("SBX_MERGE_FORCE_REWRITE", "1")
+    forced = str(tmp_path / "forced.bam")
+    st2 = sambamba_amd.merge(forced, paths)
+    check_file(forced, want)
+    assert st2["n_records_rewritten"] == 0 and st2["bytes_grown"] == 0
+
+
+def test_different_dictionaries(tmp_path):
+    a_refs, b_refs = POOL[:3], [POOL[1], POOL[3]]
+    a = write(str(tmp_path / "a.bam"), a_refs, records(1200, 3, 1))
+    b = write(str(tmp_path / "b.bam"), b_refs, records(1100, 2, 2))
+    st, want = check([a, b], tmp_path)
+    recs = sort_ref.split_stream(want)[3]
+    assert st["n_records_rewritten"] > 0 and st["bytes_grown"] == 0
+    # b's chr4 is reference 3 now, in ref_id and next_ref_id; the unplaced reads are last and keep -1
+    ids = [struct.unpack_from("<i", r, 4)[0] for r in recs]
+    assert 3 in ids and ids == sorted(ids, key=lambda x: 4 if x < 0 else x) and ids[-1] == -1
+    assert any(struct.unpack_from("<i", r, 24)[0] == 3 for r in recs)
+    assert sort_ref.split_stream(inflate(str(tmp_path / "o.api.bam")))[2] == 4
+
+
+def test_contradicting_dictionaries(tmp_path):
+    a_refs, b_refs = [POOL[1], POOL[0], POOL[5]], [POOL[0], POOL[1], POOL[2]]
+    a = write(str(tmp_path / "a.bam"), a_refs, records(900, 3, 3))
+    b = write(str(tmp_path / "b.bam"), b_refs, records(900, 3, 4))
+    _, want = check([a, b], tmp_path, with_cli=False)
+    text = sort_ref.split_stream(want)[0].decode()
+    assert [x.split("\t")[1] for x in text.splitlines() if x.startswith("@SQ")] == ["SN:alt", "SN:chr1", "SN:chr2", "SN:chr3"]
+
+
+def _edge_records():
+    """The renamed tag first, in the middle and last among the aux fields, next to B arrays and every scalar type."""
+    scalars = [bamgen.tag_num("XA", "A", "q"), bamgen.tag_num("Xc", "c", -3), bamgen.tag_num("XC", "C", 200), bamgen.tag_num("Xs", "s", -300),
+               bamgen.tag_num("XS", "S", 60000), bamgen.tag_num("Xi", "i", -70000), bamgen.tag_num("XI", "I", 4000000000),
+               bamgen.tag_num("Xf", "f", 1.5), bamgen.tag_z("XZ", "text"), b"XHH" + b"1AE3\0"]
+    arrays = [b"Ba" + b"B" + ty + struct.pack("<I", n) + bytes(range(1, 1 + n * w))
+              for ty, w, n in ((b"c", 1, 3), (b"C", 1, 0), (b"s", 2, 2), (b"S", 2, 1), (b"i", 4, 2), (b"I", 4, 1), (b"f", 4, 3))]
+    rg, pg = bamgen.tag_z("RG", "x"), bamgen.tag_z("PG", "prog")
+    other = b"".join(scalars + arrays)
+    cases = [rg + other, other + rg, b"".join(scalars) + rg + b"".join(arrays), rg + pg, pg + other + rg, b"".join(arrays) + pg + rg + b"".join(scalars),
+             b"RGi" + struct.pack("<i", 7) + other,                 # an RG that is no string: left alone
+             b"RGH" + b"78\0", b"RGA" + b"x",
+             bamgen.tag_z("RG", "absent") + other,                   # not in the header: left alone
+             bamgen.tag_z("RG", "x.1"), bamgen.tag_z("RG", "xx"), bamgen.tag_z("RG", ""), bamgen.tag_z("PG", "pro"),
+             bamgen.tag_z("RG", "keep") + bamgen.tag_z("PG", "prog"),
+             b"", other]
+    out = []
+    for k, tags in enumerate(cases):
+        for pos in (10 + k, 500):
+            out.append(bamgen.make_record(k % 2, pos, "6M", "ACGTAC"[: 6], 30, name="e%02d_%d" % (k, pos), tags=tags, next_ref=1 - k % 2, next_pos=pos))
+    out.append(bamgen.make_record(-1, -1, "", "ACGT", 30, name="unplaced", mapq=0, flag=4, tags=rg + pg))
+    return sorted(out, key=lambda b: sort_ref.record_key(b, 2))
+
+
+def test_renamed_tags_among_other_fields(tmp_path):
+    refs = POOL[:2]
+    a = write(str(tmp_path / "a.bam"), refs, records(300, 2, 5, rgs=["x", "keep"], pgs=["prog"]),
+              text=text_of(refs, rg=[("x", "s1"), ("keep", "s9")], pg=[("prog", "bwa", None)]))
+    b = write(str(tmp_path / "b.bam"), [refs[1], refs[0]], _edge_records(),
+              text=text_of([refs[1], refs[0]], rg=[("x", "s2"), ("keep", "s9")], pg=[("prog", "bowtie", None)]))
+    # (b lists the references the other way round: a cycle, and every reference id of b changes too)
+    st, want = check([a, b], tmp_path)
+    got = sort_ref.split_stream(want)[3]
+    mine = {r[36:36 + r[12] - 1].decode(): r for r in got if r[36:37] in (b"e", b"u")}
+    assert bamgen.tag_z("RG", "x.1") + bamgen.tag_z("PG", "prog.1") in mine["e03_13"] and bamgen.tag_z("RG", "x.1") in mine["unplaced"]
+    assert bamgen.tag_z("RG", "keep") + bamgen.tag_z("PG", "prog.1") in mine["e14_24"]
+    assert b"RGi" + struct.pack("<i", 7) in mine["e06_16"] and bamgen.tag_z("RG", "absent") in mine["e09_19"]
+    assert st["bytes_grown"] == sum(len(r) for r in got) - sum(len(r) for p in (a, b) for r in sort_ref.split_stream(inflate(p))[3]) > 0
+    assert st["n_records_rewritten"] == len(_edge_records())
+
+
+def test_ties_across_inputs_come_out_in_input_order(tmp_path):
+    refs = POOL[:1]
+    paths = []
+    for k in range(3):
+        recs = [bamgen.make_record(0, 100, "4M", "ACGT", 30, name="in%d_%04d" % (k, i), flag=0x10 * (i >= 700)) for i in range(1400)]
+        paths.append(write(str(tmp_path / ("t%d.bam" % k)), refs, recs))
+    _, want = check(paths, tmp_path, with_cli=False)
+    names = [r[36:36 + r[12] - 1].decode() for r in sort_ref.split_stream(want)[3]]
+    fwd = ["in%d_%04d" % (k, i) for k in range(3) for i in range(700)]
+    assert names == fwd + ["in%d_%04d" % (k, i) for k in range(3) for i in range(700, 1400)]
+
+
+def test_batches_and_straddling_records(tmp_path, monkeypatch):
+    import sambamba_amd
+    refs = POOL[:3]
+    specs = [(refs, [("x", "s1")], [("p", "bwa", None)]), ([refs[1], POOL[3]], [("x", "s2")], [("p", "bowtie", None)]), (refs, [("x", "s3")], [("p", "bwa", None)])]
+    paths = []
+    for k, (rf, rg, pg) in enumerate(specs):
+        recs = records(2000, len(rf), 20 + k, rgs=["x"], pgs=["p"])
+        hlen = len(bamgen.bam_header(text_of(rf, rg=rg, pg=pg), rf))
+        cuts = [hlen + 3, hlen + 4, hlen + 37] + list(range(hlen + 1000, hlen + 60000, 4093))
+        paths.append(write(str(tmp_path / ("b%d.bam" % k)), rf, recs, text=text_of(rf, rg=rg, pg=pg), cuts=cuts, block_size=9000))
+    st, want = check(paths, tmp_path, with_cli=False)
+    assert st["n_batches"] == 3
+    monkeypatch.setenv("SBX_INDEX_BATCH_BYTES", "20000")
+    out = str(tmp_path / "batched.bam")
+    st2 = sambamba_amd.merge(out, paths)
+    check_file(out, want)
+    assert st2["n_batches"] >= 9 and st2["bytes_grown"] == st["bytes_grown"] > 0
+    monkeypatch.setenv("SBX_MERGE_FORCE_REWRITE", "1")
+    st3 = sambamba_amd.merge(out, paths)
+    check_file(out, want)
+    assert st3["n_records_rewritten"] == st["n_records_rewritten"]
+
+
+def test_empty_inputs(tmp_path):
+    refs = POOL[:2]
+    full = write(str(tmp_path / "f.bam"), refs, records(800, 2, 30, rgs=["x"]), text=text_of(refs, rg=[("x", "s1")]))
+    empty = write(str(tmp_path / "e.bam"), refs, [], text=text_of(refs, rg=[("x", "s2")]))
+    full2 = write(str(tmp_path / "g.bam"), refs, records(700, 2, 31, rgs=["x"]), text=text_of(refs, rg=[("x", "s3")]))
+    st, _ = check([full, empty, full2], tmp_path)
+    assert st["n_records_in"] == 1500
+    st, want = check([empty, empty, str(tmp_path / "e.bam")], tmp_path, tag="none")
+    assert st["n_records_out"] == 0 and sort_ref.split_stream(want)[3] == []
+
+
+def _keep_q30(rec):
+    return rec[13] >= 30
+
+
+def test_filter_sees_the_records_of_the_input(tmp_path):
+    refs = POOL[:2]
+    a = write(str(tmp_path / "a.bam"), refs, records(1500, 2, 40, rgs=["x"]), text=text_of(refs, rg=[("x", "s1")]))
+    b = write(str(tmp_path / "b.bam"), [refs[1], refs[0]], records(1500, 2, 41, rgs=["x"]), text=text_of([refs[1], refs[0]], rg=[("x", "s2")]))
+    st, _ = check([a, b], tmp_path, flt="mapping_quality >= 30", keep=_keep_q30)
+    assert 0 < st["n_records_out"] < st["n_records_in"] == 3000
+    # ref_id is the id in the input, not in the output: b's reference 0 is chr2
+    check([a, b], tmp_path, flt="ref_id == 0", keep=lambda r: struct.unpack_from("<i", r, 4)[0] == 0, tag="byref", with_cli=False)
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_random_differential(tmp_path, seed):
+    rng = random.Random(seed)
+    paths = []
+    for k in range(3):
+        refs = sorted(rng.sample(POOL, rng.randrange(1, 5)), key=POOL.index) if rng.random() < 0.8 else rng.sample(POOL, 3)
+        rgs = [(i, rng.choice(("s1", "s2"))) for i in rng.sample(["a", "b", "a.1", "lane"], rng.randrange(0, 4))]
+        ids = rng.sample(["bwa", "sort", "dedup", "bwa.1"], rng.randrange(0, 4))
+        pgs = [(i, rng.choice(("P", "Q")), ids[j - 1] if j and rng.random() < 0.7 else None) for j, i in enumerate(ids)]
+        recs = records(2000, len(refs), 100 * seed + k, rgs=[g[0] for g in rgs] + ["nope"], pgs=ids + ["nope"], sort=rng.random() < 0.7)
+        paths.append(write(str(tmp_path / ("r%d.bam" % k)), refs, recs, text=text_of(refs, rg=rgs, pg=pgs, co=["input %d" % k])))
+    check(paths, tmp_path, with_cli=seed == 1)
+
+
+def test_index_and_flagstat_of_the_output(tmp_path):
+    import sambamba_amd
+    refs = POOL[:3]
+    a = write(str(tmp_path / "a.bam"), refs, records(1500, 3, 50, rgs=["x"]), text=text_of(refs, rg=[("x", "s1")]))
+    b = write(str(tmp_path / "b.bam"), refs[1:], records(1500, 2, 51, rgs=["x"]), text=text_of(refs[1:], rg=[("x", "s2")]))
+    out = str(tmp_path / "o.bam")
+    sambamba_amd.merge(out, [a, b], index=True)
+    check_file(out, ref.expected([a, b]))
+    bai = str(tmp_path / "own.bai")
+    sambamba_amd.build_index(out, bai)
+    assert open(out + ".bai", "rb").read() == open(bai, "rb").read()
+    fa, fb, fo = (sambamba_amd.flagstat(p) for p in (a, b, out))
+    assert fo == {k: (fa[k][0] + fb[k][0], fa[k][1] + fb[k][1]) for k in fo} and fo["reads"][0] == 3000
+
+
+def _assert_fails(out, inputs, code, tmp_path, starts=None):
+    import sambamba_amd
+    with pytest.raises(sambamba_amd.SbxError) as ei:
+        sambamba_amd.merge(out, inputs)
+    assert ei.value.code == code, ei.value
+    if starts:
+        assert ei.value.msg.startswith(starts), ei.value.msg
+    assert not os.path.exists(str(tmp_path / "fail.bam")) and not os.path.exists(str(tmp_path / "fail.bam.bai"))
+
+
+@pytest.mark.parametrize("kind", ["size_overruns", "z_without_nul", "truncated_b", "unknown_type"])
+def test_malformed_aux_fields(tmp_path, kind):
+    """Built as data, as the CIGAR case of test_gpu_markdup.py: the record ends inside an aux field.  Run once per kind."""
+    refs = POOL[:1]
+    tail = {"size_overruns": b"XIi" + b"\1\2",                       # an i of two bytes
+            "z_without_nul": b"XZZ" + b"abc",                        # no NUL before the record ends
+            "truncated_b": b"XBBi" + struct.pack("<I", 3) + bytes(8),       # three ints stated, two there
+            "unknown_type": b"XQq" + bytes(4)}[kind]
+    good = bamgen.make_record(0, 100, "4M", "ACGT", 30, name="ok", tags=bamgen.tag_z("RG", "x"))
+    bad = bamgen.make_record(0, 200, "4M", "ACGT", 30, name="bad", tags=bamgen.tag_z("RG", "x") + tail)
+    a = write(str(tmp_path / "a.bam"), refs, [good], text=text_of(refs, rg=[("x", "s1")]))
+    b = str(tmp_path / "b.bam")
+    stream = bamgen.bam_header(text_of(refs, rg=[("x", "s2")]), refs) + good + bad + good
+    open(b, "wb").write(bamgen.bgzf_block(stream) + bamgen.EOF_BLOCK)
+    _assert_fails(str(tmp_path / "fail.bam"), [a, b], -3, tmp_path, "malformed BAM record in ")
+
+
+def test_refusals(tmp_path):
+    import sambamba_amd
+    refs = POOL[:1]
+    recs = [bamgen.make_record(0, 100, "4M", "ACGT", 30, name="r")]
+    co = write(str(tmp_path / "co.bam"), refs, recs)
+    un = write(str(tmp_path / "un.bam"), refs, recs, text=text_of(refs, so="unsorted"))
+    qn = write(str(tmp_path / "qn.bam"), refs, recs, text=text_of(refs, so="queryname"))
+    other = write(str(tmp_path / "ln.bam"), [("chr1", 5)], [])
+    out = str(tmp_path / "fail.bam")
+    _assert_fails(out, [un, co], -1, tmp_path, "file headers indicate that some files are not sorted")
+    _assert_fails(out, [co, un], -1, tmp_path, "sorting orders of files don't agree, can't merge")
+    _assert_fails(out, [qn, qn], -5, tmp_path)
+    _assert_fails(out, [co, other], -1, tmp_path, "can't merge SAM headers: one of references with name chr1 has length 100000")
+    _assert_fails(out, [co], -1, tmp_path)
+    _assert_fails(out, [co, str(tmp_path / "missing.bam")], -2, tmp_path)
+    # the output is one of two inputs that could be merged: only the guard stands between the call and the input
+    co2 = write(str(tmp_path / "co2.bam"), refs, recs)
+    before = open(co, "rb").read()
+    with pytest.raises(sambamba_amd.SbxError) as ei:
+        sambamba_amd.merge(co, [co2, co])
+    assert ei.value.code == -1 and ei.value.msg == "the output would overwrite the input " + co, ei.value.msg
+    assert open(co, "rb").read() == before and not os.path.exists(co + ".bai")
+    r = cli([out, un, co])
+    assert (r.returncode, r.stdout, r.stderr) == (1, b"", b"sbx-merge: file headers indicate that some files are not sorted\n")
+    assert not os.path.exists(out)
+
+
+def test_cli_header_only(tmp_path):
+    refs = POOL[:2]
+    a = write(str(tmp_path / "a.bam"), refs, [], text=text_of(refs, rg=[("x", "s1")]))
+    b = write(str(tmp_path / "b.bam"), refs, [], text=text_of(refs, rg=[("x", "s2")]))
+    r = cli(["-H", str(tmp_path / "never.bam"), a, b])
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.decode() == ref.merge_headers([text_of(refs, rg=[("x", "s1")]), text_of(refs, rg=[("x", "s2")])])[0]
+    assert not os.path.exists(str(tmp_path / "never.bam"))
+
+
+def test_abi_sizeof_merge_stats():
+    import sambamba_amd
+    from sambamba_amd._lib import MergeStats
+    L = sambamba_amd.lib()
+    assert L.sbx_abi_sizeof(b"sbx_merge_stats") == C.sizeof(MergeStats) == 7 * 8 + 4 * 4 + 7 * 8
