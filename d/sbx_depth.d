@@ -108,6 +108,22 @@ extern (C) nothrow @nogc {
     int sbx_merge_bam(const(char)* out_path, const(char*)* in_paths, int n_inputs, const(sbx_filter)* filter, int level, int with_index,
                       int device, sbx_merge_stats* stats, char* err, size_t errlen);
     int sbx_merge_header_text(const(char*)* texts, const(size_t)* lens, int n, char* out_, size_t cap, size_t* out_len);
+    enum SBX_VIEW_MAX_REGIONS = 1024;
+    struct sbx_view_opts {
+        ushort flags_set; ushort flags_unset; int subsample; double fraction; ulong seed;
+    }
+    struct sbx_view_stats {
+        ulong n_records_in; ulong n_records_selected; ulong n_entries_out; ulong inflated_bytes; ulong stream_bytes; ulong compressed_bytes;
+        uint n_regions; uint n_sort_passes; uint n_batches; uint reserved;
+        double ms_inflate; double ms_index; double ms_select; double ms_emit; double ms_sort; double ms_gather; double ms_deflate; double ms_total_wall;
+    }
+    int sbx_view_count(const(char)* in_path, const(sbx_filter)* filter, const(sbx_view_opts)* opts, const(char*)* regions, size_t n_regions,
+                       const(char)* bed_path, int device, ulong* count, sbx_view_stats* stats, char* err, size_t errlen);
+    int sbx_view_bam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, const(sbx_view_opts)* opts, const(char*)* regions,
+                     size_t n_regions, const(char)* bed_path, const(char)* pg_command_line, int level, int with_index, int device,
+                     sbx_view_stats* stats, char* err, size_t errlen);
+    int sbx_view_num_filter(const(char)* text, ushort* flags_set, ushort* flags_unset);
+    int sbx_view_reference_info(sbx_ctx*, char* out_, size_t cap, size_t* out_len);
     int sbx_inflate_blocks(const(ubyte)* comp, const(ulong)* comp_off, const(uint)* comp_len, const(uint)* isize,
                            uint n_blocks, ubyte* out_, const(ulong)* out_off, char* err, size_t errlen);
     sbx_ctx* sbx_open(const(char*)* bam_paths, int n_bams, int device, char* err, size_t errlen);

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -272,6 +272,62 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
  * reference's parser throws on, SBX_EINVAL when the sorting orders forbid the merge or one reference name has two lengths,
  * SBX_EUNSUPPORTED for queryname.  The message of a refusal is written to out when it fits. */
 int sbx_merge_header_text(const char* const* texts, const size_t* lens, int n, char* out, size_t cap, size_t* out_len);
+
+/* `sambamba view` (sambamba/view.d), the record selection with its two cheapest sinks: a count (-c) and a BAM (-f bam).  A record is
+ * selected when ALL of these hold (a part that was not asked for always holds):
+ *   filter       the -F program (NULL: every record, not depth's default filter);
+ *   num-filter   (flag & flags_set) == flags_set && (flag & flags_unset) == 0            (FlagBitFilter, filtering.d:176-187);
+ *   subsample    low 32 bits of the 64-bit FNV-1a over the read name (without its NUL) and the 8 bytes of `seed`, least significant
+ *                first, < (uint64)(4294967296.0 * fraction); mates share a name and so a verdict (SubsampleFilter, filtering.d:340-371);
+ *   regions      the record overlaps a region: ref_id == r && pos < end && (pos > start || pos + basesCovered > start), the
+ *                predicate of the reference's random access (randomaccessmanager.d:397-460) -- a record that covers no bases is
+ *                selected strictly inside a region and not at pos == start.
+ * Regions are given as the reference gets them: `regions` are the strings of the command line ("chr", "chr:beg-end" with a 1-based
+ * beg, and "*", which stands for the records with ref_id < 0), resolved against the header of the input; an unknown name is
+ * SBX_EINVAL and named in the message.  The output is then the concatenation, in the listed order, of each region's records in file
+ * order: a record that overlaps two listed regions appears -- and is counted -- twice.  At most SBX_VIEW_MAX_REGIONS may be listed
+ * (SBX_EINVAL beyond).  `bed_path` (NULL or "": none) names a BED file instead: its regions are sorted and merged as parseBed leaves
+ * them and every record that overlaps any of them is output once, in file order.  Both at once are SBX_EINVAL.
+ * Deliberate divergences: no .bai is needed and the input need not be sorted -- the result is defined by the predicate over all
+ * records in file order, which is what the reference yields for a sorted, indexed file -- and -L uses the same predicate whatever
+ * the header's SO says.  The whole file is read even for a small region.
+ * Milliseconds are device time (inflate = K1, index = K2, select = K12a [+ the copy into the record store and the scans of its
+ * counts for BAM output], emit = K12b, sort = K9b over the region indices + the composition, gather = output offsets + K9c,
+ * deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index. */
+#define SBX_VIEW_MAX_REGIONS 1024
+typedef struct {
+    uint16_t flags_set, flags_unset;           /* --num-filter=i1/i2 (sbx_view_num_filter); 0, 0: every record */
+    int32_t subsample;                         /* != 0: -s fraction with --subsampling-seed=seed */
+    double fraction;                           /* negative or NaN: SBX_EINVAL */
+    uint64_t seed;
+} sbx_view_opts;
+typedef struct {
+    uint64_t n_records_in, n_records_selected, n_entries_out;    /* entries: selected records, one per listed region they overlap */
+    uint64_t inflated_bytes, stream_bytes, compressed_bytes;     /* the last two: BAM output only */
+    uint32_t n_regions, n_sort_passes, n_batches, reserved;
+    double ms_inflate, ms_index, ms_select, ms_emit, ms_sort, ms_gather, ms_deflate, ms_total_wall;
+} sbx_view_stats;
+/* -c: *count = the number of entries.  Streams the file in batches like sbx_flagstat; nothing is stored, so a file larger than the
+ * device works.  opts may be NULL (no num-filter, no subsampling); stats may be NULL. */
+int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions, size_t n_regions,
+                   const char* bed_path, int device, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen);
+/* -f bam: the header text of sbx_markdup_header_text (SO kept; "@PG ID:sambamba CL:<pg_command_line> ..." added unless
+ * pg_command_line is NULL or an @PG ID:sambamba exists), the selected records byte for byte in the order defined above, the EOF
+ * block; an empty selection writes header + EOF.  out_path NULL or "-": stdout (never indexed, never removed).  level as
+ * sbx_bgzf_compress; with_index != 0: out_path + ".bai" too (the selection of a sorted input through bed_path is sorted).  The
+ * records of the file are resident on the device as for sbx_sort_bam: one whose inflated records do not fit is refused with
+ * SBX_ENOMEM, more than 2^32 output entries with SBX_EUNSUPPORTED, an out_path that is the input with SBX_EINVAL.  On failure no
+ * output file is left behind. */
+int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
+                 size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device,
+                 sbx_view_stats* stats, char* err, size_t errlen);
+/* "i1/i2" of --num-filter (view.d:271-277; host only): either number may be missing ("4/", "/4", "3", ""), each is an unsigned
+ * 16-bit decimal; anything else is SBX_EINVAL. */
+int sbx_view_num_filter(const char* text, uint16_t* flags_set, uint16_t* flags_unset);
+/* The text of `view -I` for an open file (outputReferenceInfoJson, view.d:98-118; host only), exactly as the reference's code
+ * prints it -- the quote in front of the brace included: [{"name":"chr1","length":1000}] is what a correct writer would print,
+ * ["{name":"chr1","length":1000}] plus a newline is what comes out.  Lengths as sbx_sort_header_text. */
+int sbx_view_reference_info(sbx_ctx*, char* out, size_t cap, size_t* out_len);
 
 /* ---- engine seam ------------------------------------------------------------ */
 

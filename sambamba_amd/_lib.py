@@ -11,6 +11,7 @@ _FLAGSTAT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-flagstat")
 _SORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sort")
 _MARKDUP_CLI_PATH = os.path.join(HERE, "csrc", "sbx-markdup")
 _MERGE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-merge")
+_VIEW_CLI_PATH = os.path.join(HERE, "csrc", "sbx-view")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -102,6 +103,14 @@ class MergeStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_inputs", "key_bits", "n_sort_passes", "n_batches")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_rewrite", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
 
+class ViewOpts(C.Structure):
+    _fields_ = [("flags_set", C.c_uint16), ("flags_unset", C.c_uint16), ("subsample", C.c_int32), ("fraction", C.c_double), ("seed", C.c_uint64)]
+
+class ViewStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_records_in", "n_records_selected", "n_entries_out", "inflated_bytes", "stream_bytes", "compressed_bytes")] +
+                [(k, C.c_uint32) for k in ("n_regions", "n_sort_passes", "n_batches", "reserved")] +
+                [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_select", "ms_emit", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
+
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
 
 EXPORTS = [
@@ -113,6 +122,7 @@ EXPORTS = [
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
     "sbx_sort_bam", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
+    "sbx_view_count", "sbx_view_bam", "sbx_view_num_filter", "sbx_view_reference_info",
 ]
 
 _lib = None
@@ -140,6 +150,10 @@ def markdup_cli_path():
 
 def merge_cli_path():
     return _MERGE_CLI_PATH
+
+
+def view_cli_path():
+    return _VIEW_CLI_PATH
 
 
 def lib():
@@ -205,6 +219,12 @@ def lib():
     L.sbx_merge_bam.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.POINTER(MergeStats),
                                 C.c_char_p, C.c_size_t]
     L.sbx_merge_header_text.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sbx_view_count.argtypes = [C.c_char_p, C.POINTER(Filter), C.POINTER(ViewOpts), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_int,
+                                 C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
+    L.sbx_view_bam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.POINTER(ViewOpts), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_char_p,
+                               C.c_int, C.c_int, C.c_int, C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
+    L.sbx_view_num_filter.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
+    L.sbx_view_reference_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_depth_base_tile_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -220,7 +240,8 @@ def lib():
     for name, ty in (("sbx_region", Region), ("sbx_header_info", HeaderInfo), ("sbx_region_stats", RegionStats),
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
-                     ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats)):
+                     ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats),
+                     ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -612,3 +633,70 @@ def merge_header_text(texts):
         raise SbxError(rc if rc != 0 else first, buf.raw[:n.value].decode())
     out = buf.raw[:n.value]
     return out if not texts or isinstance(texts[0], bytes) else out.decode()
+
+
+def view_num_filter(text):
+    """sbx_view_num_filter: "i1/i2" of `view --num-filter` -> (flags_set, flags_unset), host only; SbxError(-1) for anything else."""
+    L = lib()
+    a, b = C.c_uint16(0), C.c_uint16(0)
+    rc = L.sbx_view_num_filter(text.encode(), C.byref(a), C.byref(b))
+    if rc != 0:
+        raise SbxError(rc, "invalid num-filter %r" % text)
+    return a.value, b.value
+
+
+def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, regions=(), bed=None, subsample=None, seed=None, level=-1,
+         index=False, command_line=None, device=-1):
+    """sbx_view_count / sbx_view_bam (`sambamba view -c` / `-f bam`): the records of in_path that pass the -F query string `filter`,
+    `num_filter` ("i1/i2"), the subsampling (`subsample` = fraction, `seed` = 64-bit seed, drawn at random when None) and overlap
+    `regions` ("chr", "chr:beg-end", "*": once per listed region, in listed order) or the BED file `bed` (once, in file order).
+    count=True returns their number; otherwise they are written to out_path ("-": stdout) as a BAM -- index=True also writes
+    out_path + ".bai", command_line is the CL field of the @PG line that is added (None: no @PG) -- and the fields of sbx_view_stats
+    come back as a dict."""
+    L = lib()
+    f = compile_filter(filter) if filter else None
+    o = ViewOpts()
+    if num_filter is not None:
+        o.flags_set, o.flags_unset = view_num_filter(num_filter)
+    if subsample is not None:
+        o.subsample, o.fraction = 1, float(subsample)
+        o.seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed)
+    regions = [regions] if isinstance(regions, str) else list(regions)
+    arr = (C.c_char_p * max(1, len(regions)))(*[r.encode() for r in regions])
+    st = ViewStats()
+    err = C.create_string_buffer(512)
+    fp = C.byref(f) if f is not None else None
+    bedp = bed.encode() if bed else None
+    if count:
+        n = C.c_uint64(0)
+        rc = L.sbx_view_count(in_path.encode(), fp, C.byref(o), arr, len(regions), bedp, device, C.byref(n), C.byref(st), err, 512)
+        if rc != 0:
+            raise SbxError(rc, err.value.decode())
+        return int(n.value)
+    if out_path is None:
+        raise ValueError("view: out_path is required unless count=True ('-' writes to stdout)")
+    rc = L.sbx_view_bam(in_path.encode(), out_path.encode(), fp, C.byref(o), arr, len(regions), bedp,
+                        command_line.encode() if command_line is not None else None, int(level), int(index), device, C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: getattr(st, k) for k, _ in ViewStats._fields_ if k != "reserved"}
+
+
+def view_reference_info(path, device=-1):
+    """sbx_view_reference_info: the text `sambamba view -I` prints for the BAM at `path`."""
+    L = lib()
+    err = C.create_string_buffer(512)
+    paths = (C.c_char_p * 1)(path.encode())
+    ctx = L.sbx_open(paths, 1, device, err, 512)
+    if not ctx:
+        raise SbxError(-2, err.value.decode())
+    try:
+        n = C.c_size_t(0)
+        L.sbx_view_reference_info(ctx, None, 0, C.byref(n))
+        buf = C.create_string_buffer(n.value + 1)
+        rc = L.sbx_view_reference_info(ctx, buf, n.value + 1, C.byref(n))
+        if rc != 0:
+            raise SbxError(rc, "sbx_view_reference_info failed")
+        return buf.raw[:n.value].decode()
+    finally:
+        L.sbx_close(ctx)

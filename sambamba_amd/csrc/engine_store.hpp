@@ -1,8 +1,9 @@
-// engine_store.hpp -- what sbx_sort_bam, sbx_markdup and sbx_merge_bam share around their kernels: the plan of the resident record store (1 x the
+// engine_store.hpp -- what sbx_sort_bam, sbx_markdup, sbx_merge_bam and sbx_view_bam share around their kernels: the plan of the resident record store (1 x the
 // inflated records of the file next to one batch of the read pass), the copy of a batch into it, K9b over the keys of the resident
 // records (sort and merge), and the writer that turns
 // "header + records of the store in the order of a permutation" into a BGZF file piece by piece (offsets, piece bounds, K9c gather,
-// deflate).  The stream written never exists as a whole.
+// deflate).  The permutation is a list of record numbers: it may leave records out (a filter) or name one several times (sbx_view_bam
+// with listed regions).  The stream written never exists as a whole.
 #pragma once
 #include <sys/stat.h>
 #include <unistd.h>
