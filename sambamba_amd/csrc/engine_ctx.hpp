@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "entry_util.hpp"
 #include "host_io.hpp"
 #include "host_res.hpp"
 #include "kernels.hpp"
@@ -284,6 +285,74 @@ inline HostResults& results(sbx_ctx* c) {
 // SBX_E* code of the last sbx_open of this thread that failed (sbx_open itself returns null and a message; the standalone entry
 // points built on it -- sbx_flagstat -- return the code)
 extern thread_local int t_open_code;
+
+// ---- the standalone entry points: one call opens a file, passes over it and closes it (sbx_flagstat, sbx_build_index and the
+// commands of engine_store.hpp) ----
+
+// Runs the body of an entry point; an Error or std::exception that leaves it becomes the returned code and the text in err.  What
+// the body owns -- a Standalone context, an OutputGuard, device buffers -- is cleaned up while the exception unwinds it.
+template <class F>
+int run_entry(char* err, size_t errlen, F&& body) {
+    try {
+        body();
+        return SBX_OK;
+    } catch (const Error& e) {
+        set_err(err, errlen, e.what());
+        return e.code;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return SBX_EINVAL;
+    }
+}
+
+// the context of one entry point: closed when it leaves scope, or early by reset() (the batch buffers of a read pass make room)
+struct Standalone {
+    sbx_ctx* c = nullptr;
+    Standalone() = default;
+    explicit Standalone(sbx_ctx* p) : c(p) {}
+    Standalone(Standalone&& o) noexcept : c(o.c) { o.c = nullptr; }
+    Standalone& operator=(Standalone&& o) noexcept { reset(); c = o.c; o.c = nullptr; return *this; }
+    ~Standalone() { reset(); }
+    void reset() { if (c) sbx_close(c); c = nullptr; }
+    sbx_ctx* operator->() const { return c; }
+    sbx_ctx* get() const { return c; }
+};
+
+inline bool has_ops(const sbx_filter* filter) { return filter && filter->n_ops > 0; }
+
+// one file, opened; a failure carries the SBX_E* code of the open
+inline Standalone open_standalone(const char* path, int device) {
+    const char* one[1] = {path};
+    char e2[512] = {0};
+    Standalone c(sbx_open(one, 1, device, e2, sizeof e2));
+    if (!c.get()) throw Error(t_open_code != SBX_OK ? t_open_code : SBX_EIO, e2);
+    return c;
+}
+
+// ... and set up for an index-mode pass (for_each_record_batch): every record is described; no sort order, index or read group is
+// required.  filter (optional; an empty one counts as none): the -F program K2 runs, not depth's default filter.
+// verdict_on_every_record: K2 leaves the filter's verdict in RecDesc::pad of every record (an empty filter admits all of them).
+inline Standalone open_record_pass(const char* path, int device, const sbx_filter* filter, bool verdict_on_every_record) {
+    Standalone c = open_standalone(path, device);
+    c->index_mode = true;
+    memset(&c->filter, 0, sizeof c->filter);
+    if (has_ops(filter)) c->filter = *filter;
+    c->filter_every = verdict_on_every_record;
+    c->mode = SBX_MODE_BASE;
+    c->fix_mate = false;
+    return c;
+}
+
+// ---- argument checks with one wording ----
+inline void check_level(int level) {
+    if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
+}
+inline void check_filter(const sbx_filter* filter) {
+    if (filter && (filter->n_ops < 0 || filter->n_ops > SBX_FILTER_MAX_OPS)) throw Error(SBX_EINVAL, "malformed filter");
+}
+inline void refuse_overwrite(const char* in_path, const char* out_path) {
+    if (same_file(in_path, out_path)) throw Error(SBX_EINVAL, std::string("the output would overwrite the input ") + in_path);
+}
 
 // engine_worklist.cpp
 std::vector<sbx_region> sorted_regions(const std::vector<sbx_region>& sel);

@@ -54,14 +54,6 @@ uint64_t compact(MdPred pred, const uint8_t* d_c, const uint32_t* d_mate, uint64
     return total;
 }
 
-int copy_text(const std::string& t, char* out, size_t cap, size_t* out_len) {
-    if (out_len) *out_len = t.size();
-    if (!out || t.size() + 1 > cap) return SBX_ENOMEM;
-    memcpy(out, t.data(), t.size());
-    out[t.size()] = 0;
-    return SBX_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -70,32 +62,18 @@ int sbx_markdup_header_text(const char* text, size_t n, const char* pg_command_l
     if (!text && n) return SBX_EINVAL;
     std::string t;
     if (!mdc::markdup_header_text(text ? text : "", n, pg_command_line, &t, nullptr)) return SBX_EFORMAT;
-    return copy_text(t, out, cap, out_len);
+    return copy_to_caller(t, out, cap, out_len);
 }
 
 int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates, int level, const char* pg_command_line, int device,
                 sbx_markdup_stats* stats, char* err, size_t errlen) {
-    sbx_ctx* c = nullptr;
-    bool out_created = false;
-    auto fail = [&](int code, const std::string& m) {
-        set_err(err, errlen, m);
-        if (c) sbx_close(c);
-        if (out_created) unlink(out_path);
-        return code;
-    };
-    try {
+    return run_entry(err, errlen, [&] {
         if (!in_path || !out_path) throw Error(SBX_EINVAL, "null argument");
-        if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
-        if (same_file(in_path, out_path)) throw Error(SBX_EINVAL, std::string("the output would overwrite the input ") + in_path);
+        check_level(level);
+        refuse_overwrite(in_path, out_path);
         const double w0 = wall_now();
-        const char* one[1] = {in_path};
-        char e2[512] = {0};
-        c = sbx_open(one, 1, device, e2, sizeof e2);
-        if (!c) throw Error(t_open_code != SBX_OK ? t_open_code : SBX_EIO, e2);
-        c->index_mode = true;                            // every record is described; no sort order, index or read group is required
-        memset(&c->filter, 0, sizeof c->filter);
-        c->mode = SBX_MODE_BASE;
-        c->fix_mate = false;
+        Standalone c = open_record_pass(in_path, device, nullptr, false);
+        OutputGuard out_file(out_path);
         const int32_t n_ref = (int32_t)c->hdr.refs.size();
         std::string text, why;
         if (!mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why)) throw Error(SBX_EFORMAT, "SAM header: " + why);
@@ -119,7 +97,7 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
             if (b < 64) hash_mask = (1ull << b) - 1ull;
         }
 
-        const StorePlan plan = plan_record_store(c, hlen, 96, "marking the duplicates of");
+        const StorePlan plan = plan_record_store(c.get(), hlen, 96, "marking the duplicates of");
         const uint64_t u_first = plan.u_first;
         hipStream_t s = c->stream.get();
         DevBuf<uint8_t> d_store((size_t)plan.store_bytes + 64);
@@ -146,7 +124,7 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
         uint32_t n_batches = 0;
         bool too_many = false;
         unsigned long long acc[kMdAccWords] = {0};
-        for_each_record_batch(c, plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        for_each_record_batch(c.get(), plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
             if (n + nrec > 0xFFFFFFF0ull) { too_many = true; return false; }
             const size_t want = (size_t)(n + nrec + 2);
             grow_keeping(d_off, (size_t)n, want, s);
@@ -157,7 +135,7 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
             grow_keeping(d_rg_at, (size_t)n, want, s);
             grow_keeping(d_cls, (size_t)n, want, s);
             t_k.start(s);
-            copy_batch_to_store(c, d_store.p, u_first, cur, base, next, s);
+            copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
             MdEndsArgs a{};
             a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base;
             a.n_ref = n_ref; a.ref_bits = ref_bits; a.hash_mask = hash_mask;
@@ -177,12 +155,9 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
             return acc[kMdAccBad] == 0;
         });
         if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-        if (acc[kMdAccBad])
-            throw Error(SBX_EFORMAT, "malformed BAM record (" + std::to_string(acc[kMdAccBad]) + " records whose reference id is out of range or "
-                                     "whose lengths are inconsistent)");
+        if (acc[kMdAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kMdAccBad]));
         const uint64_t u_total = plan.u_total;
-        sbx_close(c);                                    // the batch buffers make room for the sorts and the output pieces
-        c = nullptr;
+        c.reset();                                       // the batch buffers make room for the sorts and the output pieces
         const double w2 = wall_now();
 
         // ---- K10b: pairing ----
@@ -250,18 +225,15 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
 
         // ---- the output ----
         DevBuf<uint64_t> d_out_off((size_t)n_out + 2);
-        const OutputPlan out = plan_output(d_len.p, d_perm.p, n_out, hlen, d_out_off.p, s, &st.ms_gather);
-        if (!remove_duplicates && out.total != hlen + acc[kMdAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the records do not add up");
-        d_len.release();
-        const double w3 = wall_now();
-        BgzfPieceTimes bt_times;
-        write_permuted_bam(out_path, header, out, d_store.p, d_off.p, d_perm.p, d_out_off.p, n_out, level, &out_created, &st.ms_gather, &bt_times);
-        const double w4 = wall_now();
+        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, d_perm.p, n_out, d_out_off.p, level,
+                                                remove_duplicates ? nullptr : &acc[kMdAccBytes], "records", s, &st.ms_gather);
+        out_file.disarm();
+        const double w3 = w.w_planned, w4 = wall_now();
         st.n_records_in = n; st.n_records_out = n_out;
         st.n_end_pairs = n_pairs; st.n_single_ends = n_single; st.n_unmatched_pairs = acc[kMdAccUnmatched]; st.n_duplicates = acc[kMdAccDup];
-        st.inflated_bytes = u_total; st.stream_bytes = out.total; st.compressed_bytes = bt_times.out_bytes + 28;
+        st.inflated_bytes = u_total; st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
         st.n_sort_passes = n_passes; st.n_batches = n_batches;
-        st.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+        st.ms_deflate = w.ms_deflate;
         st.ms_total_wall = (w4 - w0) * 1e3;
         if (getenv("SBX_TIMING"))
             fprintf(stderr, "[sbx] markdup: n_records_in=%llu n_records_out=%llu n_end_pairs=%llu n_single_ends=%llu n_unmatched_pairs=%llu "
@@ -274,12 +246,7 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
                     st.n_sort_passes, st.n_batches, st.ms_inflate, st.ms_index, st.ms_ends, st.ms_pairing, st.ms_groups, st.ms_gather, st.ms_deflate,
                     st.ms_total_wall, (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
         if (stats) *stats = st;
-    } catch (const Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return fail(SBX_EINVAL, e.what());
-    }
-    return SBX_OK;
+    });
 }
 
 }  // extern "C"

@@ -65,14 +65,6 @@ void add_renames(const mergec::IdMap& m, uint32_t kind, MergeInput* in) {
     in->grow_per_record += most;     // (a record has at most one patch of a kind)
 }
 
-int copy_out(const std::string& t, char* out, size_t cap, size_t* out_len, int code) {
-    if (out_len) *out_len = t.size();
-    if (!out || t.size() + 1 > cap) return code != SBX_OK ? code : SBX_ENOMEM;
-    memcpy(out, t.data(), t.size());
-    out[t.size()] = 0;
-    return code;
-}
-
 }  // namespace
 
 extern "C" {
@@ -88,55 +80,41 @@ int sbx_merge_header_text(const char* const* texts, const size_t* lens, int n, c
     std::string why;
     try {
         const int rc = mergec::merge_headers(t, &m, &why);
-        return copy_out(rc == SBX_OK ? m.text : why, out, cap, out_len, rc);
+        return copy_to_caller(rc == SBX_OK ? m.text : why, out, cap, out_len, rc);
     } catch (const std::exception& e) {
-        return copy_out(e.what(), out, cap, out_len, SBX_EINVAL);
+        return copy_to_caller(e.what(), out, cap, out_len, SBX_EINVAL);
     }
 }
 
 int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_inputs, const sbx_filter* filter, int level, int with_index,
                   int device, sbx_merge_stats* stats, char* err, size_t errlen) {
-    sbx_ctx* c = nullptr;
-    bool out_created = false;
-    auto fail = [&](int code, const std::string& m) {
-        set_err(err, errlen, m);
-        if (c) sbx_close(c);
-        if (out_created) unlink(out_path);
-        return code;
-    };
-    try {
+    const int rc = run_entry(err, errlen, [&] {
         if (!out_path || !in_paths) throw Error(SBX_EINVAL, "null argument");
         if (n_inputs < 2) throw Error(SBX_EINVAL, "merging needs at least two input files");
         if (n_inputs > SBX_MERGE_MAX_INPUTS) throw Error(SBX_EINVAL, "more than " + std::to_string(SBX_MERGE_MAX_INPUTS) + " input files");
-        if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
-        if (filter && (filter->n_ops < 0 || filter->n_ops > SBX_FILTER_MAX_OPS)) throw Error(SBX_EINVAL, "malformed filter");
+        check_level(level);
+        check_filter(filter);
         for (int k = 0; k < n_inputs; ++k) {
             if (!in_paths[k]) throw Error(SBX_EINVAL, "null argument");
-            if (same_file(in_paths[k], out_path)) throw Error(SBX_EINVAL, std::string("the output would overwrite the input ") + in_paths[k]);
+            refuse_overwrite(in_paths[k], out_path);
         }
         const double w0 = wall_now();
         const size_t n_in_files = (size_t)n_inputs;
-        auto open_input = [&](size_t k) {
-            const char* one[1] = {in_paths[k]};
-            char e2[512] = {0};
-            c = sbx_open(one, 1, device, e2, sizeof e2);
-            if (!c) throw Error(t_open_code != SBX_OK ? t_open_code : SBX_EIO, e2);
-        };
+        const bool use_filter = has_ops(filter);
+        OutputGuard out_file(out_path);
 
         // ---- headers and sizes ----
         std::vector<MergeInput> in(n_in_files);
         std::vector<std::string> texts;
         uint64_t u_sum = 0;
         for (size_t k = 0; k < n_in_files; ++k) {
-            open_input(k);
+            Standalone c = open_standalone(in_paths[k], device);
             in[k].text = text_with_sq_lines(c->hdr, in_paths[k]);
             in[k].u_total = c->blocks.out_off.back();
             in[k].u_first = std::min<uint64_t>(c->hdr.first_record_off, in[k].u_total);
             in[k].n_ref = (int32_t)c->hdr.refs.size();
             u_sum += in[k].u_total;
             texts.push_back(in[k].text);
-            sbx_close(c);
-            c = nullptr;
         }
         mergec::MergedHeader mh;
         {
@@ -182,13 +160,7 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
         uint32_t n_batches = 0;
         bool too_many = false, store_full = false;
         for (size_t k = 0; k < n_in_files; ++k) {
-            open_input(k);
-            c->index_mode = true;                            // every record is described; no sort order, index or read group is required
-            memset(&c->filter, 0, sizeof c->filter);
-            if (filter && filter->n_ops > 0) { c->filter = *filter; c->filter_every = true; }
-            c->mode = SBX_MODE_BASE;
-            c->fix_mate = false;
-            const bool use_filter = c->filter_every;
+            Standalone c = open_record_pass(in_paths[k], device, filter, use_filter);
             const bool fast = in[k].identity && !force_rewrite;
             hipStream_t s = c->stream.get();
             DevBuf<int32_t> d_ref_map(mh.maps[k].ref.size() + 1);
@@ -203,7 +175,7 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
             }
             uint64_t cur = in[k].u_first;
             uint32_t nb = 0;
-            for_each_record_batch(c, plan.batch_u, &nb, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+            for_each_record_batch(c.get(), plan.batch_u, &nb, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
                 if (n_kept + nrec > 0xFFFFFFF0ull) { too_many = true; return false; }
                 const size_t want = (size_t)(n_kept + nrec + 2);
                 grow_keeping(d_key, (size_t)n_kept, want, s);
@@ -262,15 +234,12 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
                 return acc[kSortAccBad] == 0;
             });
             n_batches += nb;
-            sbx_close(c);                                // the batch buffers make room for the next input, the sort and the output pieces
-            c = nullptr;
+            c.reset();                                   // the batch buffers make room for the next input, the sort and the output pieces
             if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
             if (store_full) throw Error(SBX_ENOMEM, std::string("the record store is full at input ") + in_paths[k]);
-            if (acc[kSortAccBad])
-                throw Error(SBX_EFORMAT, std::string("malformed BAM record in ") + in_paths[k] + " (" + std::to_string(acc[kSortAccBad]) +
-                                         " records whose reference id is out of range or whose lengths are inconsistent)");
+            if (acc[kSortAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSortAccBad], in_paths[k]));
         }
-        if (!(filter && filter->n_ops > 0) && n_kept != n_in)
+        if (!use_filter && n_kept != n_in)
             throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(n_in) + " records received a key");
         const uint64_t n = n_kept;
         b_new_len.release(); b_keep.release(); b_key.release(); b_patch_at.release(); b_patch_entry.release();
@@ -283,27 +252,21 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
         hipStream_t s = stream.get();
         ResidentOrder order;
         sort_resident(d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
-        const uint32_t* d_perm = order.perm;
-        const uint32_t key_bits = order.key_bits, n_passes = order.n_passes;
         // the keys are done with: one of their buffers holds the output offsets
-        uint64_t* d_out_off = order.key2.p;
         d_key.release();
-        const OutputPlan out = plan_output(d_len.p, d_perm, n, hlen, d_out_off, s, &st.ms_gather);
         st.ms_sort = order.ms_sort;
-        if (out.total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the merged records do not add up");
-        d_len.release();
-        const double w3 = wall_now();
 
-        // ---- K9c + deflate, piece by piece ----
-        BgzfPieceTimes bt_times;
-        write_permuted_bam(out_path, header, out, d_store.p, d_off.p, d_perm, d_out_off, n, level, &out_created, &st.ms_gather, &bt_times);
-        const double w4 = wall_now();
+        // ---- offsets, K9c + deflate, piece by piece ----
+        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, order.perm, n, order.key2.p, level,
+                                                &acc[kSortAccBytes], "merged records", s, &st.ms_gather);
+        out_file.disarm();
+        const double w3 = w.w_planned, w4 = wall_now();
         st.n_records_in = n_in; st.n_records_out = n;
         st.n_records_rewritten = acc[kMergeAccRewritten];
         st.bytes_grown = (int64_t)k11_new_bytes - (int64_t)acc[kMergeAccOldBytes];
-        st.inflated_bytes = u_sum; st.merged_stream_bytes = out.total; st.compressed_bytes = bt_times.out_bytes + 28;
-        st.n_inputs = (uint32_t)n_in_files; st.key_bits = key_bits; st.n_sort_passes = n_passes; st.n_batches = n_batches;
-        st.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+        st.inflated_bytes = u_sum; st.merged_stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
+        st.n_inputs = (uint32_t)n_in_files; st.key_bits = order.key_bits; st.n_sort_passes = order.n_passes; st.n_batches = n_batches;
+        st.ms_deflate = w.ms_deflate;
         st.ms_total_wall = (w4 - w0) * 1e3;
         if (getenv("SBX_TIMING"))
             fprintf(stderr, "[sbx] merge: n_inputs=%u n_records_in=%llu n_records_out=%llu n_records_rewritten=%llu bytes_grown=%lld "
@@ -316,16 +279,9 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
                     st.ms_inflate, st.ms_index, st.ms_rewrite, st.ms_sort, st.ms_gather, st.ms_deflate, st.ms_total_wall, (w1 - w0) * 1e3,
                     (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
         if (stats) *stats = st;
-    } catch (const Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return fail(SBX_EINVAL, e.what());
-    }
-    if (with_index) {
-        const int rc = sbx_build_index(out_path, (std::string(out_path) + ".bai").c_str(), device, err, errlen);
-        if (rc != SBX_OK) return rc;          // (the index is a pass of its own and not part of the merge's figures)
-    }
-    return SBX_OK;
+    });
+    // (the index is a pass of its own and not part of the merge's figures)
+    return rc != SBX_OK ? rc : index_written_bam(out_path, with_index, device, err, errlen);
 }
 
 }  // extern "C"

@@ -7,7 +7,8 @@
 // -- header bytes from the host, records gathered by K9c -- is produced in pieces of whole BGZF payloads that go straight into the
 // deflate kernels (bgzf_compress_pieces) and, through pinned memory, to the file.  The sorted stream never exists as a whole.
 //
-// The plan of the store, the copy into it and the writer are engine_store.hpp, shared with sbx_markdup.
+// The scaffold of the entry point, the plan of the store, the copy into it and the output tail are engine_store.hpp, shared with
+// sbx_markdup, sbx_merge_bam and sbx_view_bam.
 // What does not fit the device next to one batch of the read pass is refused with SBX_ENOMEM (an out-of-core merge is not built).
 #include "engine_store.hpp"
 #include "sort_core.hpp"
@@ -18,46 +19,27 @@ int sbx_sort_header_text(const char* text, size_t n, char* out, size_t cap, size
     if (!text && n) return SBX_EINVAL;
     std::string t;
     if (!sortc::sort_header_text(text ? text : "", n, &t, nullptr)) return SBX_EFORMAT;
-    if (out_len) *out_len = t.size();
-    if (!out || t.size() + 1 > cap) return SBX_ENOMEM;
-    memcpy(out, t.data(), t.size());
-    out[t.size()] = 0;
-    return SBX_OK;
+    return copy_to_caller(t, out, cap, out_len);
 }
 
 int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* filter, int level, int with_index, int device,
                  sbx_sort_stats* stats, char* err, size_t errlen) {
-    sbx_ctx* c = nullptr;
-    bool out_created = false;
-    auto fail = [&](int code, const std::string& m) {
-        set_err(err, errlen, m);
-        if (c) sbx_close(c);
-        if (out_created) unlink(out_path);
-        return code;
-    };
-    try {
+    const int rc = run_entry(err, errlen, [&] {
         if (!in_path || !out_path) throw Error(SBX_EINVAL, "null argument");
-        if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
-        if (filter && (filter->n_ops < 0 || filter->n_ops > SBX_FILTER_MAX_OPS)) throw Error(SBX_EINVAL, "malformed filter");
-        if (same_file(in_path, out_path)) throw Error(SBX_EINVAL, std::string("the output would overwrite the input ") + in_path);
+        check_level(level);
+        check_filter(filter);
+        refuse_overwrite(in_path, out_path);
         const double w0 = wall_now();
-        const char* one[1] = {in_path};
-        char e2[512] = {0};
-        c = sbx_open(one, 1, device, e2, sizeof e2);
-        if (!c) throw Error(t_open_code != SBX_OK ? t_open_code : SBX_EIO, e2);
-        c->index_mode = true;                            // every record is described; no sort order, index or read group is required
-        memset(&c->filter, 0, sizeof c->filter);
-        if (filter && filter->n_ops > 0) { c->filter = *filter; c->filter_every = true; }
-        c->mode = SBX_MODE_BASE;
-        c->fix_mate = false;
-        const bool use_filter = c->filter_every;
+        const bool use_filter = has_ops(filter);
+        Standalone c = open_record_pass(in_path, device, filter, use_filter);
+        OutputGuard out_file(out_path);
         const int32_t n_ref = (int32_t)c->hdr.refs.size();
         std::string text, why;
         if (!sortc::sort_header_text(c->hdr.text.data(), c->hdr.text.size(), &text, &why)) throw Error(SBX_EFORMAT, "SAM header: " + why);
         const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
         const uint64_t hlen = header.size();
 
-        const StorePlan plan = plan_record_store(c, hlen, 48, "sorting");
+        const StorePlan plan = plan_record_store(c.get(), hlen, 48, "sorting");
         const uint64_t u_total = plan.u_total, u_first = plan.u_first, store_bytes = plan.store_bytes, batch_u = plan.batch_u;
         hipStream_t s = c->stream.get();
         DevBuf<uint8_t> d_store((size_t)store_bytes + 64);
@@ -78,14 +60,14 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         uint64_t n_in = 0, n_kept = 0, cur = u_first;
         uint32_t n_batches = 0;
         unsigned long long acc[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
-        for_each_record_batch(c, batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        for_each_record_batch(c.get(), batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
             const size_t want = (size_t)(n_kept + nrec + 2);
             grow_keeping(d_key, (size_t)n_kept, want, s);
             grow_keeping(d_off, (size_t)n_kept, want, s);
             grow_keeping(d_len, (size_t)n_kept, want, s);
             if (use_filter) { d_group_count.ensure(sort_keys_groups(nrec) + 4); d_group_base.ensure(sort_keys_groups(nrec) + 4); }
             t_k.start(s);
-            copy_batch_to_store(c, d_store.p, u_first, cur, base, next, s);
+            copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
             SortKeysArgs a{};
             a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
             a.n_ref = n_ref; a.key_n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
@@ -103,15 +85,12 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
             cur = next;
             return acc[kSortAccBad] == 0;
         });
-        if (acc[kSortAccBad])
-            throw Error(SBX_EFORMAT, "malformed BAM record (" + std::to_string(acc[kSortAccBad]) + " records whose reference id is out of range or "
-                                     "whose lengths are inconsistent)");
+        if (acc[kSortAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSortAccBad]));
         if (!use_filter && n_kept != n_in)
             throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(n_in) + " records received a key");
         if (n_kept > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
         const uint64_t n = n_kept;
-        sbx_close(c);                                    // the batch buffers make room for the sort and the output pieces
-        c = nullptr;
+        c.reset();                                       // the batch buffers make room for the sort and the output pieces
         const double w2 = wall_now();
 
         // ---- K9b ----
@@ -120,26 +99,19 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         s = stream.get();
         ResidentOrder order;
         sort_resident(d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
-        const uint32_t* d_perm = order.perm;
-        const uint32_t key_bits = order.key_bits, n_passes = order.n_passes;
         // the keys are done with: one of their buffers holds the output offsets
-        uint64_t* d_out_off = order.key2.p;
         d_key.release();
-        const OutputPlan out = plan_output(d_len.p, d_perm, n, hlen, d_out_off, s, &st.ms_gather);
-        const uint64_t total = out.total;
         st.ms_sort = order.ms_sort;
-        if (total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the sorted records do not add up");
-        d_len.release();
-        const double w3 = wall_now();
 
-        // ---- K9c + deflate, piece by piece ----
-        BgzfPieceTimes bt_times;
-        write_permuted_bam(out_path, header, out, d_store.p, d_off.p, d_perm, d_out_off, n, level, &out_created, &st.ms_gather, &bt_times);
-        const double w4 = wall_now();
+        // ---- offsets, K9c + deflate, piece by piece ----
+        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, order.perm, n, order.key2.p, level,
+                                                &acc[kSortAccBytes], "sorted records", s, &st.ms_gather);
+        out_file.disarm();
+        const double w3 = w.w_planned, w4 = wall_now();
         st.n_records_in = n_in; st.n_records_out = n;
-        st.inflated_bytes = u_total; st.sorted_stream_bytes = total; st.compressed_bytes = bt_times.out_bytes + 28;
-        st.key_bits = key_bits; st.n_sort_passes = n_passes; st.n_batches = n_batches;
-        st.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+        st.inflated_bytes = u_total; st.sorted_stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
+        st.key_bits = order.key_bits; st.n_sort_passes = order.n_passes; st.n_batches = n_batches;
+        st.ms_deflate = w.ms_deflate;
         st.ms_total_wall = (w4 - w0) * 1e3;
         if (getenv("SBX_TIMING"))
             fprintf(stderr, "[sbx] sort: n_records_in=%llu n_records_out=%llu inflated_bytes=%llu sorted_stream_bytes=%llu compressed_bytes=%llu "
@@ -150,16 +122,9 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
                     st.ms_inflate, st.ms_index, st.ms_keys, st.ms_sort, st.ms_gather, st.ms_deflate, st.ms_total_wall, (w1 - w0) * 1e3,
                     (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
         if (stats) *stats = st;
-    } catch (const Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return fail(SBX_EINVAL, e.what());
-    }
-    if (with_index) {
-        const int rc = sbx_build_index(out_path, (std::string(out_path) + ".bai").c_str(), device, err, errlen);
-        if (rc != SBX_OK) return rc;          // (the index is a pass of its own and not part of the sort's figures)
-    }
-    return SBX_OK;
+    });
+    // (the index is a pass of its own and not part of the sort's figures)
+    return rc != SBX_OK ? rc : index_written_bam(out_path, with_index, device, err, errlen);
 }
 
 }  // extern "C"

@@ -1,13 +1,12 @@
-// engine_store.hpp -- what sbx_sort_bam, sbx_markdup, sbx_merge_bam and sbx_view_bam share around their kernels: the plan of the resident record store (1 x the
-// inflated records of the file next to one batch of the read pass), the copy of a batch into it, K9b over the keys of the resident
-// records (sort and merge), and the writer that turns
-// "header + records of the store in the order of a permutation" into a BGZF file piece by piece (offsets, piece bounds, K9c gather,
-// deflate).  The permutation is a list of record numbers: it may leave records out (a filter) or name one several times (sbx_view_bam
-// with listed regions).  The stream written never exists as a whole.
+// engine_store.hpp -- what sbx_sort_bam, sbx_markdup, sbx_merge_bam and sbx_view_bam share around their kernels.  Each of them reads as:
+// checks, open (run_entry / open_record_pass / OutputGuard, engine_ctx.hpp), header, plan, its own read-pass lambda with its own
+// kernel, order, output tail, stats line.  Here: the plan of the resident record store (1 x the inflated records of the file next to
+// one batch of the read pass), the copy of a batch into it, K9b over the keys of the resident records (sort and merge), and the output
+// tail (write_store_output) that turns "header + records of the store in the order of a permutation" into a BGZF file piece by piece
+// (offsets, piece bounds, K9c gather, deflate) and hands back the figures every stats struct takes from it.  The permutation is a
+// list of record numbers: it may leave records out (a filter) or name one several times (sbx_view_bam with listed regions).  The
+// stream written never exists as a whole.  What the kernels share is wave_prims.hpp.
 #pragma once
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include "engine_ctx.hpp"
 #include "engine_stream.hpp"
 #include "sort.hpp"
@@ -30,12 +29,6 @@ inline std::vector<uint8_t> bam_header_bytes(const std::string& text, const std:
         put32((uint32_t)r.length);
     }
     return h;
-}
-
-inline bool same_file(const char* a, const char* b) {
-    struct stat sa, sb;
-    if (stat(a, &sa) != 0 || stat(b, &sb) != 0) return false;
-    return sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
 }
 
 // a device array of the kept records that grows while the batches arrive (the number of records is not known in advance)
@@ -153,15 +146,15 @@ inline OutputPlan plan_output(const uint32_t* d_len, const uint32_t* d_perm, uin
     return p;
 }
 
-// K9c + deflate, piece by piece, into out_path (+ the EOF block).  *out_created is set as soon as the file exists (the caller
-// removes it when the call fails).
-inline void write_permuted_bam(const char* out_path, const std::vector<uint8_t>& header, const OutputPlan& plan, const uint8_t* d_store,
-                               const uint64_t* d_off, const uint32_t* d_perm, const uint64_t* d_out_off, uint64_t n, int level, bool* out_created,
+// K9c + deflate, piece by piece, into the file of `out` (+ the EOF block).  `out` is armed as soon as the file exists: it removes
+// the file when the call, or the command after it, fails.
+inline void write_permuted_bam(OutputGuard& out, const std::vector<uint8_t>& header, const OutputPlan& plan, const uint8_t* d_store,
+                               const uint64_t* d_off, const uint32_t* d_perm, const uint64_t* d_out_off, uint64_t n, int level,
                                double* ms_gather, BgzfPieceTimes* bt_times) {
     const uint64_t hlen = header.size();
-    FILE* f = fopen(out_path, "wb");
-    if (!f) throw Error(SBX_EIO, std::string("cannot write ") + out_path);
-    *out_created = true;
+    FILE* f = fopen(out.c_str(), "wb");
+    if (!f) throw Error(SBX_EIO, "cannot write " + out.path);
+    out.arm();
     bool ok = true;
     EventTimer t_gather;
     try {
@@ -182,7 +175,41 @@ inline void write_permuted_bam(const char* out_path, const std::vector<uint8_t>&
                              [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
     } catch (...) { fclose(f); throw; }
     ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
-    if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + out_path);
+    if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out.path);
+}
+
+// ---- the output tail of the four commands ----
+struct WrittenBam {
+    uint64_t stream_bytes = 0;      // header + records, inflated
+    uint64_t compressed_bytes = 0;  // the file, EOF block included
+    double ms_deflate = 0;          // deflate + packing of the blocks
+    double w_planned = 0;           // wall_now() between the offsets and the first piece
+};
+// The records d_perm[0, n) of the store, behind `header`, into the file of `out`: offsets (plan_output, into d_out_off: n + 2 words
+// the caller provides -- sort and merge hand in a key buffer they are done with), the check that they add up to *expect_bytes record
+// bytes (null: no check; `records` words the refusal: "sorted records"), d_len released, K9c + deflate.  *ms_gather += device time
+// of offsets and gather.  `out` stays armed: the caller disarms it when nothing can fail any more.
+inline WrittenBam write_store_output(OutputGuard& out, const std::vector<uint8_t>& header, const uint8_t* d_store, const uint64_t* d_off,
+                                     DevBuf<uint32_t>& d_len, const uint32_t* d_perm, uint64_t n, uint64_t* d_out_off, int level,
+                                     const unsigned long long* expect_bytes, const char* records, hipStream_t s, double* ms_gather) {
+    WrittenBam w;
+    const OutputPlan plan = plan_output(d_len.p, d_perm, n, header.size(), d_out_off, s, ms_gather);
+    if (expect_bytes && plan.total != header.size() + *expect_bytes)
+        throw Error(SBX_EFORMAT, std::string("internal error: the offsets of the ") + records + " do not add up");
+    d_len.release();
+    w.w_planned = wall_now();
+    BgzfPieceTimes bt_times;
+    write_permuted_bam(out, header, plan, d_store, d_off, d_perm, d_out_off, n, level, ms_gather, &bt_times);
+    w.stream_bytes = plan.total;
+    w.compressed_bytes = bt_times.out_bytes + 28;
+    w.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+    return w;
+}
+
+// the .bai next to a BAM just written: a pass of its own, not part of the command's figures; a failure leaves the BAM in place
+inline int index_written_bam(const char* path, int with_index, int device, char* err, size_t errlen) {
+    if (!with_index) return SBX_OK;
+    return sbx_build_index(path, (std::string(path) + ".bai").c_str(), device, err, errlen);
 }
 
 }  // namespace sbx

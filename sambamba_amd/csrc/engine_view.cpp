@@ -58,25 +58,10 @@ ViewRegions resolve_regions(const sbx_ctx* c, const char* const* regions, size_t
 }
 
 void check_opts(const sbx_filter* filter, const sbx_view_opts* opts, uint64_t* threshold) {
-    if (filter && (filter->n_ops < 0 || filter->n_ops > SBX_FILTER_MAX_OPS)) throw Error(SBX_EINVAL, "malformed filter");
+    check_filter(filter);
     *threshold = 0;
     if (opts && opts->subsample && !viewc::subsample_threshold(opts->fraction, threshold))
         throw Error(SBX_EINVAL, "the subsampling fraction must be a number that is not negative");
-}
-
-// the input opened for an index-mode pass in which K2 leaves a verdict on every record (an empty filter admits all of them)
-sbx_ctx* open_for_view(const char* in_path, const sbx_filter* filter, int device) {
-    const char* one[1] = {in_path};
-    char e2[512] = {0};
-    sbx_ctx* c = sbx_open(one, 1, device, e2, sizeof e2);
-    if (!c) throw Error(t_open_code != SBX_OK ? t_open_code : SBX_EIO, e2);
-    c->index_mode = true;
-    memset(&c->filter, 0, sizeof c->filter);             // (not depth's default filter)
-    if (filter && filter->n_ops > 0) c->filter = *filter;
-    c->filter_every = true;
-    c->mode = SBX_MODE_BASE;
-    c->fix_mate = false;
-    return c;
 }
 
 ViewSelectArgs select_args(sbx_ctx* c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& regions, const sbx_region* d_regions,
@@ -95,10 +80,6 @@ ViewSelectArgs select_args(sbx_ctx* c, const sbx_view_opts* opts, uint64_t thres
 void upload_regions(const ViewRegions& regions, DevBuf<sbx_region>* d, hipStream_t s) {
     d->ensure(regions.list.size() + 1);
     if (!regions.list.empty()) SBX_HIP(hipMemcpyAsync(d->p, regions.list.data(), regions.list.size() * sizeof(sbx_region), hipMemcpyHostToDevice, s));
-}
-
-std::string malformed(unsigned long long n) {
-    return "malformed BAM record (" + std::to_string(n) + " records whose reference id is out of range or whose lengths are inconsistent)";
 }
 
 void print_timing(const sbx_view_stats& st, const char* sink) {
@@ -126,29 +107,18 @@ int sbx_view_reference_info(sbx_ctx* c, char* out, size_t cap, size_t* out_len) 
     std::vector<std::string> names;
     std::vector<int64_t> lengths;
     for (const RefSeq& r : c->hdr.refs) { names.push_back(r.name); lengths.push_back(r.length); }
-    const std::string t = viewc::reference_info_json(names, lengths);
-    if (out_len) *out_len = t.size();
-    if (!out || t.size() + 1 > cap) return SBX_ENOMEM;
-    memcpy(out, t.data(), t.size());
-    out[t.size()] = 0;
-    return SBX_OK;
+    return copy_to_caller(viewc::reference_info_json(names, lengths), out, cap, out_len);
 }
 
 int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions, size_t n_regions,
                    const char* bed_path, int device, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
-    sbx_ctx* c = nullptr;
-    auto fail = [&](int code, const std::string& m) {
-        set_err(err, errlen, m);
-        if (c) sbx_close(c);
-        return code;
-    };
-    try {
+    return run_entry(err, errlen, [&] {
         if (!in_path || !count) throw Error(SBX_EINVAL, "null argument");
         uint64_t threshold = 0;
         check_opts(filter, opts, &threshold);
         const double w0 = wall_now();
-        c = open_for_view(in_path, filter, device);
-        const ViewRegions sel = resolve_regions(c, regions, n_regions, bed_path);
+        Standalone c = open_record_pass(in_path, device, filter, true);
+        const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
         hipStream_t s = c->stream.get();
         DevBuf<sbx_region> d_regions;
         upload_regions(sel, &d_regions, s);
@@ -158,9 +128,9 @@ int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view
         EventTimer t_k;
         uint64_t n_in = 0;
         uint32_t n_batches = 0;
-        for_each_record_batch(c, index_batch_bytes(), &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        for_each_record_batch(c.get(), index_batch_bytes(), &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
             t_k.start(s);
-            launch_view_select(select_args(c, opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p), s);
+            launch_view_select(select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p), s);
             t_k.stop(s);
             // (the next batch's K2 overwrites these descriptors, and may reallocate them, from the host side: K12a ends first)
             SBX_HIP(hipStreamSynchronize(s));
@@ -172,7 +142,7 @@ int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view
         unsigned long long acc[kViewAccWords] = {0};
         SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
         SBX_HIP(hipStreamSynchronize(s));
-        if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed(acc[kViewAccBad]));
+        if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
         st.n_records_in = n_in; st.n_records_selected = acc[kViewAccRecords]; st.n_entries_out = acc[kViewAccEntries];
         st.inflated_bytes = c->blocks.out_off.back();
         st.n_regions = sel.given(); st.n_batches = n_batches;
@@ -180,45 +150,32 @@ int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view
         print_timing(st, "count");
         *count = acc[kViewAccEntries];
         if (stats) *stats = st;
-        sbx_close(c);
-        return SBX_OK;
-    } catch (const Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return fail(SBX_EINVAL, e.what());
-    }
+    });
 }
 
 int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
                  size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device,
                  sbx_view_stats* stats, char* err, size_t errlen) {
-    sbx_ctx* c = nullptr;
-    bool out_created = false;
     const bool to_stdout = !out_path || !strcmp(out_path, "-");
     const char* const path = to_stdout ? "/dev/stdout" : out_path;
-    auto fail = [&](int code, const std::string& m) {
-        set_err(err, errlen, m);
-        if (c) sbx_close(c);
-        if (out_created && !to_stdout) unlink(path);
-        return code;
-    };
-    try {
+    const int rc = run_entry(err, errlen, [&] {
         if (!in_path) throw Error(SBX_EINVAL, "null argument");
-        if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
+        check_level(level);
         if (to_stdout && with_index) throw Error(SBX_EINVAL, "an output on stdout cannot be indexed");
-        if (!to_stdout && same_file(in_path, path)) throw Error(SBX_EINVAL, std::string("the output would overwrite the input ") + in_path);
+        if (!to_stdout) refuse_overwrite(in_path, path);
         uint64_t threshold = 0;
         check_opts(filter, opts, &threshold);
         const double w0 = wall_now();
-        c = open_for_view(in_path, filter, device);
-        const ViewRegions sel = resolve_regions(c, regions, n_regions, bed_path);
+        Standalone c = open_record_pass(in_path, device, filter, true);
+        OutputGuard out_file(path, to_stdout);
+        const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
         const bool listed = !sel.merged && !sel.list.empty();
         std::string text, why;
         if (!mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why)) throw Error(SBX_EFORMAT, "SAM header: " + why);
         const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
         const uint64_t hlen = header.size();
 
-        const StorePlan plan = plan_record_store(c, hlen, 48, "selecting records of");
+        const StorePlan plan = plan_record_store(c.get(), hlen, 48, "selecting records of");
         const uint64_t u_first = plan.u_first;
         hipStream_t s = c->stream.get();
         DevBuf<uint8_t> d_store((size_t)plan.store_bytes + 64);
@@ -237,14 +194,14 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         uint32_t n_batches = 0;
         bool too_many = false;
         unsigned long long acc[kViewAccWords] = {0};
-        for_each_record_batch(c, plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        for_each_record_batch(c.get(), plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
             const uint32_t groups = view_groups(nrec);
             d_count.ensure((size_t)nrec + 2);
             d_group_entries.ensure(groups + 4); d_group_records.ensure(groups + 4);
             d_group_entry_base.ensure(groups + 4); d_group_record_base.ensure(groups + 4);
             t_a.start(s);
-            copy_batch_to_store(c, d_store.p, u_first, cur, base, next, s);
-            ViewSelectArgs a = select_args(c, opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p);
+            copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
+            ViewSelectArgs a = select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p);
             a.with_lengths = 1;
             a.count = d_count.p; a.group_entries = d_group_entries.p; a.group_records = d_group_records.p;
             launch_view_select(a, s);
@@ -284,12 +241,11 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
             n_ent = acc[kViewAccEntries];
             return true;
         });
-        if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed(acc[kViewAccBad]));
+        if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
         if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 output records");
         if (!listed && n_ent != n_rec) throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_ent) + " entries for " + std::to_string(n_rec) + " records");
         const uint64_t u_total = plan.u_total;
-        sbx_close(c);                                    // the batch buffers make room for the sort and the output pieces
-        c = nullptr;
+        c.reset();                                       // the batch buffers make room for the sort and the output pieces
         d_count.release(); d_group_entries.release(); d_group_records.release(); d_group_entry_base.release(); d_group_record_base.release();
 
         // ---- the order of the entries ----
@@ -321,30 +277,19 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         d_len.ensure(2);                                 // (nothing selected: the arrays were never grown)
         d_off.ensure(2);
         DevBuf<uint64_t> d_out_off((size_t)n + 2);
-        const OutputPlan out = plan_output(d_len.p, d_perm.p, n, hlen, d_out_off.p, s, &st.ms_gather);
-        if (out.total != hlen + acc[kViewAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the selected records do not add up");
-        d_len.release();
-
-        // ---- K9c + deflate, piece by piece ----
-        BgzfPieceTimes bt_times;
-        write_permuted_bam(path, header, out, d_store.p, d_off.p, d_perm.p, d_out_off.p, n, level, &out_created, &st.ms_gather, &bt_times);
+        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, d_perm.p, n, d_out_off.p, level,
+                                                &acc[kViewAccBytes], "selected records", s, &st.ms_gather);
+        out_file.disarm();
         st.n_records_in = n_in; st.n_records_selected = n_rec; st.n_entries_out = n;
-        st.inflated_bytes = u_total; st.stream_bytes = out.total; st.compressed_bytes = bt_times.out_bytes + 28;
+        st.inflated_bytes = u_total; st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
         st.n_regions = sel.given(); st.n_batches = n_batches;
-        st.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+        st.ms_deflate = w.ms_deflate;
         st.ms_total_wall = (wall_now() - w0) * 1e3;
         print_timing(st, "bam");
         if (stats) *stats = st;
-    } catch (const Error& e) {
-        return fail(e.code, e.what());
-    } catch (const std::exception& e) {
-        return fail(SBX_EINVAL, e.what());
-    }
-    if (with_index) {
-        const int rc = sbx_build_index(path, (std::string(path) + ".bai").c_str(), device, err, errlen);
-        if (rc != SBX_OK) return rc;          // (the index is a pass of its own and not part of the figures)
-    }
-    return SBX_OK;
+    });
+    // (the index is a pass of its own and not part of the figures)
+    return rc != SBX_OK ? rc : index_written_bam(path, with_index, device, err, errlen);
 }
 
 }  // extern "C"

@@ -15,9 +15,9 @@ extern "C" {
 
 int sbx_bgzf_compress(const uint8_t* in, size_t n, int level, int with_eof, int device, uint8_t* out, size_t cap, size_t* out_len,
                       char* err, size_t errlen) {
-    try {
+    return run_entry(err, errlen, [&] {
         if ((!in && n) || !out_len) throw Error(SBX_EINVAL, "null argument");
-        if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
+        check_level(level);
         require_device(device);
         size_t pos = 0;
         bgzf_compress_stream(in, n, level, [&](const uint8_t* p, size_t k) {
@@ -31,29 +31,20 @@ int sbx_bgzf_compress(const uint8_t* in, size_t n, int level, int with_eof, int 
         }
         *out_len = pos;
         if (pos > cap || !out) throw Error(SBX_ENOMEM, "output buffer too small for the BGZF stream");
-        return SBX_OK;
-    } catch (const Error& e) {
-        set_err(err, errlen, e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_err(err, errlen, e.what());
-        return SBX_EINVAL;
-    }
+    });
 }
 
 // ---- index-mode passes: the record stream of one file in batches (sbx_build_index, sbx_flagstat) ---------------------------------
 int sbx_build_index(const char* bam_path, const char* bai_path, int device, char* err, size_t errlen) {
-    sbx_ctx* c = nullptr;
-    try {
+    return run_entry(err, errlen, [&] {
         if (!bam_path || !bai_path) throw Error(SBX_EINVAL, "null argument");
-        const char* one[1] = {bam_path};
-        char e2[512] = {0};
-        c = sbx_open(one, 1, device, e2, sizeof e2);
-        if (!c) throw Error(SBX_EIO, e2);
-        c->index_mode = true;
-        memset(&c->filter, 0, sizeof c->filter);         // no filter: every record is described
-        c->mode = SBX_MODE_BASE;
-        c->fix_mate = false;
+        Standalone ctx;
+        try {
+            ctx = open_record_pass(bam_path, device, nullptr, false);      // no filter: every record is described
+        } catch (const Error& e) {
+            throw Error(SBX_EIO, e.what());              // (whatever the open says: a BAM that cannot be indexed is an I/O failure here)
+        }
+        sbx_ctx* const c = ctx.get();
         // IndexBuilder is one pass over a stream of records (bai/indexing.d:262-316), and so is this: the file goes through the
         // device in batches of whole BGZF blocks (for_each_record_batch).
         const BlockTable& bt = c->blocks;
@@ -181,17 +172,7 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
         if (!f) throw Error(SBX_EIO, std::string("cannot write ") + bai_path);
         const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
         if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + bai_path);
-        sbx_close(c);
-        return SBX_OK;
-    } catch (const Error& e) {
-        set_err(err, errlen, e.what());
-        if (c) sbx_close(c);
-        return e.code;
-    } catch (const std::exception& e) {
-        set_err(err, errlen, e.what());
-        if (c) sbx_close(c);
-        return SBX_EINVAL;
-    }
+    });
 }
 
 // `sambamba flagstat` (computeFlagStatistics, flagstat.d:31-58): one pass like sbx_build_index's -- index mode, no filter, no sort
@@ -200,18 +181,10 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
 // block_size) or one that starts beyond its contig: the reference reads nothing but the flags, mapq and the two reference ids.
 int sbx_flagstat(const char* bam_path, int device, sbx_flagstat_counts* out, char* err, size_t errlen) {
     static_assert(sizeof(sbx_flagstat_counts) == 26 * sizeof(uint64_t), "sbx_flagstat_counts is the kernel's 26 counters");
-    sbx_ctx* c = nullptr;
-    try {
+    return run_entry(err, errlen, [&] {
         if (!bam_path || !out) throw Error(SBX_EINVAL, "null argument");
         const double w0 = wall_now();
-        const char* one[1] = {bam_path};
-        char e2[512] = {0};
-        c = sbx_open(one, 1, device, e2, sizeof e2);
-        if (!c) throw Error(t_open_code != SBX_OK ? t_open_code : SBX_EIO, e2);
-        c->index_mode = true;
-        memset(&c->filter, 0, sizeof c->filter);         // no filter: every record is described
-        c->mode = SBX_MODE_BASE;
-        c->fix_mate = false;
+        Standalone c = open_record_pass(bam_path, device, nullptr, false);      // no filter: every record is described
         hipStream_t s = c->stream.get();
         DevBuf<unsigned long long> d_counts(26);
         SBX_HIP(hipMemsetAsync(d_counts.p, 0, d_counts.bytes(), s));
@@ -221,7 +194,7 @@ int sbx_flagstat(const char* bam_path, int device, sbx_flagstat_counts* out, cha
         double ms_inflate = 0, ms_index = 0, ms_k8 = 0;
         uint64_t n_records = 0;
         uint32_t n_batches = 0;
-        for_each_record_batch(c, index_batch_bytes(), &n_batches, [&](uint64_t nrec, uint64_t, uint64_t) -> bool {
+        for_each_record_batch(c.get(), index_batch_bytes(), &n_batches, [&](uint64_t nrec, uint64_t, uint64_t) -> bool {
             t_k.start(s);
             launch_flagstat(c->U(), c->d_desc.p, c->d_rec_ref.p, nrec, d_counts.p, s);
             t_k.stop(s);
@@ -242,17 +215,7 @@ int sbx_flagstat(const char* bam_path, int device, sbx_flagstat_counts* out, cha
             fprintf(stderr, "[sbx] flagstat: %llu records in %u batch(es): inflate %.2f ms, record index %.2f ms, flagstat kernel %.3f ms; "
                             "open %.1f ms, pass %.1f ms (wall)\n", (unsigned long long)n_records, n_batches, ms_inflate, ms_index, ms_k8,
                     (w1 - w0) * 1e3, (wall_now() - w1) * 1e3);
-        sbx_close(c);
-        return SBX_OK;
-    } catch (const Error& e) {
-        set_err(err, errlen, e.what());
-        if (c) sbx_close(c);
-        return e.code;
-    } catch (const std::exception& e) {
-        set_err(err, errlen, e.what());
-        if (c) sbx_close(c);
-        return SBX_EINVAL;
-    }
+    });
 }
 
 extern "C++" {
@@ -296,17 +259,13 @@ int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, si
     with_pct("singletons", f->single, f->pair_all);
     param("with mate mapped to a different chr", f->diff_chr);
     param("with mate mapped to a different chr (mapQ>=5)", f->diff_high);
-    if (len) *len = out.size();
-    if (!buf || out.size() + 1 > cap) return SBX_ENOMEM;
-    memcpy(buf, out.data(), out.size());
-    buf[out.size()] = 0;
-    return SBX_OK;
+    return copy_to_caller(out, buf, cap, len);
 }
 
 int sbx_write_bam(const char* path, const uint8_t* stream, size_t n, int level, int with_index, int device, char* err, size_t errlen) {
-    try {
+    const int rc = run_entry(err, errlen, [&] {
         if (!path || (!stream && n)) throw Error(SBX_EINVAL, "null argument");
-        if (level < -1 || level > 9) throw Error(SBX_EINVAL, "compression level must be -1 (default) or 0 .. 9");
+        check_level(level);
         require_device(device);
         FILE* f = fopen(path, "wb");
         if (!f) throw Error(SBX_EIO, std::string("cannot write ") + path);
@@ -316,15 +275,9 @@ int sbx_write_bam(const char* path, const uint8_t* stream, size_t n, int level, 
         } catch (...) { fclose(f); throw; }
         ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
         if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + path);
-    } catch (const Error& e) {
-        set_err(err, errlen, e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_err(err, errlen, e.what());
-        return SBX_EINVAL;
-    }
-    if (with_index) return sbx_build_index(path, (std::string(path) + ".bai").c_str(), device, err, errlen);
-    return SBX_OK;
+    });
+    if (rc != SBX_OK || !with_index) return rc;
+    return sbx_build_index(path, (std::string(path) + ".bai").c_str(), device, err, errlen);
 }
 
 }  // extern "C"

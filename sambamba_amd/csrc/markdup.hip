@@ -4,7 +4,8 @@
 //                           class (out / fragment / pairable), and for the records that take part the position key (library, ref_id,
 //                           5' coordinate, strand), the score and -- pairable ones -- the hash of name + RG (markdup_core.hpp).  Every
 //                           length the record states is checked against its block_size and the batch before a byte behind the
-//                           fixed part is read; a record that fails is counted and the call ends with SBX_EFORMAT.
+//                           fixed part is read (read_record_frame, wave_prims.hpp); a record that fails is counted and the call
+//                           ends with SBX_EFORMAT.
 //   K10b k_md_pair_runs     the pairable records, sorted by hash (K9b, stable: runs of equal hashes are in file order).  The lane at
 //                           the head of a run pairs the records of the run whose name and RG BYTES are equal, 1st with 2nd, 3rd with
 //                           4th; a run of two -- the usual case -- is one comparison.
@@ -17,12 +18,11 @@
 #include "common.hpp"
 #include "markdup.hpp"
 #include "markdup_core.hpp"
+#include "wave_prims.hpp"
 
 namespace sbx {
 
 namespace {
-
-__device__ __forceinline__ uint64_t md_lanemask_lt() { return (1ull << (threadIdx.x & 63u)) - 1ull; }
 
 // the RG:Z value among the aux fields [t, e) of a record at `rec`: its offset from rec, *len its length; 0: none
 __device__ uint32_t find_rg(const uint8_t* rec, uint64_t t, uint64_t e, uint32_t* len) {
@@ -38,7 +38,7 @@ __device__ uint32_t find_rg(const uint8_t* rec, uint64_t t, uint64_t e, uint32_t
             case 'B': {
                 if (t + 5 > e) return 0;
                 const uint8_t sub = rec[t];
-                const uint32_t n = mdc::ld32u(rec + t + 1);
+                const uint32_t n = ld32(rec + t + 1);
                 const uint32_t w = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u : 4u;
                 t += 5 + (uint64_t)n * w;
                 break;
@@ -66,37 +66,30 @@ __global__ __launch_bounds__(kMdThreads) void k_md_ends(MdEndsArgs a) {
         uint8_t cls = kMdOut;
         uint64_t key = 0, hash = 0;
         uint32_t score = 0, rg_at = 0;
-        bad = rec_off + 36 > a.u_end;
+        RecordFrame f;
+        bad = !read_record_frame(a.U, rec_off, a.u_end, a.n_ref, &f);
         if (!bad) {
-            const uint32_t bs = mdc::ld32u(p);
-            const int32_t ref = (int32_t)mdc::ld32u(p + 4), pos = (int32_t)mdc::ld32u(p + 8);
-            const uint32_t l_name = p[12], fnc = mdc::ld32u(p + 16), n_cigar = fnc & 0xFFFFu, flag = fnc >> 16;
-            const int32_t l_seq = (int32_t)mdc::ld32u(p + 20);
-            const uint64_t seq = l_seq < 0 ? 0 : (uint64_t)l_seq;
-            const uint64_t fixed = 32 + (uint64_t)l_name + 4ull * n_cigar + (seq + 1) / 2 + seq;
-            bad = bs < 32u || bs > 0x7FFFFFF0u || rec_off + 4ull + bs > a.u_end || l_seq < 0 || fixed > bs || ref < -1 || ref >= a.n_ref;
-            if (!bad) {
-                len = bs + 4u;
-                if (ref != -1 && !(flag & 0x904u)) {
-                    const bool reversed = flag & 0x10u;
-                    cls = ((flag & 1u) && !(flag & 8u)) ? kMdPairable : kMdFragment;
-                    const uint8_t* cigar = p + 36 + l_name;
-                    const int32_t coord = mdc::five_prime_coord(pos, reversed, cigar, n_cigar);
-                    score = mdc::score_of(cigar + 4ull * n_cigar + (seq + 1) / 2, (uint32_t)seq);
-                    uint32_t rg_len = 0;
-                    rg_at = find_rg(p, 4 + fixed, 4ull + bs, &rg_len);
-                    int32_t library = -1;
-                    if (rg_at) {
-                        for (int32_t g = 0; g < a.lib.n_rg; ++g) {
-                            const char* id = a.lib.ids + a.lib.id_off[g];
-                            uint32_t k = 0;
-                            while (k < rg_len && id[k] && (uint8_t)id[k] == p[rg_at + k]) ++k;
-                            if (k == rg_len && id[k] == 0) { library = a.lib.library_of[g]; break; }
-                        }
+            len = f.bs + 4u;
+            if (f.ref != -1 && !(f.flag & 0x904u)) {
+                const bool reversed = f.flag & 0x10u;
+                const uint64_t seq = (uint64_t)f.l_seq;
+                cls = ((f.flag & 1u) && !(f.flag & 8u)) ? kMdPairable : kMdFragment;
+                const uint8_t* cigar = p + 36 + f.l_name;
+                const int32_t coord = mdc::five_prime_coord(f.pos, reversed, cigar, f.n_cigar);
+                score = mdc::score_of(cigar + 4ull * f.n_cigar + (seq + 1) / 2, (uint32_t)seq);
+                uint32_t rg_len = 0;
+                rg_at = find_rg(p, 4 + f.fixed, 4ull + f.bs, &rg_len);
+                int32_t library = -1;
+                if (rg_at) {
+                    for (int32_t g = 0; g < a.lib.n_rg; ++g) {
+                        const char* id = a.lib.ids + a.lib.id_off[g];
+                        uint32_t k = 0;
+                        while (k < rg_len && id[k] && (uint8_t)id[k] == p[rg_at + k]) ++k;
+                        if (k == rg_len && id[k] == 0) { library = a.lib.library_of[g]; break; }
                     }
-                    key = mdc::pos_key(library, ref, coord, reversed ? 1u : 0u, a.ref_bits);
-                    if (cls == kMdPairable) hash = mdc::pair_hash(p + 36, l_name ? l_name - 1u : 0u, p + rg_at, rg_len) & a.hash_mask;
                 }
+                key = mdc::pos_key(library, f.ref, coord, reversed ? 1u : 0u, a.ref_bits);
+                if (cls == kMdPairable) hash = mdc::pair_hash(p + 36, f.l_name ? f.l_name - 1u : 0u, p + rg_at, rg_len) & a.hash_mask;
             }
         }
         a.r.off[at] = (uint64_t)((int64_t)rec_off + a.store_delta);
@@ -108,16 +101,15 @@ __global__ __launch_bounds__(kMdThreads) void k_md_ends(MdEndsArgs a) {
         a.r.rg_at[at] = rg_at;
     }
     const unsigned long long mb = __ballot(bad);
-    unsigned long long bytes = len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) bytes += __shfl_xor(bytes, d, 64);
+    const unsigned long long bytes = wave_sum<unsigned long long>(len);
     if ((threadIdx.x & 63u) == 0) {
         if (bytes) atomicAdd(a.acc + kMdAccBytes, bytes);
         if (mb) atomicAdd(a.acc + kMdAccBad, (unsigned long long)__popcll(mb));
     }
 }
 
-// ---- compaction ------------------------------------------------------------------------------------------------------------
+// ---- compaction: the record numbers that satisfy a predicate, in file order (block_rank_of_kept, wave_prims.hpp; the workgroups
+// through launch_count_scan over k_md_compact_count's counts) ------------------------------------------------------------------
 __device__ __forceinline__ bool md_pred(uint32_t pred, const uint8_t* c, const uint32_t* mate, uint64_t i) {
     switch (pred) {
         case kMdPredPairable: return c[i] == kMdPairable;
@@ -131,29 +123,18 @@ __global__ __launch_bounds__(kMdThreads) void k_md_compact_count(uint32_t pred, 
                                                                  uint64_t n, uint32_t* __restrict__ cnt) {
     __shared__ uint32_t wcnt[kMdThreads / 64];
     const uint64_t i = (uint64_t)blockIdx.x * kMdThreads + threadIdx.x;
-    const bool keep = i < n && md_pred(pred, c, mate, i);
-    const unsigned long long m = __ballot(keep);
-    if ((threadIdx.x & 63u) == 0) wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (uint32_t w = 0; w < kMdThreads / 64; ++w) s += wcnt[w];
-        cnt[blockIdx.x] = s;
-    }
+    uint32_t total;
+    block_rank_of_kept(i < n && md_pred(pred, c, mate, i), wcnt, &total);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kMdThreads) void k_md_compact_write(uint32_t pred, const uint8_t* __restrict__ c, const uint32_t* __restrict__ mate,
                                                                  uint64_t n, const uint64_t* __restrict__ group_base, uint32_t* __restrict__ out) {
     __shared__ uint32_t wcnt[kMdThreads / 64];
-    const uint32_t wave = threadIdx.x >> 6;
     const uint64_t i = (uint64_t)blockIdx.x * kMdThreads + threadIdx.x;
     const bool keep = i < n && md_pred(pred, c, mate, i);
-    const unsigned long long m = __ballot(keep);
-    if ((threadIdx.x & 63u) == 0) wcnt[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += wcnt[w];
-    if (keep) out[group_base[blockIdx.x] + before + (uint32_t)__popcll(m & md_lanemask_lt())] = (uint32_t)i;
+    const uint32_t rank = block_rank_of_kept(keep, wcnt);
+    if (keep) out[group_base[blockIdx.x] + rank] = (uint32_t)i;
 }
 
 __global__ __launch_bounds__(kMdThreads) void k_md_gather_keys(const uint64_t* __restrict__ word, const uint32_t* __restrict__ idx, uint64_t n,
@@ -162,12 +143,7 @@ __global__ __launch_bounds__(kMdThreads) void k_md_gather_keys(const uint64_t* _
     const bool live = j < n;
     const uint64_t k = live ? word[idx[j]] : 0;
     if (live) key[j] = k;
-    unsigned long long k_or = live ? k : 0ull, k_and = live ? k : ~0ull;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        k_or |= __shfl_xor(k_or, d, 64);
-        k_and &= __shfl_xor(k_and, d, 64);
-    }
+    const unsigned long long k_or = wave_or(live ? k : 0ull), k_and = wave_and(live ? k : ~0ull);
     if ((threadIdx.x & 63u) == 0 && live) {               // (lane 0 is live when any lane of the wave is)
         atomicOr(acc + kMdAccOr, k_or);
         atomicAnd(acc + kMdAccAnd, k_and);

@@ -2,7 +2,8 @@
 // input are rewritten on their way into the resident record store.
 //
 //   K11a k_merge_describe  one lane per described record.  Every length the record states is checked against its block_size and the
-//                          batch before a byte behind the fixed part is read (as K10a does); then the aux fields are walked, every
+//                          batch before a byte behind the fixed part is read (read_record_frame, wave_prims.hpp, as in K10a; the
+//                          reference ids are those of the input's own dictionary); then the aux fields are walked, every
 //                          type's size checked against the record end -- `B` arrays by element type and count, `Z` / `H` to a NUL
 //                          inside the record.  The value of the first RG:Z and of the first PG:Z field is looked up in the input's
 //                          rename table (only the ids that change, compared byte for byte); a hit is a patch: offset of the old
@@ -14,26 +15,20 @@
 //                          behind the store's fill, and its record number behind the records kept before.
 //   K11b k_merge_rewrite   sixteen lanes per record (K9c's partition).  The first 36 bytes go out byte by byte with block_size,
 //                          ref_id and next_ref_id replaced (-1 stays -1; a next_ref_id outside the input's dictionary stays as it
-//                          is); the stretches between the patches move as K9c moves a record -- head bytes up to a 16-byte boundary
-//                          of the destination, 16 bytes per lane, tail bytes --; the new ids are written byte by byte.  Plain C++
-//                          vector stores.  The host has compared the scanned size of the batch with what is left of the store
-//                          before the launch: no lane writes behind store_at + len_base[n].
+//                          is); the stretches between the patches move as K9c moves a record (copy_span16, wave_prims.hpp); the
+//                          new ids are written byte by byte.  Plain C++ vector stores.  The host has compared the scanned size of
+//                          the batch with what is left of the store before the launch: no lane writes behind store_at + len_base[n].
 //
 // Bytes moved (n records, b bytes): K11a reads 32 n of descriptors and the fixed part + aux fields of every record, writes 36 n;
 // the scans read and write 24 n; K11b reads and writes b.
 #include "common.hpp"
 #include "merge.hpp"
 #include "sort_core.hpp"
+#include "wave_prims.hpp"
 
 namespace sbx {
 
 namespace {
-
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);                  // (records start at any byte)
-    return v;
-}
 
 // the entry of `kind` whose old id is the n bytes at v; kMergeNone: the id does not change.  A linear scan, one lane per record,
 // byte loads: written for the handful of colliding ids of per-lane files (a table of a few entries, which stays in cache).  The
@@ -66,30 +61,15 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_describe(MergeArgs a) {
         if (a.use_filter) { keep = d.pad == kFilterPass; bad = d.pad == kFilterBad; }
         if (keep && !bad) {
             const uint8_t* p = a.U + rec_off;
-            bad = rec_off + 36 > a.u_end;
-            uint32_t bs = 0;
-            uint64_t fixed = 0;
-            int32_t ref = -1, next_ref = -1, pos = 0;
-            uint32_t flag = 0;
+            RecordFrame f;
+            bad = !read_record_frame(a.U, rec_off, a.u_end, a.n_ref_own, &f);
             if (!bad) {
-                bs = ld32(p);
-                ref = (int32_t)ld32(p + 4);
-                pos = (int32_t)ld32(p + 8);
-                const uint32_t l_name = p[12], fnc = ld32(p + 16), n_cigar = fnc & 0xFFFFu;
-                flag = fnc >> 16;
-                const int32_t l_seq = (int32_t)ld32(p + 20);
-                next_ref = (int32_t)ld32(p + 24);
-                const uint64_t seq = l_seq < 0 ? 0 : (uint64_t)l_seq;
-                fixed = 32 + (uint64_t)l_name + 4ull * n_cigar + (seq + 1) / 2 + seq;
-                bad = bs < 32u || bs > 0x7FFFFFF0u || rec_off + 4ull + bs > a.u_end || l_seq < 0 || fixed > bs || ref < -1 || ref >= a.n_ref_own;
-            }
-            if (!bad) {
-                old_len = bs + 4u;
+                old_len = f.bs + 4u;
                 int64_t grow = 0;
                 uint32_t np = 0;
                 bool seen[2] = {false, false};
-                uint64_t t = 4 + fixed;
-                const uint64_t e = 4ull + bs;
+                uint64_t t = 4 + f.fixed;
+                const uint64_t e = 4ull + f.bs;
                 while (t < e) {
                     if (t + 3 > e) { bad = true; break; }
                     const uint8_t k0 = p[t], k1 = p[t + 1], ty = p[t + 2];
@@ -131,9 +111,9 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_describe(MergeArgs a) {
                     const int64_t nl = (int64_t)old_len + grow;
                     bad = nl < 36 || nl > 0x7FFFFFF0ll;
                     new_len = (uint32_t)nl;
-                    const int32_t new_ref = map_ref(a, ref), new_next = map_ref(a, next_ref);
-                    changed = np != 0 || new_ref != ref || new_next != next_ref;
-                    key = sortc::sort_key(new_ref, pos, flag, a.n_ref_merged);
+                    const int32_t new_ref = map_ref(a, f.ref), new_next = map_ref(a, f.next_ref);
+                    changed = np != 0 || new_ref != f.ref || new_next != f.next_ref;
+                    key = sortc::sort_key(new_ref, f.pos, f.flag, a.n_ref_merged);
                 }
             }
         }
@@ -147,14 +127,8 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_describe(MergeArgs a) {
     }
     // the wave's share of the accumulators
     const unsigned long long m = __ballot(keep), mb = __ballot(bad), mc = __ballot(changed);
-    unsigned long long k_or = keep ? key : 0ull, k_and = keep ? key : ~0ull, bytes = new_len, old_bytes = old_len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        k_or |= __shfl_xor(k_or, d, 64);
-        k_and &= __shfl_xor(k_and, d, 64);
-        bytes += __shfl_xor(bytes, d, 64);
-        old_bytes += __shfl_xor(old_bytes, d, 64);
-    }
+    const unsigned long long k_or = wave_or(keep ? key : 0ull), k_and = wave_and(keep ? key : ~0ull);
+    const unsigned long long bytes = wave_sum<unsigned long long>(new_len), old_bytes = wave_sum<unsigned long long>(old_len);
     if ((threadIdx.x & 63u) == 0) {
         if (m) {
             atomicOr(a.acc + kSortAccOr, k_or);
@@ -169,23 +143,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_describe(MergeArgs a) {
 }
 
 // ---- K11b ----------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kRewriteGroup = 16, kRewriteRecs = kMergeThreads / kRewriteGroup;
-struct __attribute__((packed, aligned(1))) Bytes16 { uint32_t w[4]; };
-
-// nb bytes from s to d, both at any byte address, by the sixteen lanes of a record (lane l): K9c's scheme
-__device__ __forceinline__ void copy_span(uint8_t* d, const uint8_t* s, uint64_t nb, uint32_t l) {
-    const uint32_t head = (uint32_t)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u);
-    const uint32_t h = head < nb ? head : (uint32_t)nb;
-    if (l < h) d[l] = s[l];
-    s += h; d += h; nb -= h;
-    const uint64_t chunks = nb >> 4;
-    for (uint64_t c = l; c < chunks; c += kRewriteGroup) {
-        const Bytes16 x = *(const Bytes16*)(s + 16 * c);
-        *(uint4*)(d + 16 * c) = uint4{x.w[0], x.w[1], x.w[2], x.w[3]};
-    }
-    const uint32_t tail = (uint32_t)(nb & 15u);
-    if (l < tail) d[16 * chunks + l] = s[16 * chunks + l];
-}
+constexpr uint32_t kRewriteGroup = kCopyGroup, kRewriteRecs = kMergeThreads / kRewriteGroup;
 
 __global__ __launch_bounds__(kMergeThreads) void k_merge_rewrite(MergeArgs a) {
     const uint32_t l = threadIdx.x % kRewriteGroup;
@@ -209,13 +167,13 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_rewrite(MergeArgs a) {
         if (en == kMergeNone) break;
         const uint32_t p_at = a.b.patch_at[2 * i + k];
         const RenameEntry x = a.table.entry[en];
-        copy_span(dst + d_pos, src + s_pos, p_at - s_pos, l);
+        copy_span16(dst + d_pos, src + s_pos, p_at - s_pos, l);
         d_pos += p_at - s_pos;
         for (uint32_t b = l; b < x.new_len; b += kRewriteGroup) dst[d_pos + b] = (uint8_t)a.table.blob[x.new_off + b];
         d_pos += x.new_len;
         s_pos = (uint64_t)p_at + x.old_len;
     }
-    copy_span(dst + d_pos, src + s_pos, old_len - s_pos, l);
+    copy_span16(dst + d_pos, src + s_pos, old_len - s_pos, l);
     if (l == 0) {
         const uint64_t r = a.out_base + a.b.keep_base[i];
         a.key[r] = a.b.key[i];

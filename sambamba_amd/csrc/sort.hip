@@ -3,10 +3,10 @@
 //   K9a  k_sort_keys      one lane per described record of a batch: the 64-bit key (sort_core.hpp) from rec_ref, RecDesc::pos and
 //                         RecDesc::flag, the record's length (block_size + 4, read from U at any byte address) and its offset in the
 //                         resident record store.  With -F the records the filter rejects (RecDesc::pad, written by K2) are compacted
-//                         away: ballot + prefix inside a wave, the waves of a workgroup through LDS, the workgroups through an
-//                         exclusive scan of their counts (k_sort_group_count) -- so the kept records stay in file order, which is what
-//                         makes the sort below stable with respect to the file.  The kernel also folds the keys into an OR and an AND
-//                         word: the bits in which two keys of the file differ are the only ones K9b has to sort.
+//                         away: inside a workgroup by block_rank_of_kept (wave_prims.hpp), the workgroups through an exclusive scan
+//                         of their counts (k_sort_group_count) -- so the kept records stay in file order, which is what makes the
+//                         sort below stable with respect to the file.  The kernel also folds the keys into an OR and an AND word:
+//                         the bits in which two keys of the file differ are the only ones K9b has to sort.
 //   K9b  k_radix_hist /   stable LSD radix sort of (key, record number), 8 bits per pass.  A workgroup of four waves owns a tile of
 //        k_radix_scatter  4096 consecutive elements and takes them in sixteen rounds of 256.  Histogram: LDS atomics, one counter row
 //                         per tile, laid out [digit][tile] so that one exclusive scan (launch_count_scan) yields the first output
@@ -15,41 +15,31 @@
 //                         of them publishes the count in the wave's row of LDS, and a lane's slot is the tile's running offset of its
 //                         digit + the counts of the waves in front + its rank -- input order, hence stable.  No atomics in the scatter.
 //   K9c  k_gather_records sixteen lanes per record: the record's bytes go from the store to their place in a piece of the sorted
-//                         stream.  Both ends sit at arbitrary byte addresses; the destination is brought to a 16-byte boundary with
-//                         a head of single bytes, the body moves 16 bytes per lane (aligned store, unaligned load -- gfx950 takes
-//                         global loads at any byte address), the tail is single bytes again.  A piece is a whole number of BGZF
-//                         payloads; a record that straddles a piece boundary is copied in part by both pieces.
+//                         stream, both ends at arbitrary byte addresses (copy_span16, wave_prims.hpp).  A piece is a whole number
+//                         of BGZF payloads; a record that straddles a piece boundary is copied in part by both pieces.
 //
 // Bytes moved (n records, b bytes of records): K9a reads 36 n (descriptor, rec_ref) + 4 n scattered words of U and writes 20 n; a pass of
 // K9b reads 12 n twice (histogram: keys only, 8 n) and writes 12 n; the offsets read 8 n and write 8 n; K9c reads and writes b.
 #include "common.hpp"
 #include "sort.hpp"
 #include "sort_core.hpp"
+#include "wave_prims.hpp"
 
 namespace sbx {
 
 namespace {
 
-__device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << (threadIdx.x & 63u)) - 1ull; }
-
 // ---- K9a -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSortKeysThreads) void k_sort_group_count(const RecDesc* __restrict__ desc, uint64_t n, uint32_t* __restrict__ cnt) {
     __shared__ uint32_t wcnt[kSortKeysThreads / 64];
     const uint64_t i = (uint64_t)blockIdx.x * kSortKeysThreads + threadIdx.x;
-    const bool keep = i < n && desc[i].pad == kFilterPass;
-    const unsigned long long m = __ballot(keep);
-    if ((threadIdx.x & 63u) == 0) wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t s = 0;
-        for (uint32_t w = 0; w < kSortKeysThreads / 64; ++w) s += wcnt[w];
-        cnt[blockIdx.x] = s;
-    }
+    uint32_t total;
+    block_rank_of_kept(i < n && desc[i].pad == kFilterPass, wcnt, &total);
+    if (threadIdx.x == 0) cnt[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kSortKeysThreads) void k_sort_keys(SortKeysArgs a, const uint64_t* __restrict__ group_base) {
     __shared__ uint32_t wcnt[kSortKeysThreads / 64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t i = (uint64_t)blockIdx.x * kSortKeysThreads + threadIdx.x;
     const bool live = i < a.n;
     bool keep = live, bad = false;
@@ -62,37 +52,27 @@ __global__ __launch_bounds__(kSortKeysThreads) void k_sort_keys(SortKeysArgs a, 
         if (a.use_filter) { keep = d.pad == kFilterPass; bad = d.pad == kFilterBad; }
         else bad = ref < -1 || ref >= a.n_ref;
         if (keep && !bad) {
-            uint32_t bs;
-            __builtin_memcpy(&bs, a.U + rec_off, 4);                 // block_size (records start at any byte)
+            const uint32_t bs = ld32(a.U + rec_off);                 // block_size
             len = bs + 4u;
             // (the chain of K2 ends every record inside the batch; a record that would not is never copied)
-            bad = bs < 32u || bs > 0x7FFFFFF0u || rec_off + len > a.u_end;
+            bad = !record_len_ok(bs, rec_off, a.u_end);
             key = sortc::sort_key(ref, d.pos, d.flag, a.key_n_ref);
         }
         keep = keep && !bad;
     }
     const unsigned long long m = __ballot(keep);
     const unsigned long long mb = __ballot(bad);
-    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += wcnt[w];
+    const uint32_t rank = block_rank_of_kept(keep, wcnt);
     const uint64_t gbase = group_base ? group_base[blockIdx.x] : (uint64_t)blockIdx.x * kSortKeysThreads;
     if (keep) {
-        const uint64_t at = a.out_base + gbase + before + (uint32_t)__popcll(m & lanemask_lt());
+        const uint64_t at = a.out_base + gbase + rank;
         a.key[at] = key;
         a.off[at] = (uint64_t)((int64_t)rec_off + a.store_delta);
         a.len[at] = len;
     }
     // the wave's share of the accumulators
-    unsigned long long k_or = keep ? key : 0ull, k_and = keep ? key : ~0ull, bytes = keep ? len : 0ull;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        k_or |= __shfl_xor(k_or, d, 64);
-        k_and &= __shfl_xor(k_and, d, 64);
-        bytes += __shfl_xor(bytes, d, 64);
-    }
-    if (lane == 0) {
+    const unsigned long long k_or = wave_or(keep ? key : 0ull), k_and = wave_and(keep ? key : ~0ull), bytes = wave_sum<unsigned long long>(keep ? len : 0ull);
+    if ((threadIdx.x & 63u) == 0) {
         if (m) {
             atomicOr(a.acc + kSortAccOr, k_or);
             atomicAnd(a.acc + kSortAccAnd, k_and);
@@ -175,36 +155,6 @@ __global__ __launch_bounds__(kRadixThreads) void k_radix_scatter(const uint64_t*
 // ---- offsets of the sorted records ---------------------------------------------------------------------------------------------
 constexpr uint32_t kLenThreads = 256, kLenItems = kLenTile / kLenThreads;
 
-// sum of the values of the workgroup's threads; valid in every thread
-__device__ __forceinline__ uint64_t block_sum(uint64_t v, uint64_t* wsum) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor((unsigned long long)v, d, 64);
-    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t s = 0;
-    for (uint32_t w = 0; w < blockDim.x / 64; ++w) s += wsum[w];
-    __syncthreads();
-    return s;
-}
-
-// exclusive prefix of v over the workgroup's threads (thread order); *total receives the sum
-__device__ __forceinline__ uint64_t block_exclusive(uint64_t v, uint64_t* wsum, uint64_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = (uint64_t)__shfl_up((unsigned long long)incl, d, 64);
-        if ((int)lane >= d) incl += o;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (uint32_t w = 0; w < blockDim.x / 64; ++w) { const uint64_t x = wsum[w]; if (w < wave) before += x; all += x; }
-    __syncthreads();
-    *total = all;
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(kLenThreads) void k_len_tile_sum(const uint32_t* __restrict__ len, const uint32_t* __restrict__ perm, uint64_t n,
                                                               uint64_t* __restrict__ tile_sum) {
     __shared__ uint64_t wsum[kLenThreads / 64];
@@ -263,32 +213,17 @@ __global__ __launch_bounds__(256) void k_piece_bounds(const uint64_t* __restrict
 }
 
 // ---- K9c -----------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kGatherThreads = 256, kGatherGroup = 16, kGatherRecs = kGatherThreads / kGatherGroup;
-struct __attribute__((packed, aligned(1))) Bytes16 { uint32_t w[4]; };
+constexpr uint32_t kGatherThreads = 256, kGatherRecs = kGatherThreads / kCopyGroup;
 
 __global__ __launch_bounds__(kGatherThreads) void k_gather_records(const uint8_t* __restrict__ store, const uint64_t* __restrict__ off,
                                                                    const uint32_t* __restrict__ perm, const uint64_t* __restrict__ out_off,
                                                                    uint64_t r0, uint64_t r1, uint64_t p0, uint64_t p1, uint8_t* __restrict__ dst) {
-    const uint32_t l = threadIdx.x % kGatherGroup;
-    const uint64_t i = r0 + (uint64_t)blockIdx.x * kGatherRecs + threadIdx.x / kGatherGroup;
+    const uint64_t i = r0 + (uint64_t)blockIdx.x * kGatherRecs + threadIdx.x / kCopyGroup;
     if (i >= r1) return;
     const uint64_t o = out_off[i], e = out_off[i + 1];
     const uint64_t lo = o > p0 ? o : p0, hi = e < p1 ? e : p1;
     if (lo >= hi) return;
-    const uint8_t* s = store + off[perm[i]] + (lo - o);
-    uint8_t* d = dst + (lo - p0);
-    uint64_t nb = hi - lo;
-    const uint32_t head = (uint32_t)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u);
-    const uint32_t h = head < nb ? head : (uint32_t)nb;
-    if (l < h) d[l] = s[l];
-    s += h; d += h; nb -= h;
-    const uint64_t chunks = nb >> 4;
-    for (uint64_t c = l; c < chunks; c += kGatherGroup) {
-        const Bytes16 x = *(const Bytes16*)(s + 16 * c);
-        *(uint4*)(d + 16 * c) = uint4{x.w[0], x.w[1], x.w[2], x.w[3]};
-    }
-    const uint32_t tail = (uint32_t)(nb & 15u);
-    if (l < tail) d[16 * chunks + l] = s[16 * chunks + l];
+    copy_span16(dst + (lo - p0), store + off[perm[i]] + (lo - o), hi - lo, threadIdx.x % kCopyGroup);
 }
 
 }  // namespace

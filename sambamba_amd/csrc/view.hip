@@ -6,11 +6,11 @@
 //                        the first region that ends behind pos -- the only one the record can overlap first --, for listed regions a
 //                        loop over the list (wave-uniform addresses) that counts the regions the record overlaps.  The lane's
 //                        number of entries (0, 1, or one per overlapped region) is stored; the entries and the selected records of a
-//                        workgroup are summed (shuffles inside a wave, LDS across the waves) so that two exclusive scans
+//                        workgroup are summed (block_sum, block_rank_of_kept: wave_prims.hpp) so that two exclusive scans
 //                        (launch_count_scan) give every workgroup its first output slots -- the file-order-preserving compaction
 //                        of K9a.  For -c nothing is stored: one atomicAdd per wave into the file's counter.
-//   K12b k_view_emit     the same lanes again: a selected record's ordinal is the workgroup's base + the selected lanes in front of
-//                        it (ballot + popcount, waves through LDS), its first entry the base + an exclusive prefix of the counts.
+//   K12b k_view_emit     the same lanes again: a selected record's ordinal is the workgroup's base + the selected threads in front
+//                        of it (block_rank_of_kept), its first entry the base + an exclusive prefix of the counts (block_exclusive).
 //                        Store offset and length are written once per record; for listed regions the list is walked again and
 //                        (region index, record ordinal) written per overlapped region, in listed order.
 //   k_view_compose       perm[i] = entry_rec[order[i]]: the sorted entries (K9b over the region index) as record ordinals, the form
@@ -22,12 +22,11 @@
 #include "common.hpp"
 #include "view.hpp"
 #include "view_core.hpp"
+#include "wave_prims.hpp"
 
 namespace sbx {
 
 namespace {
-
-__device__ __forceinline__ uint64_t view_lanemask_lt() { return (1ull << (threadIdx.x & 63u)) - 1ull; }
 
 // is the record (ref, pos, covered) in the merged list?  g = the first region, in (ref, start) order, with (ref, end) > (ref, pos):
 // every region in front of it ends at or before pos, every region behind it starts later than g does.
@@ -60,7 +59,6 @@ __device__ __forceinline__ bool passes_filters(const ViewSelectArgs& a, const Re
 
 __global__ __launch_bounds__(kViewThreads) void k_view_select(ViewSelectArgs a) {
     __shared__ uint32_t w_entries[kViewThreads / 64], w_records[kViewThreads / 64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t i = (uint64_t)blockIdx.x * kViewThreads + threadIdx.x;
     uint32_t cnt = 0;
     bool bad = false;
@@ -86,68 +84,48 @@ __global__ __launch_bounds__(kViewThreads) void k_view_select(ViewSelectArgs a) 
     }
     uint32_t len = 0;
     if (cnt && a.with_lengths) {
-        uint32_t bs;
-        __builtin_memcpy(&bs, a.U + rec_off, 4);              // block_size (records start at any byte)
+        const uint32_t bs = ld32(a.U + rec_off);              // block_size
         len = bs + 4u;
-        if (bs < 32u || bs > 0x7FFFFFF0u || rec_off + len > a.u_end) { bad = true; cnt = 0; len = 0; }
+        if (!record_len_ok(bs, rec_off, a.u_end)) { bad = true; cnt = 0; len = 0; }
     }
     if (a.count && i < a.n) a.count[i] = cnt;
     // the wave's share
-    unsigned long long entries = cnt, bytes = (unsigned long long)cnt * len;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        entries += __shfl_xor(entries, d, 64);
-        bytes += __shfl_xor(bytes, d, 64);
-    }
+    const unsigned long long entries = wave_sum<unsigned long long>(cnt), bytes = wave_sum((unsigned long long)cnt * len);
     const unsigned long long m = __ballot(cnt != 0), mb = __ballot(bad);
-    if (lane == 0) {
+    if ((threadIdx.x & 63u) == 0) {
         if (m) {
             atomicAdd(a.acc + kViewAccEntries, entries);
             atomicAdd(a.acc + kViewAccRecords, (unsigned long long)__popcll(m));
             if (bytes) atomicAdd(a.acc + kViewAccBytes, bytes);
         }
         if (mb) atomicAdd(a.acc + kViewAccBad, (unsigned long long)__popcll(mb));
-        w_entries[wave] = (uint32_t)entries;
-        w_records[wave] = (uint32_t)__popcll(m);
     }
     if (!a.group_entries) return;                              // (uniform: -c)
-    __syncthreads();
+    // the workgroup's share: what the two scans of the host turn into the first output slots of K12b
+    uint32_t records;
+    block_rank_of_kept(cnt != 0, w_records, &records);
+    const uint32_t all = block_sum(cnt, w_entries);
     if (threadIdx.x == 0) {
-        uint32_t e = 0, r = 0;
-        for (uint32_t w = 0; w < kViewThreads / 64; ++w) { e += w_entries[w]; r += w_records[w]; }
-        a.group_entries[blockIdx.x] = e;
-        a.group_records[blockIdx.x] = r;
+        a.group_entries[blockIdx.x] = all;
+        a.group_records[blockIdx.x] = records;
     }
 }
 
 __global__ __launch_bounds__(kViewThreads) void k_view_emit(ViewEmitArgs a) {
     __shared__ uint32_t w_entries[kViewThreads / 64], w_records[kViewThreads / 64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t i = (uint64_t)blockIdx.x * kViewThreads + threadIdx.x;
-    const bool live = i < a.s.n;
-    const uint32_t cnt = live ? a.s.count[i] : 0u;
-    // entries of the lanes in front, inside the wave
-    uint32_t incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        if ((int)lane >= d) incl += o;
-    }
-    const unsigned long long m = __ballot(cnt != 0);
-    if (lane == 63) w_entries[wave] = incl;
-    if (lane == 0) w_records[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t e_before = 0, r_before = 0;
-    for (uint32_t w = 0; w < wave; ++w) { e_before += w_entries[w]; r_before += w_records[w]; }
+    const uint32_t cnt = i < a.s.n ? a.s.count[i] : 0u;
+    // the selected records and the entries of the threads in front, inside the workgroup
+    uint32_t all;
+    const uint32_t e_before = block_exclusive(cnt, w_entries, &all);
+    const uint32_t r_before = block_rank_of_kept(cnt != 0, w_records);
     if (!cnt) return;
     const RecDesc d = a.s.desc[i];
-    const uint64_t ord = a.record_base + a.group_record_base[blockIdx.x] + r_before + (uint32_t)__popcll(m & view_lanemask_lt());
-    uint32_t bs;
-    __builtin_memcpy(&bs, a.s.U + d.rec_off, 4);               // (checked by K12a: a record that fails has no entries)
+    const uint64_t ord = a.record_base + a.group_record_base[blockIdx.x] + r_before;
     a.off[ord] = (uint64_t)((int64_t)d.rec_off + a.store_delta);
-    a.len[ord] = bs + 4u;
+    a.len[ord] = ld32(a.s.U + d.rec_off) + 4u;                 // (checked by K12a: a record that fails has no entries)
     if (!a.entry_key) return;
-    uint64_t at = a.entry_base + a.group_entry_base[blockIdx.x] + e_before + (incl - cnt);
+    uint64_t at = a.entry_base + a.group_entry_base[blockIdx.x] + e_before;
     const int32_t ref = a.s.rec_ref[i];
     const uint32_t covered = (uint32_t)(d.end - d.pos);
     uint32_t left = cnt;
