@@ -116,10 +116,11 @@ inline void sort_resident(uint64_t* d_key, uint64_t n, uint64_t varying, hipStre
 }
 
 // ---- the writer ----
-constexpr uint64_t kPieceCap = kBgzfPieceBlocks * (uint64_t)kBgzfPayload;
 struct OutputPlan {
     uint64_t total = 0;             // bytes of the stream: header + records
-    std::vector<uint32_t> bounds;   // the first record that ends behind byte k * kPieceCap
+    uint64_t piece_blocks = 0;      // BGZF payloads per piece (bgzf_piece_blocks(), read once for the call)
+    std::vector<uint32_t> bounds;   // the first record that ends behind byte k * piece_bytes()
+    uint64_t piece_bytes() const { return piece_blocks * (uint64_t)kBgzfPayload; }
 };
 // Offsets of the records d_perm[0, n) in the output stream (d_out_off[0, n], n + 2 words) and the records at the piece boundaries.
 // *ms_gather += device time of the offsets.
@@ -127,6 +128,7 @@ inline OutputPlan plan_output(const uint32_t* d_len, const uint32_t* d_perm, uin
                               double* ms_gather) {
     OutputPlan p;
     p.total = hlen;
+    p.piece_blocks = bgzf_piece_blocks();
     EventTimer t;
     DevBuf<uint64_t> d_tile_sum(len_tiles(n) + 2);
     t.start(s);
@@ -135,11 +137,12 @@ inline OutputPlan plan_output(const uint32_t* d_len, const uint32_t* d_perm, uin
     if (n) SBX_HIP(hipMemcpyAsync(&p.total, d_out_off + n, 8, hipMemcpyDeviceToHost, s));
     SBX_HIP(hipStreamSynchronize(s));
     if (n) *ms_gather += t.ms();                        // (the offsets are the gather's preparation)
-    const uint32_t n_bounds = (uint32_t)((p.total + kPieceCap - 1) / kPieceCap) + 1;
+    const uint64_t cap = p.piece_bytes();
+    const uint32_t n_bounds = (uint32_t)((p.total + cap - 1) / cap) + 1;
     p.bounds.assign(n_bounds, (uint32_t)n);
     if (n) {
         DevBuf<uint32_t> d_bounds(n_bounds);
-        launch_piece_bounds(d_out_off, n, kPieceCap, n_bounds, d_bounds.p, s);
+        launch_piece_bounds(d_out_off, n, cap, n_bounds, d_bounds.p, s);
         SBX_HIP(hipMemcpyAsync(p.bounds.data(), d_bounds.p, (size_t)n_bounds * 4, hipMemcpyDeviceToHost, s));
         SBX_HIP(hipStreamSynchronize(s));
     }
@@ -158,16 +161,17 @@ inline void write_permuted_bam(OutputGuard& out, const std::vector<uint8_t>& hea
     bool ok = true;
     EventTimer t_gather;
     try {
-        bgzf_compress_pieces((size_t)plan.total, level, true, false, bt_times,
+        bgzf_compress_pieces((size_t)plan.total, (size_t)plan.piece_blocks, level, true, false, bt_times,
                              [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
                                  const uint64_t p0 = done, p1 = done + bytes;
-                                 const size_t k = (size_t)(p0 / kPieceCap);
+                                 const size_t k = (size_t)(p0 / plan.piece_bytes());
                                  t_gather.start(ps);
                                  if (p0 < hlen) {
                                      const uint64_t he = std::min<uint64_t>(hlen, p1);
                                      SBX_HIP(hipMemcpyAsync(d_in, header.data() + p0, he - p0, hipMemcpyHostToDevice, ps));
                                  }
-                                 const uint64_t r0 = plan.bounds[k], r1 = std::min<uint64_t>(n, (uint64_t)plan.bounds[k + 1] + 1);
+                                 uint64_t r0, r1;
+                                 sortc::piece_records(plan.bounds.data(), k, n, &r0, &r1);
                                  launch_gather_records(d_store, d_off, d_perm, d_out_off, r0, r1, p0, p1, d_in, ps);
                                  t_gather.stop(ps);
                                  *ms_gather += t_gather.ms();
@@ -203,6 +207,9 @@ inline WrittenBam write_store_output(OutputGuard& out, const std::vector<uint8_t
     w.stream_bytes = plan.total;
     w.compressed_bytes = bt_times.out_bytes + 28;
     w.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+    if (getenv("SBX_TIMING"))
+        fprintf(stderr, "[sbx] output: stream_bytes=%llu compressed_bytes=%llu n_pieces=%u piece_blocks=%llu\n", (unsigned long long)w.stream_bytes,
+                (unsigned long long)w.compressed_bytes, bt_times.n_pieces, (unsigned long long)plan.piece_blocks);
     return w;
 }
 

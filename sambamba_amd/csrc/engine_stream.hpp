@@ -15,19 +15,32 @@ constexpr uint8_t kEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 
 
 constexpr size_t kBgzfPieceBlocks = 32768;      // BGZF blocks compressed per launch: a piece of the stream is at most this many payloads
 
-struct BgzfPieceTimes { double ms_fill = 0, ms_deflate = 0, ms_pack = 0, ms_d2h = 0; uint64_t out_bytes = 0; };
+// BGZF blocks per piece for one call: kBgzfPieceBlocks, or SBX_BGZF_PIECE_BLOCKS (tests: a decimal number, brought into
+// [1, kBgzfPieceBlocks]; anything else counts as unset).  Blocks are cut every kBgzfPayload bytes whatever the piece, so the value
+// does not change a byte of the output.  Read once per call: the caller hands the value to everything that depends on it.
+inline size_t bgzf_piece_blocks() {
+    const char* e = getenv("SBX_BGZF_PIECE_BLOCKS");
+    if (!e || *e < '0' || *e > '9') return kBgzfPieceBlocks;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (*end) return kBgzfPieceBlocks;
+    return (size_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 1), kBgzfPieceBlocks);
+}
 
-// Compresses a stream of n bytes piece by piece on the device.  fill(d_in, done, bytes, s) puts bytes [done, done + bytes) of the stream
-// at d_in, in order on stream s; sink(data, len) receives consecutive pieces of the BGZF stream.  Blocks are cut every kBgzfPayload
-// bytes.  pinned: the compressed piece travels through pinned host memory.  times (may be null) accumulates; the wall-clock figures
-// (fill, device -> host) are taken only when `timing`, which synchronises after the fill.
+struct BgzfPieceTimes { double ms_fill = 0, ms_deflate = 0, ms_pack = 0, ms_d2h = 0; uint64_t out_bytes = 0; uint32_t n_pieces = 0; };
+
+// Compresses a stream of n bytes piece by piece on the device: pieces of piece_blocks (bgzf_piece_blocks()) payloads, the last one
+// shorter.  fill(d_in, done, bytes, s) puts bytes [done, done + bytes) of the stream at d_in, in order on stream s; sink(data, len)
+// receives consecutive pieces of the BGZF stream.  Blocks are cut every kBgzfPayload bytes.  pinned: the compressed piece travels
+// through pinned host memory.  times (may be null) accumulates; the wall-clock figures (fill, device -> host) are taken only when
+// `timing`, which synchronises after the fill.
 template <class Fill, class Sink>
-void bgzf_compress_pieces(size_t n, int level, bool pinned, bool timing, BgzfPieceTimes* times, Fill&& fill, Sink&& sink) {
+void bgzf_compress_pieces(size_t n, size_t piece_blocks, int level, bool pinned, bool timing, BgzfPieceTimes* times, Fill&& fill, Sink&& sink) {
     Stream stream;
     stream.create();
     hipStream_t s = stream.get();
     const size_t n_blocks_total = (n + kBgzfPayload - 1) / kBgzfPayload;
-    const uint32_t cap_blocks = (uint32_t)std::min<size_t>(kBgzfPieceBlocks, std::max<size_t>(1, n_blocks_total));
+    const uint32_t cap_blocks = (uint32_t)std::min<size_t>(piece_blocks, std::max<size_t>(1, n_blocks_total));
     DevBuf<uint8_t> d_in((size_t)cap_blocks * kBgzfPayload + 64), d_slots((size_t)cap_blocks * kBgzfSlot), d_out((size_t)cap_blocks * kBgzfSlot);
     DevBuf<uint16_t> d_tab(deflate_table_entries(cap_blocks));
     DevBuf<uint8_t> d_work(deflate_work_bytes(cap_blocks));
@@ -59,7 +72,7 @@ void bgzf_compress_pieces(size_t n, int level, bool pinned, bool timing, BgzfPie
         else { host.resize((size_t)total); h = host.data(); }
         SBX_HIP(hipMemcpy(h, d_out.p, (size_t)total, hipMemcpyDeviceToHost));
         if (times) {
-            times->ms_deflate += t_def.ms(); times->ms_pack += t_pack.ms(); times->out_bytes += total;
+            times->ms_deflate += t_def.ms(); times->ms_pack += t_pack.ms(); times->out_bytes += total; ++times->n_pieces;
             if (timing) { times->ms_fill += (w1 - w0) * 1e3; times->ms_d2h += (wall_now() - w2) * 1e3; }
         }
         sink(h, (size_t)total);
@@ -72,14 +85,14 @@ template <class Sink>
 void bgzf_compress_stream(const uint8_t* in, size_t n, int level, Sink&& sink) {
     const bool timing = getenv("SBX_TIMING") != nullptr;
     BgzfPieceTimes t;
-    bgzf_compress_pieces(n, level, false, timing, &t,
+    bgzf_compress_pieces(n, bgzf_piece_blocks(), level, false, timing, &t,
                          [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t s) {
                              SBX_HIP(hipMemcpyAsync(d_in, in + done, bytes, hipMemcpyHostToDevice, s));
                          },
                          sink);
     if (timing)
-        fprintf(stderr, "[sbx] bgzf_compress: %zu bytes -> %llu in %zu blocks: host -> device %.1f ms (pageable), deflate kernel %.1f ms (%.1f GB/s of input), "
-                        "scan + pack %.1f ms, device -> host %.1f ms\n", n, (unsigned long long)t.out_bytes, (n + kBgzfPayload - 1) / kBgzfPayload,
+        fprintf(stderr, "[sbx] bgzf_compress: %zu bytes -> %llu in %zu blocks, %u pieces: host -> device %.1f ms (pageable), deflate kernel %.1f ms (%.1f GB/s of input), "
+                        "scan + pack %.1f ms, device -> host %.1f ms\n", n, (unsigned long long)t.out_bytes, (n + kBgzfPayload - 1) / kBgzfPayload, t.n_pieces,
                 t.ms_fill, t.ms_deflate, t.ms_deflate > 0 ? (double)n / t.ms_deflate / 1e6 : 0.0, t.ms_pack, t.ms_d2h);
 }
 

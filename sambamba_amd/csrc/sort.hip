@@ -203,13 +203,7 @@ __global__ __launch_bounds__(256) void k_piece_bounds(const uint64_t* __restrict
                                                       uint32_t* __restrict__ rec) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n_bounds) return;
-    const uint64_t target = (uint64_t)k * piece_bytes;
-    uint64_t lo = 0, hi = n;                    // the first i with out_off[i + 1] > target
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (out_off[mid + 1] > target) hi = mid; else lo = mid + 1;
-    }
-    rec[k] = (uint32_t)lo;
+    rec[k] = (uint32_t)sortc::first_record_ending_behind(out_off, n, (uint64_t)k * piece_bytes);
 }
 
 // ---- K9c -----------------------------------------------------------------------------------------------------------------
@@ -220,10 +214,9 @@ __global__ __launch_bounds__(kGatherThreads) void k_gather_records(const uint8_t
                                                                    uint64_t r0, uint64_t r1, uint64_t p0, uint64_t p1, uint8_t* __restrict__ dst) {
     const uint64_t i = r0 + (uint64_t)blockIdx.x * kGatherRecs + threadIdx.x / kCopyGroup;
     if (i >= r1) return;
-    const uint64_t o = out_off[i], e = out_off[i + 1];
-    const uint64_t lo = o > p0 ? o : p0, hi = e < p1 ? e : p1;
-    if (lo >= hi) return;
-    copy_span16(dst + (lo - p0), store + off[perm[i]] + (lo - o), hi - lo, threadIdx.x % kCopyGroup);
+    sortc::PieceClip c;
+    if (!sortc::clip_to_piece(out_off[i], out_off[i + 1], p0, p1, &c)) return;
+    copy_span16(dst + c.dst, store + off[perm[i]] + c.src, c.len, threadIdx.x % kCopyGroup);
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 // sort_core.hpp -- what `sambamba sort` (coordinate order) needs besides the kernels: the 64-bit sort key of a record, the digits a
-// radix sort has to look at, and the header text of the output.  The key functions are `__host__ __device__` (K9a, sort.hip, packs the
-// key with the very statement the CPU test checks: tests/native/sort_host.cpp); the header text is host code.
+// radix sort has to look at, the arithmetic of the pieces the output stream is produced in, and the header text of the output.  The
+// key and piece functions are `__host__ __device__` (K9a, k_piece_bounds and K9c of sort.hip run the very statements the CPU test
+// checks: tests/native/sort_host.cpp); the header text is host code.
 //
 // Order (compareCoordinatesAndStrand, BioD bio/std/hts/bam/read.d:1632-1642, applied by a stable merge sort): ref_id -1 last, ascending
 // ref_id, ascending position as a signed number, forward strand in front of reverse strand, ties in file order.  Records with ref_id -1
@@ -57,6 +58,42 @@ SBX_SORT_HD uint32_t plan_passes(uint64_t varying, uint32_t* shift, uint32_t* bi
     for (uint32_t s = lo; s < hi; s += kDigitBits)
         if ((varying >> s) & ((1u << kDigitBits) - 1)) shift[n++] = s;
     return n;
+}
+
+// ---- the pieces of the output stream (engine_store.hpp; k_piece_bounds and K9c, sort.hip) ----
+// The stream is header + records; record i holds the bytes [out_off[i], out_off[i + 1]) of it, out_off[n] is its length.  It is
+// produced in pieces [k * cap, min((k + 1) * cap, total)).
+
+// the first i in [0, n) with out_off[i + 1] > target, n when there is none: the record that holds byte `target` of the stream, or
+// the first record when `target` lies in the header
+SBX_SORT_HD uint64_t first_record_ending_behind(const uint64_t* out_off, uint64_t n, uint64_t target) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (out_off[mid + 1] > target) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// The records a piece has bytes of: bounds[k] = first_record_ending_behind(k * cap), for every k up to and including the one behind
+// the last piece.  Piece k takes [r0, r1): from the record that holds its first byte to the one that holds the first byte of the
+// next piece -- which starts there, and has nothing in this piece, when the boundary is a record's edge (clip_to_piece says so).
+SBX_SORT_HD void piece_records(const uint32_t* bounds, size_t k, uint64_t n, uint64_t* r0, uint64_t* r1) {
+    *r0 = bounds[k];
+    const uint64_t e = (uint64_t)bounds[k + 1] + 1;
+    *r1 = e < n ? e : n;
+}
+
+// What the piece [p0, p1) holds of a record at [o, e) of the stream: `len` bytes from byte `src` of the record to byte `dst` of the
+// piece; false when it holds none.
+struct PieceClip { uint64_t dst, src, len; };
+SBX_SORT_HD bool clip_to_piece(uint64_t o, uint64_t e, uint64_t p0, uint64_t p1, PieceClip* c) {
+    const uint64_t lo = o > p0 ? o : p0, hi = e < p1 ? e : p1;
+    if (lo >= hi) return false;
+    c->dst = lo - p0;
+    c->src = lo - o;
+    c->len = hi - lo;
+    return true;
 }
 
 }  // namespace sortc

@@ -78,7 +78,8 @@ def test_levels_trade_work_for_bytes():
 
 
 def test_many_blocks_in_several_pieces():
-    """More blocks than one launch piece holds is out of reach of a unit test; several thousand blocks exercise the scan + pack."""
+    """Several thousand blocks in one call exercise the scan + pack; they fit one piece of 32768 blocks.  Streams of several pieces
+    are tests/test_gpu_pieces.py."""
     data = bam_like(40_000_000, 21)
     comp = sambamba_amd.bgzf_compress(data, with_eof=False)
     assert gzip.decompress(comp) == data

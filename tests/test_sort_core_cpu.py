@@ -1,9 +1,13 @@
 """What `sambamba sort` needs besides its kernels (sambamba_amd/csrc/sort_core.hpp), compiled for the host with g++ into
 tests/native/sort_host.cpp and checked against the Python restatement (tests/sort_ref.py): the 64-bit key K9a packs orders records
 exactly as compareCoordinatesAndStrand does, the bits and passes the radix sort is told to look at cover every key, and the
-header text of the output is the re-serialisation SamHeader.toSam prints -- no GPU needed."""
+header text of the output is the re-serialisation SamHeader.toSam prints, and the piece arithmetic of the output tail (the bounds of
+k_piece_bounds, the record range of a piece, the clip of K9c) puts every byte of the stream into exactly one place of exactly one
+piece -- no GPU needed."""
+import bisect
 import itertools
 import os
+import random
 import struct
 import subprocess
 
@@ -80,6 +84,60 @@ def test_passes_skip_constant_digits(host):
     varying = 0x1FE | (0x3 << 33)
     out = [int(x) for x in run(host, ["passes", varying]).stdout.split()]
     assert out == [2, 34, 1, 33]
+
+
+# ---- the pieces of the output stream ------------------------------------------------------------------------------------------------
+PIECE_BLOCK = 64               # a "BGZF payload" small enough to enumerate: the cap is a parameter of the functions under test
+
+
+def _piece_cases(cap):
+    """name -> (header length, record lengths); the boundaries are at the multiples of cap."""
+    rng = random.Random(cap)
+    cases = {}
+    for seed in range(4):
+        cases["random%d" % seed] = (rng.randrange(0, 3 * cap), [rng.randrange(36, 201) for _ in range(rng.randrange(1, 80))])
+    # every record 64 bytes behind a header of a multiple of 64: every boundary is a record's edge; one byte more: none is
+    cases["boundary_on_record_edges"] = (cap, [PIECE_BLOCK] * 13)
+    cases["boundary_one_byte_into_records"] = (cap + 1, [PIECE_BLOCK] * 13)
+    cases["boundary_one_byte_before_the_edge"] = (cap - 1, [PIECE_BLOCK] * 13)
+    cases["record_longer_than_two_pieces"] = (17, [40, 2 * cap + 100, 50, 3 * cap, 36])
+    cases["record_is_exactly_a_piece"] = (cap, [cap, 2 * cap, 36])
+    cases["header_longer_than_a_piece"] = (cap + 37, [40, 50, 60])
+    cases["header_of_two_whole_pieces"] = (2 * cap, [40, 50, 60])
+    cases["no_records"] = (2 * cap + 5, [])
+    cases["no_records_header_is_one_piece"] = (cap, [])
+    cases["nothing_at_all"] = (0, [])
+    lens = [rng.randrange(36, 201) for _ in range(20)]
+    hlen = 29
+    lens.append(5 * cap - (hlen + sum(lens)) % cap if (hlen + sum(lens)) % cap else 4 * cap)
+    assert (hlen + sum(lens)) % cap == 0
+    cases["total_is_a_multiple_of_the_cap"] = (hlen, lens)
+    return cases
+
+
+@pytest.mark.parametrize("blocks", [1, 2, 3])
+def test_pieces_hold_every_byte_of_the_stream_once(host, blocks):
+    cap = blocks * PIECE_BLOCK
+    for name, (hlen, lens) in _piece_cases(cap).items():
+        r = run(host, ["pieces", hlen, cap], " ".join(map(str, lens)).encode())
+        assert r.returncode == 0, (name, r.stderr)
+        want = bytes(0x80 | (j % 127) for j in range(hlen)) + b"".join(bytes((i * 131 + j * 7 + 3) % 127 for j in range(l)) for i, l in enumerate(lens))
+        total, n = len(want), len(lens)
+        # the concatenation of the pieces is header + records
+        assert r.stdout == want, name
+        lines = r.stderr.decode().splitlines()
+        pieces = [[int(x) for x in ln.split()[1:]] for ln in lines if ln.startswith("piece ")]
+        assert len(pieces) == (total + cap - 1) // cap, name
+        for k, (kk, p0, p1, r0, r1, unwritten, twice, outside) in enumerate(pieces):
+            assert (kk, p0, p1) == (k, k * cap, min(total, (k + 1) * cap)), name
+            # every byte of the piece written exactly once, none outside [0, p1 - p0)
+            assert (unwritten, twice, outside) == (0, 0, 0), (name, k)
+            assert 0 <= r0 <= r1 <= n, (name, k)
+        # the bounds are what their definition says: the first record that ends behind byte k * cap, n when none does
+        ends = list(itertools.accumulate(lens, initial=hlen))[1:]
+        bounds = [int(x) for x in lines[0].split()[1:]]
+        assert lines[0].startswith("bounds") and bounds == [bisect.bisect_right(ends, k * cap) for k in range(len(pieces) + 1)], name
+        assert bounds[-1] == n
 
 
 def _bam_text(name):
