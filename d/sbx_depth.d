@@ -122,6 +122,9 @@ extern (C) nothrow @nogc {
     int sbx_view_bam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, const(sbx_view_opts)* opts, const(char*)* regions,
                      size_t n_regions, const(char)* bed_path, const(char)* pg_command_line, int level, int with_index, int device,
                      sbx_view_stats* stats, char* err, size_t errlen);
+    int sbx_view_sam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, const(sbx_view_opts)* opts, const(char*)* regions,
+                     size_t n_regions, const(char)* bed_path, const(char)* pg_command_line, int with_header, int device,
+                     sbx_view_stats* stats, char* err, size_t errlen);
     int sbx_view_num_filter(const(char)* text, ushort* flags_set, ushort* flags_unset);
     int sbx_view_reference_info(sbx_ctx*, char* out_, size_t cap, size_t* out_len);
     int sbx_inflate_blocks(const(ubyte)* comp, const(ulong)* comp_off, const(uint)* comp_len, const(uint)* isize,

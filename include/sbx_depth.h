@@ -321,6 +321,17 @@ int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view
 int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
                  size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device,
                  sbx_view_stats* stats, char* err, size_t errlen);
+/* -f sam, the reference's default: one line per entry (BamRead.toSam, BioD bio/std/hts/bam/read.d:695-760; tags as TagValue.toSam,
+ * floats as C's "%g" of the value widened to double), in the order sbx_view_bam writes the entries, formatted on the device (K13).
+ * with_header != 0 (-h): the header text of sbx_view_bam comes first, with its @PG line, no blank line added; 0: no header.
+ * out_path NULL or "-": stdout.  A selected record the reference dies on with a range error -- ref_id or mate_ref_id outside
+ * [-1, n_ref), a tag of unknown type, a tag value that runs past the record, a Z / H without NUL -- is counted and the call
+ * fails with SBX_EFORMAT before a byte is written; a record that is not selected is not looked at.  The file is resident as for
+ * sbx_view_bam (SBX_ENOMEM when it does not fit); an out_path that is the input is SBX_EINVAL; on failure no output file is left.
+ * stats: stream_bytes = bytes of record text (header excluded), compressed_bytes = 0, ms_deflate = 0, ms_gather = K13a + K13b. */
+int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
+                 size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device,
+                 sbx_view_stats* stats, char* err, size_t errlen);
 /* "i1/i2" of --num-filter (view.d:271-277; host only): either number may be missing ("4/", "/4", "3", ""), each is an unsigned
  * 16-bit decimal; anything else is SBX_EINVAL. */
 int sbx_view_num_filter(const char* text, uint16_t* flags_set, uint16_t* flags_unset);

@@ -12,6 +12,7 @@ _SORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sort")
 _MARKDUP_CLI_PATH = os.path.join(HERE, "csrc", "sbx-markdup")
 _MERGE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-merge")
 _VIEW_CLI_PATH = os.path.join(HERE, "csrc", "sbx-view")
+_SAM_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sam")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -122,7 +123,7 @@ EXPORTS = [
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
     "sbx_sort_bam", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
-    "sbx_view_count", "sbx_view_bam", "sbx_view_num_filter", "sbx_view_reference_info",
+    "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_num_filter", "sbx_view_reference_info",
 ]
 
 _lib = None
@@ -154,6 +155,10 @@ def merge_cli_path():
 
 def view_cli_path():
     return _VIEW_CLI_PATH
+
+
+def sam_cli_path():
+    return _SAM_CLI_PATH
 
 
 def lib():
@@ -223,6 +228,8 @@ def lib():
                                  C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
     L.sbx_view_bam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.POINTER(ViewOpts), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_char_p,
                                C.c_int, C.c_int, C.c_int, C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
+    L.sbx_view_sam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.POINTER(ViewOpts), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_char_p,
+                               C.c_int, C.c_int, C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
     L.sbx_view_num_filter.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
     L.sbx_view_reference_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -646,13 +653,18 @@ def view_num_filter(text):
 
 
 def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, regions=(), bed=None, subsample=None, seed=None, level=-1,
-         index=False, command_line=None, device=-1):
-    """sbx_view_count / sbx_view_bam (`sambamba view -c` / `-f bam`): the records of in_path that pass the -F query string `filter`,
+         index=False, command_line=None, device=-1, format="bam", with_header=False):
+    """sbx_view_count / sbx_view_bam / sbx_view_sam (`sambamba view -c` / `-f bam` / `-f sam`): the records of in_path that pass the -F query string `filter`,
     `num_filter` ("i1/i2"), the subsampling (`subsample` = fraction, `seed` = 64-bit seed, drawn at random when None) and overlap
     `regions` ("chr", "chr:beg-end", "*": once per listed region, in listed order) or the BED file `bed` (once, in file order).
     count=True returns their number; otherwise they are written to out_path ("-": stdout) as a BAM -- index=True also writes
     out_path + ".bai", command_line is the CL field of the @PG line that is added (None: no @PG) -- and the fields of sbx_view_stats
-    come back as a dict."""
+    come back as a dict.  format="sam" writes SAM text instead, formatted on the device: one line per record, after the header text
+    when with_header (`view -h`); level and index do not apply to it (ValueError)."""
+    if format not in ("bam", "sam"):
+        raise ValueError("view: format must be 'bam' or 'sam'")
+    if format == "sam" and (level != -1 or index):
+        raise ValueError("view: level and index do not apply to format='sam'")
     L = lib()
     f = compile_filter(filter) if filter else None
     o = ViewOpts()
@@ -675,8 +687,13 @@ def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, r
         return int(n.value)
     if out_path is None:
         raise ValueError("view: out_path is required unless count=True ('-' writes to stdout)")
-    rc = L.sbx_view_bam(in_path.encode(), out_path.encode(), fp, C.byref(o), arr, len(regions), bedp,
-                        command_line.encode() if command_line is not None else None, int(level), int(index), device, C.byref(st), err, 512)
+    cl = command_line.encode() if command_line is not None else None
+    if format == "sam":
+        rc = L.sbx_view_sam(in_path.encode(), out_path.encode(), fp, C.byref(o), arr, len(regions), bedp, cl, int(bool(with_header)), device,
+                            C.byref(st), err, 512)
+    else:
+        rc = L.sbx_view_bam(in_path.encode(), out_path.encode(), fp, C.byref(o), arr, len(regions), bedp, cl, int(level), int(index), device,
+                            C.byref(st), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
     return {k: getattr(st, k) for k, _ in ViewStats._fields_ if k != "reserved"}

@@ -1,4 +1,4 @@
-// engine_view.cpp -- sbx_view_count / sbx_view_bam: the record selection of `sambamba view` (sambamba/view.d) on the device.
+// engine_view.cpp -- sbx_view_count / sbx_view_bam / sbx_view_sam: the record selection of `sambamba view` (sambamba/view.d) on the device.
 //
 // One index-mode pass over the input (for_each_record_batch: K1 + K2 per batch, K2 leaving the verdict of -F in RecDesc::pad); per
 // batch K12a (view.hip) decides, for every record, how many times it is selected.  -c adds that up and stores nothing, so it streams
@@ -8,9 +8,14 @@
 // and the result -- record ordinals, possibly the same one several times -- is the permutation plan_output / write_permuted_bam
 // read.  Those index d_len / d_off through the permutation and nowhere assume that it is a bijection.
 //
+// sbx_view_sam is a third sink over the same store and permutation: K13a (sam.hip) measures the line of every entry, a scan gives the
+// 64-bit offsets, and K13b writes the text piece by piece -- two device and two pinned buffers, so that the copy and the write of
+// a piece overlap the kernel of the next.
+//
 // The whole file is read whatever the regions say: restricting the read pass through the BAI work list is not built.
 #include "engine_store.hpp"
 #include "markdup_core.hpp"
+#include "sam.hpp"
 #include "view.hpp"
 #include "view_core.hpp"
 
@@ -93,6 +98,147 @@ void print_timing(const sbx_view_stats& st, const char* sink) {
             st.ms_total_wall);
 }
 
+// ---- what the BAM and the SAM sink share: the read pass and the order of the entries ----
+// The records of the file in the resident store and the selected entries in output order: entry i is record perm[i], len[perm[i]]
+// bytes at store + off[perm[i]].
+struct SelectedRecords {
+    DevBuf<uint8_t> store;
+    DevBuf<uint64_t> off;
+    DevBuf<uint32_t> len, perm;
+    uint64_t n = 0;                 // entries
+    unsigned long long record_bytes = 0;    // their record bytes, as K12a added them up
+    Stream stream;                  // what follows the read pass runs on it (declared last: it is waited for before the buffers go)
+};
+
+// Reads the file (K1, K2, K12a, K12b per batch; the records go to the store), closes the context and orders the entries (K9b over
+// the region index for listed regions).  hlen / per_record: bytes of the sink's header and of the per-record arrays it will add,
+// for the refusal of a file that does not fit.  Fills the counts and the times of the passes into *st.
+void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& sel, uint64_t hlen, uint64_t per_record,
+                     SelectedRecords* out, sbx_view_stats* st_out) {
+    sbx_view_stats& st = *st_out;
+    const bool listed = !sel.merged && !sel.list.empty();
+    DevBuf<uint8_t>& d_store = out->store;
+    DevBuf<uint64_t>& d_off = out->off;
+    DevBuf<uint32_t>& d_len = out->len;
+    DevBuf<uint32_t>& d_perm = out->perm;
+    Stream& stream = out->stream;
+    const StorePlan plan = plan_record_store(c.get(), hlen, per_record, "selecting records of");
+    const uint64_t u_first = plan.u_first;
+    hipStream_t s = c->stream.get();
+    d_store = DevBuf<uint8_t>((size_t)plan.store_bytes + 64);
+    DevBuf<sbx_region> d_regions;
+    upload_regions(sel, &d_regions, s);
+    DevBuf<uint64_t> d_entry_key, d_group_entry_base, d_group_record_base;
+    DevBuf<uint32_t> d_entry_rec, d_count, d_group_entries, d_group_records;
+    DevBuf<unsigned long long> d_acc(kViewAccWords);
+    SBX_HIP(hipMemsetAsync(d_acc.p, 0, kViewAccWords * sizeof(unsigned long long), s));
+    SBX_HIP(hipStreamSynchronize(s));
+
+    // ---- the read pass ----
+    EventTimer t_a, t_b;
+    uint64_t n_in = 0, n_rec = 0, n_ent = 0, cur = u_first;
+    uint32_t n_batches = 0;
+    bool too_many = false;
+    unsigned long long acc[kViewAccWords] = {0};
+    for_each_record_batch(c.get(), plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        const uint32_t groups = view_groups(nrec);
+        d_count.ensure((size_t)nrec + 2);
+        d_group_entries.ensure(groups + 4); d_group_records.ensure(groups + 4);
+        d_group_entry_base.ensure(groups + 4); d_group_record_base.ensure(groups + 4);
+        t_a.start(s);
+        copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
+        ViewSelectArgs a = select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p);
+        a.with_lengths = 1;
+        a.count = d_count.p; a.group_entries = d_group_entries.p; a.group_records = d_group_records.p;
+        launch_view_select(a, s);
+        if (nrec) {
+            launch_count_scan(d_group_entries.p, groups, d_group_entry_base.p, nullptr, 0, s);
+            launch_count_scan(d_group_records.p, groups, d_group_record_base.p, nullptr, 0, s);
+        }
+        t_a.stop(s);
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_select += t_a.ms();
+        n_in += nrec;
+        cur = next;
+        if (acc[kViewAccBad]) return false;
+        if (acc[kViewAccEntries] > 0xFFFFFFF0ull) { too_many = true; return false; }
+        // the arrays grow to what the batch selected, then K12b fills them
+        grow_keeping(d_off, (size_t)n_rec, (size_t)acc[kViewAccRecords] + 2, s);
+        grow_keeping(d_len, (size_t)n_rec, (size_t)acc[kViewAccRecords] + 2, s);
+        if (listed) {
+            grow_keeping(d_entry_key, (size_t)n_ent, (size_t)acc[kViewAccEntries] + 2, s);
+            grow_keeping(d_entry_rec, (size_t)n_ent, (size_t)acc[kViewAccEntries] + 2, s);
+        }
+        ViewEmitArgs b{};
+        b.s = a;
+        b.group_entry_base = d_group_entry_base.p; b.group_record_base = d_group_record_base.p;
+        b.store_delta = (int64_t)base - (int64_t)u_first;
+        b.record_base = n_rec; b.entry_base = n_ent;
+        b.off = d_off.p; b.len = d_len.p;
+        b.entry_key = listed ? d_entry_key.p : nullptr; b.entry_rec = listed ? d_entry_rec.p : nullptr;
+        t_b.start(s);
+        launch_view_emit(b, s);
+        t_b.stop(s);
+        // (the next batch's K1 / K2 overwrite U and the descriptors: K12b and the copy end first)
+        SBX_HIP(hipStreamSynchronize(s));
+        if (nrec) st.ms_emit += t_b.ms();
+        n_rec = acc[kViewAccRecords];
+        n_ent = acc[kViewAccEntries];
+        return true;
+    });
+    if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
+    if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 output records");
+    if (!listed && n_ent != n_rec) throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_ent) + " entries for " + std::to_string(n_rec) + " records");
+    const uint64_t u_total = plan.u_total;
+    c.reset();                                       // the batch buffers make room for the sort and the output pieces
+    d_count.release(); d_group_entries.release(); d_group_records.release(); d_group_entry_base.release(); d_group_record_base.release();
+
+    // ---- the order of the entries ----
+    stream.create();
+    s = stream.get();
+    const uint64_t n = n_ent;
+    d_perm = DevBuf<uint32_t>((size_t)n + 2);
+    ResidentOrder order;
+    if (listed && sel.list.size() > 1) {
+        // keys are region indices: what varies lies below the width of the largest one
+        const uint64_t varying = (1ull << sortc::bit_width64((uint64_t)sel.list.size() - 1)) - 1ull;
+        d_entry_key.ensure((size_t)n + 2);
+        sort_resident(d_entry_key.p, n, varying, s, &order);
+        EventTimer t_c;
+        t_c.start(s);
+        launch_view_compose(d_entry_rec.p, order.perm, n, d_perm.p, s);
+        t_c.stop(s);
+        SBX_HIP(hipStreamSynchronize(s));
+        st.ms_sort = order.ms_sort + (n ? t_c.ms() : 0.0);
+        st.n_sort_passes = order.n_passes;
+        order = ResidentOrder();
+    } else if (listed) {
+        if (n) SBX_HIP(hipMemcpyAsync(d_perm.p, d_entry_rec.p, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+        launch_iota(d_perm.p, n, s);
+    }
+    d_entry_key.release(); d_entry_rec.release();
+    d_len.ensure(2);                                 // (nothing selected: the arrays were never grown)
+    d_off.ensure(2);
+    out->n = n;
+    out->record_bytes = acc[kViewAccBytes];
+    st.n_records_in = n_in; st.n_records_selected = n_rec; st.n_entries_out = n;
+    st.inflated_bytes = u_total;
+    st.n_regions = sel.given(); st.n_batches = n_batches;
+}
+
+// Text bytes per piece of sbx_view_sam: 64 MiB (not tuned), or SBX_SAM_PIECE_BYTES (tests: a decimal number of at least 1; anything
+// else counts as unset).  Pieces are cut at line ends and written in order, so the value does not change a byte of the output.
+uint64_t sam_piece_bytes() {
+    constexpr uint64_t kDefault = 64ull << 20;
+    const char* e = getenv("SBX_SAM_PIECE_BYTES");
+    if (!e || *e < '0' || *e > '9') return kDefault;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    return *end || !v ? kDefault : (uint64_t)v;
+}
+
 }  // namespace
 
 extern "C" {
@@ -169,120 +315,21 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
         Standalone c = open_record_pass(in_path, device, filter, true);
         OutputGuard out_file(path, to_stdout);
         const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
-        const bool listed = !sel.merged && !sel.list.empty();
         std::string text, why;
         if (!mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why)) throw Error(SBX_EFORMAT, "SAM header: " + why);
         const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
         const uint64_t hlen = header.size();
 
-        const StorePlan plan = plan_record_store(c.get(), hlen, 48, "selecting records of");
-        const uint64_t u_first = plan.u_first;
-        hipStream_t s = c->stream.get();
-        DevBuf<uint8_t> d_store((size_t)plan.store_bytes + 64);
-        DevBuf<sbx_region> d_regions;
-        upload_regions(sel, &d_regions, s);
-        DevBuf<uint64_t> d_off, d_entry_key, d_group_entry_base, d_group_record_base;
-        DevBuf<uint32_t> d_len, d_entry_rec, d_count, d_group_entries, d_group_records;
-        DevBuf<unsigned long long> d_acc(kViewAccWords);
-        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kViewAccWords * sizeof(unsigned long long), s));
-        SBX_HIP(hipStreamSynchronize(s));
-
-        // ---- the read pass ----
         sbx_view_stats st{};
-        EventTimer t_a, t_b;
-        uint64_t n_in = 0, n_rec = 0, n_ent = 0, cur = u_first;
-        uint32_t n_batches = 0;
-        bool too_many = false;
-        unsigned long long acc[kViewAccWords] = {0};
-        for_each_record_batch(c.get(), plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-            const uint32_t groups = view_groups(nrec);
-            d_count.ensure((size_t)nrec + 2);
-            d_group_entries.ensure(groups + 4); d_group_records.ensure(groups + 4);
-            d_group_entry_base.ensure(groups + 4); d_group_record_base.ensure(groups + 4);
-            t_a.start(s);
-            copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
-            ViewSelectArgs a = select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p);
-            a.with_lengths = 1;
-            a.count = d_count.p; a.group_entries = d_group_entries.p; a.group_records = d_group_records.p;
-            launch_view_select(a, s);
-            if (nrec) {
-                launch_count_scan(d_group_entries.p, groups, d_group_entry_base.p, nullptr, 0, s);
-                launch_count_scan(d_group_records.p, groups, d_group_record_base.p, nullptr, 0, s);
-            }
-            t_a.stop(s);
-            SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipStreamSynchronize(s));
-            st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_select += t_a.ms();
-            n_in += nrec;
-            cur = next;
-            if (acc[kViewAccBad]) return false;
-            if (acc[kViewAccEntries] > 0xFFFFFFF0ull) { too_many = true; return false; }
-            // the arrays grow to what the batch selected, then K12b fills them
-            grow_keeping(d_off, (size_t)n_rec, (size_t)acc[kViewAccRecords] + 2, s);
-            grow_keeping(d_len, (size_t)n_rec, (size_t)acc[kViewAccRecords] + 2, s);
-            if (listed) {
-                grow_keeping(d_entry_key, (size_t)n_ent, (size_t)acc[kViewAccEntries] + 2, s);
-                grow_keeping(d_entry_rec, (size_t)n_ent, (size_t)acc[kViewAccEntries] + 2, s);
-            }
-            ViewEmitArgs b{};
-            b.s = a;
-            b.group_entry_base = d_group_entry_base.p; b.group_record_base = d_group_record_base.p;
-            b.store_delta = (int64_t)base - (int64_t)u_first;
-            b.record_base = n_rec; b.entry_base = n_ent;
-            b.off = d_off.p; b.len = d_len.p;
-            b.entry_key = listed ? d_entry_key.p : nullptr; b.entry_rec = listed ? d_entry_rec.p : nullptr;
-            t_b.start(s);
-            launch_view_emit(b, s);
-            t_b.stop(s);
-            // (the next batch's K1 / K2 overwrite U and the descriptors: K12b and the copy end first)
-            SBX_HIP(hipStreamSynchronize(s));
-            if (nrec) st.ms_emit += t_b.ms();
-            n_rec = acc[kViewAccRecords];
-            n_ent = acc[kViewAccEntries];
-            return true;
-        });
-        if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
-        if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 output records");
-        if (!listed && n_ent != n_rec) throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_ent) + " entries for " + std::to_string(n_rec) + " records");
-        const uint64_t u_total = plan.u_total;
-        c.reset();                                       // the batch buffers make room for the sort and the output pieces
-        d_count.release(); d_group_entries.release(); d_group_records.release(); d_group_entry_base.release(); d_group_record_base.release();
-
-        // ---- the order of the entries ----
-        Stream stream;
-        stream.create();
-        s = stream.get();
-        const uint64_t n = n_ent;
-        DevBuf<uint32_t> d_perm((size_t)n + 2);
-        ResidentOrder order;
-        if (listed && sel.list.size() > 1) {
-            // keys are region indices: what varies lies below the width of the largest one
-            const uint64_t varying = (1ull << sortc::bit_width64((uint64_t)sel.list.size() - 1)) - 1ull;
-            d_entry_key.ensure((size_t)n + 2);
-            sort_resident(d_entry_key.p, n, varying, s, &order);
-            EventTimer t_c;
-            t_c.start(s);
-            launch_view_compose(d_entry_rec.p, order.perm, n, d_perm.p, s);
-            t_c.stop(s);
-            SBX_HIP(hipStreamSynchronize(s));
-            st.ms_sort = order.ms_sort + (n ? t_c.ms() : 0.0);
-            st.n_sort_passes = order.n_passes;
-            order = ResidentOrder();
-        } else if (listed) {
-            if (n) SBX_HIP(hipMemcpyAsync(d_perm.p, d_entry_rec.p, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-        } else {
-            launch_iota(d_perm.p, n, s);
-        }
-        d_entry_key.release(); d_entry_rec.release();
-        d_len.ensure(2);                                 // (nothing selected: the arrays were never grown)
-        d_off.ensure(2);
+        SelectedRecords r;
+        select_resident(c, opts, threshold, sel, hlen, 48, &r, &st);
+        const uint64_t n = r.n;
+        hipStream_t s = r.stream.get();
         DevBuf<uint64_t> d_out_off((size_t)n + 2);
-        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, d_perm.p, n, d_out_off.p, level,
-                                                &acc[kViewAccBytes], "selected records", s, &st.ms_gather);
+        const WrittenBam w = write_store_output(out_file, header, r.store.p, r.off.p, r.len, r.perm.p, n, d_out_off.p, level,
+                                                &r.record_bytes, "selected records", s, &st.ms_gather);
         out_file.disarm();
-        st.n_records_in = n_in; st.n_records_selected = n_rec; st.n_entries_out = n;
-        st.inflated_bytes = u_total; st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
-        st.n_regions = sel.given(); st.n_batches = n_batches;
+        st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
         st.ms_deflate = w.ms_deflate;
         st.ms_total_wall = (wall_now() - w0) * 1e3;
         print_timing(st, "bam");
@@ -290,6 +337,128 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
     });
     // (the index is a pass of its own and not part of the figures)
     return rc != SBX_OK ? rc : index_written_bam(path, with_index, device, err, errlen);
+}
+
+int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
+                 size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device, sbx_view_stats* stats,
+                 char* err, size_t errlen) {
+    const bool to_stdout = !out_path || !strcmp(out_path, "-");
+    const char* const path = to_stdout ? "/dev/stdout" : out_path;
+    return run_entry(err, errlen, [&] {
+        if (!in_path) throw Error(SBX_EINVAL, "null argument");
+        if (!to_stdout) refuse_overwrite(in_path, path);
+        uint64_t threshold = 0;
+        check_opts(filter, opts, &threshold);
+        const double w0 = wall_now();
+        Standalone c = open_record_pass(in_path, device, filter, true);
+        OutputGuard out_file(path, to_stdout);
+        const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
+        std::string text, why;
+        if (with_header && !mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why))
+            throw Error(SBX_EFORMAT, "SAM header: " + why);
+        // the reference names, once: offsets + bytes
+        std::vector<uint32_t> ref_off{0};
+        std::string ref_bytes;
+        for (const RefSeq& q : c->hdr.refs) { ref_bytes += q.name; ref_off.push_back((uint32_t)ref_bytes.size()); }
+
+        sbx_view_stats st{};
+        SelectedRecords r;
+        select_resident(c, opts, threshold, sel, text.size(), 48 + 12, &r, &st);       // (+ length and offset of every line)
+        const uint64_t n = r.n;
+        hipStream_t s = r.stream.get();
+        DevBuf<uint32_t> d_ref_off(ref_off.size());
+        DevBuf<char> d_ref_bytes(ref_bytes.size() + 1);
+        SBX_HIP(hipMemcpyAsync(d_ref_off.p, ref_off.data(), ref_off.size() * 4, hipMemcpyHostToDevice, s));
+        if (!ref_bytes.empty()) SBX_HIP(hipMemcpyAsync(d_ref_bytes.p, ref_bytes.data(), ref_bytes.size(), hipMemcpyHostToDevice, s));
+        const SamEntries e{r.store.p, r.off.p, r.len.p, r.perm.p, n, samc::RefNames{d_ref_off.p, d_ref_bytes.p, (int32_t)ref_off.size() - 1}};
+
+        // ---- K13a over all entries, the offsets of the lines, the pieces ----
+        const uint32_t groups = sam_groups(n);
+        DevBuf<uint32_t> d_line_len((size_t)n + 2), d_group_sum(groups + 2), d_n_pieces(1);
+        DevBuf<uint64_t> d_group_base(groups + 2), d_line_off((size_t)n + 2);
+        DevBuf<unsigned long long> d_acc(kSamAccWords);
+        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kSamAccWords * sizeof(unsigned long long), s));
+        EventTimer t_a;
+        t_a.start(s);
+        launch_sam_measure(e, d_line_len.p, d_group_sum.p, d_acc.p, s);
+        if (n) {
+            launch_count_scan(d_group_sum.p, groups, d_group_base.p, nullptr, 0, s);
+            launch_sam_offsets(d_line_len.p, d_group_base.p, n, d_line_off.p, s);
+        }
+        t_a.stop(s);
+        const uint64_t budget = sam_piece_bytes();
+        launch_sam_pieces(d_line_off.p, n, budget, nullptr, nullptr, d_n_pieces.p, s);
+        unsigned long long acc[kSamAccWords] = {0};
+        uint32_t n_pieces = 0;
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipMemcpyAsync(&n_pieces, d_n_pieces.p, 4, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        if (acc[kSamAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSamAccBad]));       // (before a byte is written)
+        if (acc[kSamAccTooLong]) throw Error(SBX_EUNSUPPORTED, "a SAM line of 4 GiB or more");
+        if (n) st.ms_gather += t_a.ms();
+        DevBuf<uint32_t> d_first((size_t)n_pieces + 2);
+        DevBuf<uint64_t> d_first_off((size_t)n_pieces + 2);
+        std::vector<uint32_t> first((size_t)n_pieces + 1, 0);
+        std::vector<uint64_t> first_off((size_t)n_pieces + 1, 0);
+        launch_sam_pieces(d_line_off.p, n, budget, d_first.p, d_first_off.p, d_n_pieces.p, s);
+        SBX_HIP(hipMemcpyAsync(first.data(), d_first.p, first.size() * 4, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipMemcpyAsync(first_off.data(), d_first_off.p, first_off.size() * 8, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        uint64_t max_piece = 0;
+        for (uint32_t k = 0; k < n_pieces; ++k) max_piece = std::max(max_piece, first_off[k + 1] - first_off[k]);
+
+        // ---- K13b piece by piece: while the host copies and writes piece k, the device formats piece k + 1 ----
+        DevBuf<uint8_t> d_piece[2];
+        PinnedBuf<uint8_t> h_piece[2];
+        PinnedBuf<unsigned long long> h_acc;
+        h_acc.ensure(2 * kSamAccWords);
+        for (int b = 0; b < 2 && b < (int)n_pieces; ++b) { d_piece[b].alloc((size_t)max_piece + 64); h_piece[b].ensure((size_t)max_piece + 64); }
+        EventTimer t_b[2];
+        Event ev_copy[2];
+        Stream copy;
+        copy.create();
+        FILE* f = fopen(out_file.c_str(), "wb");
+        if (!f) throw Error(SBX_EIO, "cannot write " + out_file.path);
+        out_file.arm();
+        bool ok = text.empty() || fwrite(text.data(), 1, text.size(), f) == text.size();
+        try {
+            auto finish = [&](uint32_t k) {             // piece k: its copy has arrived; check, write
+                const int b = (int)(k & 1u);
+                SBX_HIP(hipEventSynchronize(ev_copy[b].get()));
+                st.ms_gather += t_b[b].ms();
+                if (h_acc.p[b * kSamAccWords + kSamAccOverrun])
+                    throw Error(SBX_EFORMAT, "internal error: a SAM line did not have the length it was measured with");
+                const size_t bytes = (size_t)(first_off[k + 1] - first_off[k]);
+                ok = ok && fwrite(h_piece[b].p, 1, bytes, f) == bytes;
+            };
+            for (uint32_t k = 0; k < n_pieces; ++k) {
+                const int b = (int)(k & 1u);
+                t_b[b].start(s);
+                launch_sam_emit(e, d_line_len.p, d_line_off.p, first[k], first[k + 1], d_piece[b].p, d_acc.p, s);
+                t_b[b].stop(s);
+                if (k) finish(k - 1);
+                SBX_HIP(hipStreamWaitEvent(copy.get(), t_b[b].b, 0));
+                SBX_HIP(hipMemcpyAsync(h_piece[b].p, d_piece[b].p, (size_t)(first_off[k + 1] - first_off[k]), hipMemcpyDeviceToHost, copy.get()));
+                SBX_HIP(hipMemcpyAsync(h_acc.p + b * kSamAccWords, d_acc.p, kSamAccWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, copy.get()));
+                SBX_HIP(hipEventRecord(ev_copy[b].get(), copy.get()));
+            }
+            if (n_pieces) finish(n_pieces - 1);
+        } catch (...) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamSynchronize(copy.get());
+            fclose(f);
+            throw;
+        }
+        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out_file.path);
+        out_file.disarm();
+        st.stream_bytes = n ? first_off[n_pieces] : 0;
+        st.ms_total_wall = (wall_now() - w0) * 1e3;
+        print_timing(st, "sam");
+        if (getenv("SBX_TIMING"))
+            fprintf(stderr, "[sbx] output: text_bytes=%llu n_pieces=%u piece_bytes=%llu\n", (unsigned long long)st.stream_bytes, n_pieces,
+                    (unsigned long long)budget);
+        if (stats) *stats = st;
+    });
 }
 
 }  // extern "C"

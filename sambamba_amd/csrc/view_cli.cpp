@@ -10,6 +10,11 @@
 // options may follow the file name (cli_opts.hpp scans them) and `--` ends the options.  Without arguments the usage goes to stderr
 // and the exit status is 0, as in the reference.  Without --subsampling-seed a random 64-bit seed is drawn.  The @PG line's CL is
 // "view" followed by the arguments as given.  Errors: "sbx-view: <message>" on stderr and exit status 1.
+//
+// Compiled a second time with -DSBX_VIEW_SAM=1 this file is `sbx-sam`: the same options under the same policy, with the third sink
+// (sbx_view_sam).  There `sam` is the default format as in the reference, -f sam and -f bam are both taken, -h writes the header in
+// front of the SAM records, and -l together with SAM output is refused.  (sbx-view keeps refusing sam: folding the two into one
+// executable is the removal of this switch.)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -21,7 +26,57 @@
 #include "../../include/sbx_depth.h"
 #include "cli_opts.hpp"
 
+#ifndef SBX_VIEW_SAM
+#define SBX_VIEW_SAM 0
+#endif
+
 namespace {
+
+#if SBX_VIEW_SAM
+const char* const kProgram = "sbx-sam";
+
+void usage() {
+    fputs("Usage: sbx-sam [options] <input.bam> [region1 [...]]\n"
+          "\n"
+          "Selects records of a BAM file, as `sambamba view` does, on the GPU; writes them as SAM (the default), as a BAM (-f bam)\n"
+          "or their number (-c).  The SAM text is formatted on the GPU.\n"
+          "\n"
+          "Options: -F, --filter=FILTER\n"
+          "                    set custom filter for alignments\n"
+          "         --num-filter=NUMFILTER\n"
+          "                    filter flag bits; 'i1/i2' corresponds to -f i1 -F i2 samtools arguments;\n"
+          "                    either of the numbers can be omitted\n"
+          "         -f, --format=sam|bam\n"
+          "                    output format (default: sam); json, unpack, msgpack and cram are not supported\n"
+          "         -h, --with-header\n"
+          "                    print header before reads (always done for BAM output)\n"
+          "         -H, --header\n"
+          "                    output only header to stdout, as SAM\n"
+          "         -I, --reference-info\n"
+          "                    output to stdout only reference names and lengths in JSON\n"
+          "         -L, --regions=FILENAME\n"
+          "                    output only reads overlapping one of regions from the BED file\n"
+          "         -c, --count\n"
+          "                    output to stdout only count of matching records, hHI are ignored\n"
+          "         -l, --compression-level\n"
+          "                    specify compression level (from 0 to 9, works only for BAM output)\n"
+          "         -o, --output-filename\n"
+          "                    specify output filename (default, and '-': stdout)\n"
+          "         -s, --subsample=FRACTION\n"
+          "                    subsample reads (read pairs)\n"
+          "         --subsampling-seed=SEED\n"
+          "                    set seed for subsampling\n"
+          "         -t, --nthreads=NTHREADS, -p, --show-progress, -T, --ref-filename=FASTA\n"
+          "                    accepted for compatibility\n"
+          "         -v, --valid, -S, --sam-input\n"
+          "                    not supported\n"
+          "\n"
+          "Regions are 'chr', 'chr:beg-end' or '*' (reads without a reference); at most 1024 may be listed, a BED file has no limit.\n"
+          "A read that overlaps several listed regions is written once per region.  No index is needed; the whole file is read.\n",
+          stderr);
+}
+#else
+const char* const kProgram = "sbx-view";
 
 void usage() {
     fputs("Usage: sbx-view [options] <input.bam> [region1 [...]]\n"
@@ -63,9 +118,10 @@ void usage() {
           "A read that overlaps several listed regions is written once per region.  No index is needed; the whole file is read.\n",
           stderr);
 }
+#endif
 
 int die(const std::string& m) {
-    fprintf(stderr, "sbx-view: %s\n", m.c_str());
+    fprintf(stderr, "%s: %s\n", kProgram, m.c_str());
     return 1;
 }
 
@@ -102,12 +158,12 @@ int print_text(const std::string& in, bool reference_info) {
 
 int main(int argc, char** argv) {
     std::string filter_str, num_filter, format = "sam", bed, level_str, out, frac_str, seed_str;
-    bool have_num_filter = false, have_frac = false, have_seed = false, header_only = false, reference_info = false, count_only = false;
+    bool have_num_filter = false, have_frac = false, have_seed = false, header_only = false, reference_info = false, count_only = false, with_header = false;
     std::vector<std::string> files;
     // long name, short name, takes a value, what it does: 0 ignored, 1 filter, 2 num-filter, 3 format, 4 -H, 5 -I, 6 -L, 7 -c, 8 level, 9 out,
-    // 10 fraction, 11 seed, 12 refused
+    // 10 fraction, 11 seed, 12 refused, 13 -h
     static const sbx::OptSpec opts[] = {
-        {"filter", 'F', true, 1}, {"num-filter", 0, true, 2}, {"format", 'f', true, 3}, {"with-header", 'h', false, 0}, {"header", 'H', false, 4},
+        {"filter", 'F', true, 1}, {"num-filter", 0, true, 2}, {"format", 'f', true, 3}, {"with-header", 'h', false, 13}, {"header", 'H', false, 4},
         {"reference-info", 'I', false, 5}, {"regions", 'L', true, 6}, {"count", 'c', false, 7}, {"valid", 'v', false, 12},
         {"sam-input", 'S', false, 12}, {"show-progress", 'p', false, 0}, {"compression-level", 'l', true, 8}, {"output-filename", 'o', true, 9},
         {"nthreads", 't', true, 0}, {"subsample", 's', true, 10}, {"subsampling-seed", 0, true, 11}, {"ref-filename", 'T', true, 0},
@@ -136,6 +192,7 @@ int main(int argc, char** argv) {
             case 9: out = t.value; break;
             case 10: frac_str = t.value; have_frac = true; break;
             case 11: seed_str = t.value; have_seed = true; break;
+            case 13: with_header = true; break;
             default: break;
         }
     }
@@ -146,7 +203,8 @@ int main(int argc, char** argv) {
     const std::string in = files[0];
     if (reference_info && !count_only) return print_text(in, true);
     if (header_only && !count_only) return print_text(in, false);
-    if (!count_only && format != "bam") {
+    const bool sam_out = SBX_VIEW_SAM && !count_only && format == "sam";
+    if (!count_only && format != "bam" && !sam_out) {
         if (format == "sam" || format == "json" || format == "unpack" || format == "msgpack" || format == "cram")
             return die("output format " + format + " is not supported yet: use -f bam or -c");
         return die("output format must be one of sam, bam, json");                        // view.d:397
@@ -157,6 +215,7 @@ int main(int argc, char** argv) {
         const long v = strtol(level_str.c_str(), &end, 10);
         if (*end || v < -1 || v > 9) return die("invalid compression level " + level_str);
         level = (int)v;
+        if (sam_out) return die("-l / --compression-level applies to BAM output only: give -f bam");
     }
     sbx_view_opts vo;
     memset(&vo, 0, sizeof vo);
@@ -198,6 +257,15 @@ int main(int argc, char** argv) {
     }
     std::string cl = "view";
     for (int i = 1; i < argc; ++i) { cl += ' '; cl += argv[i]; }
+#if SBX_VIEW_SAM
+    if (sam_out) {
+        const int rc = sbx_view_sam(in.c_str(), out.empty() ? "-" : out.c_str(), have_filter ? &filter : nullptr, &vo, regions.data(), regions.size(),
+                                    bed.c_str(), cl.c_str(), with_header ? 1 : 0, -1, nullptr, err, sizeof err);
+        if (rc != SBX_OK) return die(err);
+        return 0;
+    }
+#endif
+    (void)with_header;
     const int rc = sbx_view_bam(in.c_str(), out.empty() ? "-" : out.c_str(), have_filter ? &filter : nullptr, &vo, regions.data(), regions.size(),
                                 bed.c_str(), cl.c_str(), level, 0, -1, nullptr, err, sizeof err);
     if (rc != SBX_OK) return die(err);
