@@ -89,6 +89,9 @@ extern (C) nothrow @nogc {
     int sbx_sort_bam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, int level, int with_index, int device,
                      sbx_sort_stats* stats, char* err, size_t errlen);
     int sbx_sort_header_text(const(char)* text, size_t n, char* out_, size_t cap, size_t* out_len);
+    // order: 1 sort -n, 2 sort -N; match_mates: -M
+    int sbx_sort_bam_by_name(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, int level, int order, int match_mates,
+                             int device, sbx_sort_stats* stats, char* err, size_t errlen);
     struct sbx_markdup_stats {
         ulong n_records_in; ulong n_records_out; ulong n_end_pairs; ulong n_single_ends; ulong n_unmatched_pairs; ulong n_duplicates;
         ulong inflated_bytes; ulong stream_bytes; ulong compressed_bytes;

@@ -212,6 +212,24 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
  * the length (without the terminating zero, also with SBX_ENOMEM when cap is too small); SBX_EFORMAT for a text the reference's
  * parser throws on. */
 int sbx_sort_header_text(const char* text, size_t n, char* out, size_t cap, size_t* out_len);
+/* `sambamba sort -n` (order 1) and `sambamba sort -N` (order 2), with -M when match_mates != 0 (sambamba/sort.d:221-298; the
+ * comparators: BioD bio/std/hts/bam/read.d:1493-1621), applied by a stable sort -- whatever compares equal keeps file order.
+ *   order 1  compareReadNames: read names as unsigned bytes, a proper prefix first.
+ *   order 2  mixedStrCompare: as order 1, but where both names stand at a digit the digit runs compare as numbers, leading zeros
+ *            skipped; runs of equal value compare by their number of leading zeros.
+ *   match_mates  among equal names: ascending HI tag (absent: 0), then ascending flag.
+ * Everything else is sbx_sort_bam: filter, level, the record bytes, the resident store and its SBX_ENOMEM.  The header text is
+ * what sbx_sort_header_text gives with SO:queryname in the place of SO:coordinate.  No index is written.
+ * Deliberate divergences, both SBX_EFORMAT with the number of such records in err and no output file: a read name that holds a byte
+ * outside 0x01..0x7F or is not NUL-terminated (the reference orders such bytes unsigned under -n and signed under -N); with
+ * match_mates, an HI tag that is of no integer type (c C s S i I) or does not fit int, or aux fields that run past the record (the
+ * reference throws).  SBX_EINVAL for another order.
+ * sbx_sort_stats for this call: key_bits is the sum of the widths of the varying bits over the key words sorted (a name's key is
+ * a string of 64-bit words; a word in which no two records differ is not sorted at all), n_sort_passes the sum of all K9b passes,
+ * ms_keys = K9a + the copy into the record store + K14a (key measure, scan, emit), ms_sort = K14b (the gather of one word) + K9b
+ * over all words; the other fields as for sbx_sort_bam. */
+int sbx_sort_bam_by_name(const char* in_path, const char* out_path, const sbx_filter* filter, int level, int order, int match_mates,
+                         int device, sbx_sort_stats* stats, char* err, size_t errlen);
 
 /* `sambamba markdup` (sambamba/markdup.d): every record is written in input order, byte for byte except flag 0x400, which is set on
  * the duplicates and cleared on every other record that is neither secondary nor supplementary; remove_duplicates != 0 drops the

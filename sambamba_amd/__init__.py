@@ -8,7 +8,7 @@ fails loudly when the library has not been built.
 """
 from ._lib import (SbxError, Depth, lib, lib_path, inflate_blocks, compile_filter, regex_search, cli_path,  # noqa: F401
                    bgzf_compress, write_bam, build_index, flagstat, format_flagstat, flagstat_cli_path,
-                   sort_bam, sort_header_text, sort_cli_path, markdup, markdup_header_text, markdup_cli_path,
+                   sort_bam, sort_header_text, sort_cli_path, nsort_cli_path, markdup, markdup_header_text, markdup_cli_path,
                    merge, merge_header_text, merge_cli_path,
                    view, view_num_filter, view_reference_info, view_cli_path, sam_cli_path,
                    SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW)

@@ -13,6 +13,7 @@ _MARKDUP_CLI_PATH = os.path.join(HERE, "csrc", "sbx-markdup")
 _MERGE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-merge")
 _VIEW_CLI_PATH = os.path.join(HERE, "csrc", "sbx-view")
 _SAM_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sam")
+_NSORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-nsort")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -121,7 +122,7 @@ EXPORTS = [
     "sbx_depth_window_stats",
     "sbx_format_base_rows", "sbx_stream_base_rows", "sbx_plan_batches", "sbx_run_batch", "sbx_last_run_stats", "sbx_tile_info", "sbx_next_active_range", "sbx_preload",
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
-    "sbx_sort_bam", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
+    "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
     "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_num_filter", "sbx_view_reference_info",
 ]
@@ -159,6 +160,10 @@ def view_cli_path():
 
 def sam_cli_path():
     return _SAM_CLI_PATH
+
+
+def nsort_cli_path():
+    return _NSORT_CLI_PATH
 
 
 def lib():
@@ -218,6 +223,8 @@ def lib():
     L.sbx_flagstat.argtypes = [C.c_char_p, C.c_int, C.POINTER(Flagstat), C.c_char_p, C.c_size_t]
     L.sbx_format_flagstat.argtypes = [C.POINTER(Flagstat), C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_sort_bam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.POINTER(SortStats), C.c_char_p, C.c_size_t]
+    L.sbx_sort_bam_by_name.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SortStats), C.c_char_p,
+                                       C.c_size_t]
     L.sbx_sort_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_markdup.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(MarkdupStats), C.c_char_p, C.c_size_t]
     L.sbx_markdup_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -332,15 +339,30 @@ def format_flagstat(counts, tabular=False):
     return buf.raw[:n.value].decode()
 
 
-def sort_bam(in_path, out_path, filter=None, level=-1, index=False, device=-1):
-    """sbx_sort_bam (`sambamba sort`, coordinate order): sorts in_path into out_path on the device; filter is a -F query string (None:
-    every record); index=True also writes out_path + ".bai".  Returns the fields of sbx_sort_stats as a dict."""
+SORT_ORDERS = {"coordinate": 0, "queryname": 1, "natural": 2}
+
+
+def sort_bam(in_path, out_path, filter=None, level=-1, index=False, device=-1, order="coordinate", match_mates=False):
+    """sbx_sort_bam (`sambamba sort`): sorts in_path into out_path on the device; filter is a -F query string (None: every record);
+    index=True also writes out_path + ".bai".  order: "coordinate", or through sbx_sort_bam_by_name "queryname" (sort -n: names as
+    bytes) or "natural" (sort -N: digit runs as numbers); match_mates (sort -M, name orders only): equal names by HI tag, then flag.
+    Returns the fields of sbx_sort_stats as a dict."""
+    if order not in SORT_ORDERS:
+        raise ValueError("order must be one of coordinate, queryname, natural")
+    by_name = SORT_ORDERS[order]
+    if by_name and index:
+        raise ValueError("a BAM sorted by name has no index")
+    if match_mates and not by_name:
+        raise ValueError("match_mates only works with order queryname or natural")
     L = lib()
     f = compile_filter(filter) if filter else None
     st = SortStats()
     err = C.create_string_buffer(512)
-    rc = L.sbx_sort_bam(in_path.encode(), out_path.encode(), C.byref(f) if f is not None else None, int(level), int(index), device,
-                        C.byref(st), err, 512)
+    fp = C.byref(f) if f is not None else None
+    if by_name:
+        rc = L.sbx_sort_bam_by_name(in_path.encode(), out_path.encode(), fp, int(level), by_name, int(bool(match_mates)), device, C.byref(st), err, 512)
+    else:
+        rc = L.sbx_sort_bam(in_path.encode(), out_path.encode(), fp, int(level), int(index), device, C.byref(st), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
     return {k: getattr(st, k) for k, _ in SortStats._fields_ if k != "reserved"}

@@ -10,8 +10,236 @@
 // The scaffold of the entry point, the plan of the store, the copy into it and the output tail are engine_store.hpp, shared with
 // sbx_markdup, sbx_merge_bam and sbx_view_bam.
 // What does not fit the device next to one batch of the read pass is refused with SBX_ENOMEM (an out-of-core merge is not built).
+//
+// sbx_sort_bam_by_name (`sambamba sort -n / -N`, with or without -M) is the same call with another order: next to K9a, K14a
+// (namesort.hip) builds the key of every kept record's name in a key store of 64-bit words, and the order is an LSD sort over those
+// words -- the -M word first, then the words from the last to word 0, each one K14b + K9b, and only the words and bits that vary.
 #include "engine_store.hpp"
+#include "namesort.hpp"
 #include "sort_core.hpp"
+
+namespace {
+
+// The keys of the names while the batches arrive (K14a) and the order over them (K14b + K9b).
+struct NameKeys {
+    uint32_t order = 0;             // nsc::kOrderLex / kOrderNatural
+    bool match_mates = false;
+    DevBuf<uint64_t> store, off, mate;          // the key store, [n + 1] where a record's key starts in it, [n] the -M words
+    DevBuf<uint32_t> words;                     // of one batch
+    DevBuf<uint64_t> word_base;
+    DevBuf<unsigned long long> d_acc;
+    unsigned long long acc[kNameAccWords];
+    uint64_t n_words = 0;                       // key words of the batches so far
+    uint32_t words_sorted = 0;
+
+    void init(uint32_t order_, bool match_mates_, hipStream_t s) {
+        order = order_;
+        match_mates = match_mates_;
+        d_acc = DevBuf<unsigned long long>(kNameAccWords);
+        name_acc_init(acc);
+        SBX_HIP(hipMemcpyAsync(d_acc.p, acc, sizeof acc, hipMemcpyHostToDevice, s));
+        SBX_HIP(hipStreamSynchronize(s));
+    }
+    // K14a over the kept records [first, first + n) of a batch (K9a has written their offsets and lengths, their bytes are queued
+    // into the record store on the same stream).  Returns false when a name or an HI tag was refused.
+    bool add_batch(const uint8_t* d_store, const uint64_t* d_off, const uint32_t* d_len, uint64_t first, uint64_t n, hipStream_t s,
+                   double* ms_keys) {
+        if (!n) return true;
+        grow_keeping(off, (size_t)first, (size_t)(first + n + 2), s);       // (emit writes off[first] again)
+        if (match_mates) grow_keeping(mate, (size_t)first, (size_t)(first + n + 2), s);
+        words.ensure((size_t)n + 4);
+        word_base.ensure((size_t)n + 4);
+        NameKeyArgs a{};
+        a.store = d_store; a.off = d_off; a.len = d_len; a.first = first; a.n = n;
+        a.order = order; a.match_mates = match_mates ? 1u : 0u;
+        a.words = words.p; a.word_base = word_base.p; a.key_base = n_words;
+        a.key_off = off.p; a.mate_word = mate.p; a.acc = d_acc.p;
+        EventTimer t;
+        t.start(s);
+        launch_name_key_measure(a, s);
+        launch_count_scan(words.p, (uint32_t)n, word_base.p, nullptr, 0, s);
+        t.stop(s);
+        uint64_t batch_words = 0;
+        SBX_HIP(hipMemcpyAsync(&batch_words, word_base.p + n, 8, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, 2 * sizeof acc[0], hipMemcpyDeviceToHost, s));      // the two counts of refusals
+        SBX_HIP(hipStreamSynchronize(s));
+        *ms_keys += t.ms();
+        if (acc[kNameAccBadName] || acc[kNameAccBadHi]) return false;
+        grow_keeping(store, (size_t)n_words, (size_t)(n_words + batch_words + 2), s);     // (SBX_ENOMEM when the keys do not fit)
+        a.key_store = store.p;
+        t.start(s);
+        launch_name_key_emit(a, s);
+        t.stop(s);
+        *ms_keys += t.ms();
+        n_words += batch_words;
+        return true;
+    }
+    void refuse_bad() {
+        if (!acc[kNameAccBadName] && !acc[kNameAccBadHi]) return;
+        if (acc[kNameAccBadName])
+            throw Error(SBX_EFORMAT, std::to_string(acc[kNameAccBadName]) + " record(s) have a read name that is not NUL-terminated inside the record or "
+                                     "holds a byte outside 0x01..0x7F: such names are not sorted");
+        throw Error(SBX_EFORMAT, std::to_string(acc[kNameAccBadHi]) + " record(s) have an HI tag that is not an integer fitting int, or aux fields that "
+                                 "run past the record: -M cannot order them");
+    }
+    // LSD over the words: the -M word first, then the key words from the last to word 0; a word no bit of which varies costs nothing
+    void sort(uint64_t* d_key, uint64_t n, hipStream_t s, ResidentOrder* o) {
+        begin_resident_order(n, s, o);
+        if (!n) return;
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        EventTimer t;
+        if (match_mates && (acc[kNameAccMateOr] ^ acc[kNameAccMateAnd])) {
+            t.start(s);
+            launch_name_mate_gather(mate.p, o->perm, n, d_key, s);
+            t.stop(s);
+            continue_resident_order(d_key, n, acc[kNameAccMateOr] ^ acc[kNameAccMateAnd], s, o);
+            o->ms_sort += t.ms();
+            ++words_sorted;
+        }
+        const uint32_t w_min = (uint32_t)std::min<unsigned long long>(acc[kNameAccMinWords], nsc::kMaxKeyWords);
+        const uint32_t w_max = (uint32_t)std::min<unsigned long long>(acc[kNameAccMaxWords], nsc::kMaxKeyWords);
+        for (uint32_t w = w_max; w-- > 0;) {
+            // (from the shortest key on, some record has ended at this word and counts as 0)
+            const uint64_t varying = acc[kNameAccOr + w] ^ (w < w_min ? acc[kNameAccAnd + w] : 0ull);
+            if (!varying) continue;
+            t.start(s);
+            launch_name_word_gather(store.p, off.p, o->perm, n, w, d_key, s);
+            t.stop(s);
+            continue_resident_order(d_key, n, varying, s, o);
+            o->ms_sort += t.ms();
+            ++words_sorted;
+        }
+    }
+    void release() { store.release(); off.release(); mate.release(); words.release(); word_base.release(); }
+};
+
+// order: 0 coordinate (sbx_sort_bam), nsc::kOrderLex, nsc::kOrderNatural (sbx_sort_bam_by_name)
+void sort_file(const char* in_path, const char* out_path, const sbx_filter* filter, int level, uint32_t name_order, bool match_mates,
+               int device, sbx_sort_stats* stats) {
+    check_level(level);
+    check_filter(filter);
+    refuse_overwrite(in_path, out_path);
+    const double w0 = wall_now();
+    const bool use_filter = has_ops(filter);
+    Standalone c = open_record_pass(in_path, device, filter, use_filter);
+    OutputGuard out_file(out_path);
+    const int32_t n_ref = (int32_t)c->hdr.refs.size();
+    std::string text, why;
+    if (!sortc::sort_header_text(c->hdr.text.data(), c->hdr.text.size(), &text, &why, name_order ? "queryname" : "coordinate"))
+        throw Error(SBX_EFORMAT, "SAM header: " + why);
+    const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
+    const uint64_t hlen = header.size();
+
+    // per record: key, offset, length and K9b's second key and two values; a name order adds the key's offset, the -M word and
+    // -- an estimate, the key store grows with the batches -- four key words
+    const StorePlan plan = plan_record_store(c.get(), hlen, name_order ? 48 + 16 + 32 : 48, "sorting");
+    const uint64_t u_total = plan.u_total, u_first = plan.u_first, store_bytes = plan.store_bytes, batch_u = plan.batch_u;
+    hipStream_t s = c->stream.get();
+    DevBuf<uint8_t> d_store((size_t)store_bytes + 64);
+    DevBuf<uint64_t> d_key, d_off;
+    DevBuf<uint32_t> d_len, d_group_count;
+    DevBuf<uint64_t> d_group_base;
+    DevBuf<unsigned long long> d_acc(kSortAccWords);
+    {
+        const unsigned long long init[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
+        SBX_HIP(hipMemcpyAsync(d_acc.p, init, sizeof init, hipMemcpyHostToDevice, s));
+        SBX_HIP(hipStreamSynchronize(s));
+    }
+    NameKeys names;
+    if (name_order) names.init(name_order, match_mates, s);
+    const double w1 = wall_now();
+
+    // ---- the read pass ----
+    sbx_sort_stats st{};
+    EventTimer t_k;
+    uint64_t n_in = 0, n_kept = 0, cur = u_first;
+    uint32_t n_batches = 0;
+    bool names_ok = true;
+    unsigned long long acc[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
+    for_each_record_batch(c.get(), batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        const size_t want = (size_t)(n_kept + nrec + 2);
+        grow_keeping(d_key, (size_t)n_kept, want, s);
+        grow_keeping(d_off, (size_t)n_kept, want, s);
+        grow_keeping(d_len, (size_t)n_kept, want, s);
+        if (use_filter) { d_group_count.ensure(sort_keys_groups(nrec) + 4); d_group_base.ensure(sort_keys_groups(nrec) + 4); }
+        t_k.start(s);
+        copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
+        SortKeysArgs a{};
+        a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
+        a.n_ref = n_ref; a.key_n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
+        a.store_delta = (int64_t)base - (int64_t)u_first;
+        a.out_base = n_kept;
+        a.key = d_key.p; a.off = d_off.p; a.len = d_len.p; a.acc = d_acc.p;
+        launch_sort_keys(a, d_group_count.p, d_group_base.p, s);
+        t_k.stop(s);
+        // (the next batch's K1 / K2 overwrite U and the descriptors: K9a and the copy end first)
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_keys += t_k.ms();
+        n_in += nrec;
+        const uint64_t kept_before = n_kept;
+        n_kept = acc[kSortAccKept];
+        cur = next;
+        if (acc[kSortAccBad]) return false;
+        // K14a: the keys of the names of the records K9a kept, read from the store
+        if (name_order) names_ok = names.add_batch(d_store.p, d_off.p, d_len.p, kept_before, n_kept - kept_before, s, &st.ms_keys);
+        return names_ok;
+    });
+    if (acc[kSortAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSortAccBad]));
+    if (name_order) names.refuse_bad();
+    if (!use_filter && n_kept != n_in)
+        throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(n_in) + " records received a key");
+    if (n_kept > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
+    const uint64_t n = n_kept;
+    c.reset();                                       // the batch buffers make room for the sort and the output pieces
+    const double w2 = wall_now();
+
+    // ---- K9b (a name order: K14b + K9b, word by word) ----
+    Stream stream;
+    stream.create();
+    s = stream.get();
+    ResidentOrder order;
+    if (name_order) {
+        names.sort(d_key.p, n, s, &order);
+        SBX_HIP(hipStreamSynchronize(s));
+        names.release();                             // the key store goes before the output pieces come
+        order.hist.release();
+        order.hist_base.release();
+    } else {
+        sort_resident(d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
+    }
+    // the keys are done with: one of their buffers holds the output offsets
+    d_key.release();
+    st.ms_sort = order.ms_sort;
+
+    // ---- offsets, K9c + deflate, piece by piece ----
+    const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, order.perm, n, order.key2.p, level,
+                                            &acc[kSortAccBytes], "sorted records", s, &st.ms_gather);
+    out_file.disarm();
+    const double w3 = w.w_planned, w4 = wall_now();
+    st.n_records_in = n_in; st.n_records_out = n;
+    st.inflated_bytes = u_total; st.sorted_stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
+    st.key_bits = order.key_bits; st.n_sort_passes = order.n_passes; st.n_batches = n_batches;
+    st.ms_deflate = w.ms_deflate;
+    st.ms_total_wall = (w4 - w0) * 1e3;
+    if (getenv("SBX_TIMING")) {
+        char by[64] = "";
+        if (name_order)
+            snprintf(by, sizeof by, "order=%s%s words_sorted=%u ", name_order == nsc::kOrderNatural ? "natural" : "queryname",
+                     match_mates ? "+mates" : "", names.words_sorted);
+        fprintf(stderr, "[sbx] sort: %sn_records_in=%llu n_records_out=%llu inflated_bytes=%llu sorted_stream_bytes=%llu compressed_bytes=%llu "
+                        "key_bits=%u n_sort_passes=%u n_batches=%u ms_inflate=%.2f ms_index=%.2f ms_keys=%.2f ms_sort=%.2f ms_gather=%.2f "
+                        "ms_deflate=%.2f ms_total_wall=%.1f (open %.1f, read pass %.1f, sort %.1f, write %.1f)\n", by,
+                (unsigned long long)st.n_records_in, (unsigned long long)st.n_records_out, (unsigned long long)st.inflated_bytes,
+                (unsigned long long)st.sorted_stream_bytes, (unsigned long long)st.compressed_bytes, st.key_bits, st.n_sort_passes, st.n_batches,
+                st.ms_inflate, st.ms_index, st.ms_keys, st.ms_sort, st.ms_gather, st.ms_deflate, st.ms_total_wall, (w1 - w0) * 1e3,
+                (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
+    }
+    if (stats) *stats = st;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -26,105 +254,19 @@ int sbx_sort_bam(const char* in_path, const char* out_path, const sbx_filter* fi
                  sbx_sort_stats* stats, char* err, size_t errlen) {
     const int rc = run_entry(err, errlen, [&] {
         if (!in_path || !out_path) throw Error(SBX_EINVAL, "null argument");
-        check_level(level);
-        check_filter(filter);
-        refuse_overwrite(in_path, out_path);
-        const double w0 = wall_now();
-        const bool use_filter = has_ops(filter);
-        Standalone c = open_record_pass(in_path, device, filter, use_filter);
-        OutputGuard out_file(out_path);
-        const int32_t n_ref = (int32_t)c->hdr.refs.size();
-        std::string text, why;
-        if (!sortc::sort_header_text(c->hdr.text.data(), c->hdr.text.size(), &text, &why)) throw Error(SBX_EFORMAT, "SAM header: " + why);
-        const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
-        const uint64_t hlen = header.size();
-
-        const StorePlan plan = plan_record_store(c.get(), hlen, 48, "sorting");
-        const uint64_t u_total = plan.u_total, u_first = plan.u_first, store_bytes = plan.store_bytes, batch_u = plan.batch_u;
-        hipStream_t s = c->stream.get();
-        DevBuf<uint8_t> d_store((size_t)store_bytes + 64);
-        DevBuf<uint64_t> d_key, d_off;
-        DevBuf<uint32_t> d_len, d_group_count;
-        DevBuf<uint64_t> d_group_base;
-        DevBuf<unsigned long long> d_acc(kSortAccWords);
-        {
-            const unsigned long long init[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
-            SBX_HIP(hipMemcpyAsync(d_acc.p, init, sizeof init, hipMemcpyHostToDevice, s));
-            SBX_HIP(hipStreamSynchronize(s));
-        }
-        const double w1 = wall_now();
-
-        // ---- the read pass ----
-        sbx_sort_stats st{};
-        EventTimer t_k;
-        uint64_t n_in = 0, n_kept = 0, cur = u_first;
-        uint32_t n_batches = 0;
-        unsigned long long acc[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
-        for_each_record_batch(c.get(), batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-            const size_t want = (size_t)(n_kept + nrec + 2);
-            grow_keeping(d_key, (size_t)n_kept, want, s);
-            grow_keeping(d_off, (size_t)n_kept, want, s);
-            grow_keeping(d_len, (size_t)n_kept, want, s);
-            if (use_filter) { d_group_count.ensure(sort_keys_groups(nrec) + 4); d_group_base.ensure(sort_keys_groups(nrec) + 4); }
-            t_k.start(s);
-            copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
-            SortKeysArgs a{};
-            a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
-            a.n_ref = n_ref; a.key_n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
-            a.store_delta = (int64_t)base - (int64_t)u_first;
-            a.out_base = n_kept;
-            a.key = d_key.p; a.off = d_off.p; a.len = d_len.p; a.acc = d_acc.p;
-            launch_sort_keys(a, d_group_count.p, d_group_base.p, s);
-            t_k.stop(s);
-            // (the next batch's K1 / K2 overwrite U and the descriptors: K9a and the copy end first)
-            SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipStreamSynchronize(s));
-            st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_keys += t_k.ms();
-            n_in += nrec;
-            n_kept = acc[kSortAccKept];
-            cur = next;
-            return acc[kSortAccBad] == 0;
-        });
-        if (acc[kSortAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSortAccBad]));
-        if (!use_filter && n_kept != n_in)
-            throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(n_in) + " records received a key");
-        if (n_kept > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-        const uint64_t n = n_kept;
-        c.reset();                                       // the batch buffers make room for the sort and the output pieces
-        const double w2 = wall_now();
-
-        // ---- K9b ----
-        Stream stream;
-        stream.create();
-        s = stream.get();
-        ResidentOrder order;
-        sort_resident(d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
-        // the keys are done with: one of their buffers holds the output offsets
-        d_key.release();
-        st.ms_sort = order.ms_sort;
-
-        // ---- offsets, K9c + deflate, piece by piece ----
-        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, order.perm, n, order.key2.p, level,
-                                                &acc[kSortAccBytes], "sorted records", s, &st.ms_gather);
-        out_file.disarm();
-        const double w3 = w.w_planned, w4 = wall_now();
-        st.n_records_in = n_in; st.n_records_out = n;
-        st.inflated_bytes = u_total; st.sorted_stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
-        st.key_bits = order.key_bits; st.n_sort_passes = order.n_passes; st.n_batches = n_batches;
-        st.ms_deflate = w.ms_deflate;
-        st.ms_total_wall = (w4 - w0) * 1e3;
-        if (getenv("SBX_TIMING"))
-            fprintf(stderr, "[sbx] sort: n_records_in=%llu n_records_out=%llu inflated_bytes=%llu sorted_stream_bytes=%llu compressed_bytes=%llu "
-                            "key_bits=%u n_sort_passes=%u n_batches=%u ms_inflate=%.2f ms_index=%.2f ms_keys=%.2f ms_sort=%.2f ms_gather=%.2f "
-                            "ms_deflate=%.2f ms_total_wall=%.1f (open %.1f, read pass %.1f, sort %.1f, write %.1f)\n",
-                    (unsigned long long)st.n_records_in, (unsigned long long)st.n_records_out, (unsigned long long)st.inflated_bytes,
-                    (unsigned long long)st.sorted_stream_bytes, (unsigned long long)st.compressed_bytes, st.key_bits, st.n_sort_passes, st.n_batches,
-                    st.ms_inflate, st.ms_index, st.ms_keys, st.ms_sort, st.ms_gather, st.ms_deflate, st.ms_total_wall, (w1 - w0) * 1e3,
-                    (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
-        if (stats) *stats = st;
+        sort_file(in_path, out_path, filter, level, 0, false, device, stats);
     });
     // (the index is a pass of its own and not part of the sort's figures)
     return rc != SBX_OK ? rc : index_written_bam(out_path, with_index, device, err, errlen);
+}
+
+int sbx_sort_bam_by_name(const char* in_path, const char* out_path, const sbx_filter* filter, int level, int order, int match_mates,
+                         int device, sbx_sort_stats* stats, char* err, size_t errlen) {
+    return run_entry(err, errlen, [&] {
+        if (!in_path || !out_path) throw Error(SBX_EINVAL, "null argument");
+        if (order != (int)nsc::kOrderLex && order != (int)nsc::kOrderNatural) throw Error(SBX_EINVAL, "order must be 1 (lexicographic) or 2 (natural)");
+        sort_file(in_path, out_path, filter, level, (uint32_t)order, match_mates != 0, device, stats);
+    });
 }
 
 }  // extern "C"

@@ -91,28 +91,63 @@ struct ResidentOrder {
     const uint32_t* perm = nullptr; // [n] record numbers in key order, equal keys in the order they had (one of val / val2)
     uint32_t key_bits = 0, n_passes = 0;
     double ms_sort = 0;
+    DevBuf<uint32_t> hist;          // K9b's counters and their scan
+    DevBuf<uint64_t> hist_base;
 };
-// Stable radix sort of d_key[0, n) (n + 2 words; overwritten) over the key bits that vary: `varying` = OR of the keys ^ AND of the keys.
-inline void sort_resident(uint64_t* d_key, uint64_t n, uint64_t varying, hipStream_t s, ResidentOrder* o) {
-    uint32_t shifts[8];
-    o->n_passes = n ? sortc::plan_passes(varying, shifts, &o->key_bits) : 0;
+// The buffers of an order over n resident records
+inline void alloc_resident_order(uint64_t n, ResidentOrder* o) {
     o->key2 = DevBuf<uint64_t>((size_t)n + 2);
     o->val = DevBuf<uint32_t>((size_t)n + 2);
     o->val2 = DevBuf<uint32_t>((size_t)n + 2);
-    EventTimer t_sort;
+    o->hist = DevBuf<uint32_t>(radix_hist_entries(n) + 4);
+    o->hist_base = DevBuf<uint64_t>(radix_hist_entries(n) + 4);
+}
+// K9b from the permutation the order holds: d_key[i] (n + 2 words; overwritten) is the key of record o->perm[i].  The passes over the
+// key bits that vary (`varying` = OR of the keys ^ AND of the keys) are queued on s; o->perm, key_bits and n_passes follow.
+inline void queue_resident_passes(uint64_t* d_key, uint64_t n, uint64_t varying, hipStream_t s, ResidentOrder* o) {
+    uint32_t shifts[8], bits = 0;
+    const uint32_t n_passes = n ? sortc::plan_passes(varying, shifts, &bits) : 0;
     uint64_t* keys[2] = {d_key, o->key2.p};
     uint32_t* vals[2] = {o->val.p, o->val2.p};
-    int at = 0;
-    DevBuf<uint32_t> d_hist(radix_hist_entries(n) + 4);
-    DevBuf<uint64_t> d_hist_base(radix_hist_entries(n) + 4);
+    int at = 0, vat = o->perm == o->val2.p ? 1 : 0;
+    for (uint32_t p = 0; p < n_passes; ++p, at ^= 1, vat ^= 1)
+        launch_radix_pass(keys[at], vals[vat], keys[at ^ 1], vals[vat ^ 1], n, shifts[p], o->hist.p, o->hist_base.p, s);
+    o->perm = vals[vat];
+    o->key_bits += bits;
+    o->n_passes += n_passes;
+}
+// Stable radix sort of d_key[0, n) (n + 2 words; overwritten), the key of record i at d_key[i], over the key bits that vary.
+inline void sort_resident(uint64_t* d_key, uint64_t n, uint64_t varying, hipStream_t s, ResidentOrder* o) {
+    alloc_resident_order(n, o);
+    EventTimer t_sort;
     t_sort.start(s);
-    launch_iota(vals[0], n, s);
-    for (uint32_t p = 0; p < o->n_passes; ++p, at ^= 1)
-        launch_radix_pass(keys[at], vals[at], keys[at ^ 1], vals[at ^ 1], n, shifts[p], d_hist.p, d_hist_base.p, s);
+    launch_iota(o->val.p, n, s);
+    o->perm = o->val.p;
+    queue_resident_passes(d_key, n, varying, s, o);
     t_sort.stop(s);
     SBX_HIP(hipStreamSynchronize(s));
-    o->perm = vals[at];
+    o->hist.release();
+    o->hist_base.release();
     o->ms_sort = t_sort.ms();
+}
+// The same sort for a key of several words, one call per word, the least significant first: begin_resident_order sets the identity,
+// every continue_resident_order sorts by one more word (d_key[i]: that word of record o->perm[i]) and keeps the order records with
+// equal words had.  key_bits, n_passes and ms_sort add up over the calls.
+inline void begin_resident_order(uint64_t n, hipStream_t s, ResidentOrder* o) {
+    alloc_resident_order(n, o);
+    EventTimer t;
+    t.start(s);
+    launch_iota(o->val.p, n, s);
+    t.stop(s);
+    o->perm = o->val.p;
+    o->ms_sort += t.ms();
+}
+inline void continue_resident_order(uint64_t* d_key, uint64_t n, uint64_t varying, hipStream_t s, ResidentOrder* o) {
+    EventTimer t;
+    t.start(s);
+    queue_resident_passes(d_key, n, varying, s, o);
+    t.stop(s);
+    o->ms_sort += t.ms();
 }
 
 // ---- the writer ----

@@ -9,6 +9,11 @@
 // "Unrecognized option X", and so is a short flag with text attached (`-ux`).  Without -o the output is the input with its extension replaced by "sorted.bam"
 // (setExtension, sort.d:535); an output that is the input is refused (protectFromOverwrite); like the reference's BamWriter, an
 // output whose name ends in ".bam" gets a "<out>.bai" next to it.  Errors: "sbx-sort: <message>" on stderr and exit status 1.
+//
+// Built once more with -DSBX_SORT_BY_NAME=1 this file is `sbx-nsort`: everything above, and -n / --sort-by-name, -N /
+// --natural-sort and -M / --match-mates are taken (sbx_sort_bam_by_name; no .bai for a name order).  -n with -N is the reference's
+// "only one of -n and -N and -s parameters can be provided", -M alone its "-M option only works in combination with either -n or
+// -N" (sort.d:524-532); --sort-picard stays refused.  Without -n and -N it is sbx-sort.  Errors: "sbx-nsort: <message>".
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,12 +23,25 @@
 #include "../../include/sbx_depth.h"
 #include "cli_opts.hpp"
 
+#ifndef SBX_SORT_BY_NAME
+#define SBX_SORT_BY_NAME 0
+#endif
+#if SBX_SORT_BY_NAME
+#define SBX_SORT_PROG "sbx-nsort"
+#else
+#define SBX_SORT_PROG "sbx-sort"
+#endif
+
 namespace {
 
 void usage() {
-    fputs("Usage: sbx-sort [options] <input.bam>\n"
+    fputs("Usage: " SBX_SORT_PROG " [options] <input.bam>\n"
           "\n"
+#if SBX_SORT_BY_NAME
+          "Sorts a BAM file by coordinate or by read name, as `sambamba sort` does, on the GPU.\n"
+#else
           "Sorts a BAM file by coordinate, as `sambamba sort` does, on the GPU.\n"
+#endif
           "\n"
           "Options: -o, --out=OUTPUTFILE\n"
           "               output file name; if not provided, the result is written to a file with .sorted.bam extension\n"
@@ -33,13 +51,24 @@ void usage() {
           "               keep only reads that satisfy FILTER\n"
           "         -m, --memory-limit=LIMIT, --tmpdir=TMPDIR, -u, --uncompressed-chunks, -t, --nthreads=NTHREADS, -p, --show-progress\n"
           "               accepted for compatibility; the file is sorted in GPU memory\n"
+#if SBX_SORT_BY_NAME
+          "         -n, --sort-by-name\n"
+          "               sort by read name instead of coordinate (lexicographical order)\n"
+          "         -N, --natural-sort\n"
+          "               sort by read name instead of coordinate (so-called 'natural' sort as in samtools)\n"
+          "         -M, --match-mates\n"
+          "               pull mates of the same alignment together when sorting by read name\n"
+          "         --sort-picard\n"
+          "               not supported\n",
+#else
           "         -n, --sort-by-name, -N, --natural-sort, --sort-picard, -M, --match-mates\n"
           "               not supported: coordinate order only\n",
+#endif
           stderr);
 }
 
 int die(const std::string& m) {
-    fprintf(stderr, "sbx-sort: %s\n", m.c_str());
+    fprintf(stderr, SBX_SORT_PROG ": %s\n", m.c_str());
     return 1;
 }
 
@@ -62,10 +91,12 @@ bool ends_with(const std::string& s, const char* t) {
 int main(int argc, char** argv) {
     std::string out, filter_str, level_str;
     std::vector<std::string> files;
-    // long name, short name, takes a value, what it does: 0 ignored, 1 out, 2 level, 3 filter, 4 refused
+    bool by_name = false, natural = false, match_mates = false;
+    // long name, short name, takes a value, what it does: 0 ignored, 1 out, 2 level, 3 filter, 4 refused, 5 -n, 6 -N, 7 -M
+    constexpr int kN = SBX_SORT_BY_NAME ? 5 : 4, kNat = SBX_SORT_BY_NAME ? 6 : 4, kM = SBX_SORT_BY_NAME ? 7 : 4;
     static const sbx::OptSpec opts[] = {
-        {"memory-limit", 'm', true, 0}, {"tmpdir", 0, true, 0}, {"out", 'o', true, 1}, {"sort-by-name", 'n', false, 4},
-        {"natural-sort", 'N', false, 4}, {"sort-picard", 0, false, 4}, {"match-mates", 'M', false, 4},
+        {"memory-limit", 'm', true, 0}, {"tmpdir", 0, true, 0}, {"out", 'o', true, 1}, {"sort-by-name", 'n', false, kN},
+        {"natural-sort", 'N', false, kNat}, {"sort-picard", 0, false, 4}, {"match-mates", 'M', false, kM},
         {"uncompressed-chunks", 'u', false, 0}, {"compression-level", 'l', true, 2}, {"show-progress", 'p', false, 0},
         {"nthreads", 't', true, 0}, {"filter", 'F', true, 3},
     };
@@ -80,12 +111,18 @@ int main(int argc, char** argv) {
         if (t.kind == sbx::OptToken::Unknown || (t.attached && !t.spec->takes_value && t.arg[1] != '-')) return die("Unrecognized option " + t.arg);
         const sbx::OptSpec& o = *t.spec;
         const std::string shown = o.sht ? std::string("-") + o.sht + " / --" + o.lng : std::string("--") + o.lng;
-        if (o.id == 4) return die("option " + shown + " is not supported: sbx-sort sorts by coordinate only");
+        if (o.id == 4)
+            return die("option " + shown + (SBX_SORT_BY_NAME ? " is not supported" : " is not supported: sbx-sort sorts by coordinate only"));
+        if (o.id == 5) { by_name = true; continue; }
+        if (o.id == 6) { natural = true; continue; }
+        if (o.id == 7) { match_mates = true; continue; }
         if (t.missing) return die("Missing value for argument " + t.arg + ".");
         if (o.id == 1) out = t.value;
         else if (o.id == 2) level_str = t.value;
         else if (o.id == 3) filter_str = t.value;
     }
+    if (by_name && natural) return die("only one of -n and -N and -s parameters can be provided");
+    if (match_mates && !(by_name || natural)) return die("-M option only works in combination with either -n or -N");
     if (files.empty()) {
         usage();
         return 1;
@@ -103,8 +140,10 @@ int main(int argc, char** argv) {
     sbx_filter filter;
     const bool have_filter = !filter_str.empty();
     if (have_filter && sbx_compile_filter(filter_str.c_str(), &filter, err, sizeof err) != SBX_OK) return die(err);
-    const int rc = sbx_sort_bam(in.c_str(), out.c_str(), have_filter ? &filter : nullptr, level, ends_with(out, ".bam") ? 1 : 0, -1, nullptr, err,
-                                sizeof err);
+    const sbx_filter* fp = have_filter ? &filter : nullptr;
+    const int rc = by_name || natural
+                       ? sbx_sort_bam_by_name(in.c_str(), out.c_str(), fp, level, natural ? 2 : 1, match_mates ? 1 : 0, -1, nullptr, err, sizeof err)
+                       : sbx_sort_bam(in.c_str(), out.c_str(), fp, level, ends_with(out, ".bam") ? 1 : 0, -1, nullptr, err, sizeof err);
     if (rc != SBX_OK) return die(err);
     return 0;
 }

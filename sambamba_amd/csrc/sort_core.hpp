@@ -198,11 +198,11 @@ inline std::string serialise_header(const ParsedHeader& h, const std::string& so
     return out;
 }
 
-// The header of the sorted file: the sorting order was set to coordinate (sambamba/sort.d:294-298).
-inline bool sort_header_text(const char* text, size_t n, std::string* out, std::string* why) {
+// The header of the sorted file: the sorting order was set to `so` (sambamba/sort.d:294-298: coordinate, or queryname for the name orders).
+inline bool sort_header_text(const char* text, size_t n, std::string* out, std::string* why, const char* so = "coordinate") {
     ParsedHeader h;
     if (!parse_header(text, n, &h, why)) return false;
-    *out = serialise_header(h, "coordinate");
+    *out = serialise_header(h, so);
     return true;
 }
 

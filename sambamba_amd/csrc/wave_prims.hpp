@@ -1,5 +1,5 @@
 // wave_prims.hpp -- the wave and workgroup idioms the kernels of the resident-store commands share: sort.hip (K9), markdup.hip (K10),
-// merge.hip (K11) and view.hip (K12), and no other file.  (The depth path -- inflate, index, depth, reduce, mates, format, deflate,
+// merge.hip (K11), view.hip (K12) and namesort.hip (K14), and no other file.  (The depth path -- inflate, index, depth, reduce, mates, format, deflate,
 // flagstat -- keeps private helpers with similar names and does not include this.)  A wave is 64 lanes; a workgroup a whole number
 // of waves, its threads numbered by threadIdx.x.
 #pragma once

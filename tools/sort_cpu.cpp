@@ -2,7 +2,9 @@
 // orders the records by the key sbx-sort uses (sambamba_amd/csrc/sort_core.hpp), and zlib deflates the sorted stream in blocks of
 // 0xFF00 bytes at the given level, again on N threads.  The header is copied as it is (the text is not re-serialised): a timing tool,
 // not a test oracle (tests/sort_ref.py is that).  Prints the wall time of its phases on stderr.
-//   make sort_cpu && ./sort_cpu [-t N] [-l LEVEL] [--shuffle SEED] in.bam out.bam
+//   make sort_cpu && ./sort_cpu [-t N] [-l LEVEL] [-n | -N] [-M] [--shuffle SEED] in.bam out.bam
+// -n / -N / -M order by read name as `sbx-nsort` does: std::stable_sort under the comparators of namesort_core.hpp (-M: HI tag, then
+// flag, among equal names); the yardstick of K14.
 // --shuffle SEED writes the records in a seeded random order instead of the sorted one (makes the unsorted input of a measurement).
 #include <zlib.h>
 
@@ -18,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "../sambamba_amd/csrc/namesort_core.hpp"
 #include "../sambamba_amd/csrc/sort_core.hpp"
 
 namespace {
@@ -35,17 +38,21 @@ void parallel_for(size_t n, int threads, F&& f) {
 
 int main(int argc, char** argv) {
     int threads = 1, level = 1;
-    bool shuffle = false;
+    bool shuffle = false, match_mates = false;
+    uint32_t name_order = 0;
     uint64_t seed = 0;
     std::vector<std::string> files;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "-t" && i + 1 < argc) threads = std::max(1, atoi(argv[++i]));
         else if (a == "-l" && i + 1 < argc) level = atoi(argv[++i]);
+        else if (a == "-n") name_order = sbx::nsc::kOrderLex;
+        else if (a == "-N") name_order = sbx::nsc::kOrderNatural;
+        else if (a == "-M") match_mates = true;
         else if (a == "--shuffle" && i + 1 < argc) { shuffle = true; seed = strtoull(argv[++i], nullptr, 10); }
         else files.push_back(a);
     }
-    if (files.size() != 2) { fprintf(stderr, "usage: sort_cpu [-t N] [-l LEVEL] [--shuffle SEED] in.bam out.bam\n"); return 1; }
+    if (files.size() != 2) { fprintf(stderr, "usage: sort_cpu [-t N] [-l LEVEL] [-n | -N] [-M] [--shuffle SEED] in.bam out.bam\n"); return 1; }
     const double t0 = now();
     // ---- read the file, find the blocks ----
     FILE* f = fopen(files[0].c_str(), "rb");
@@ -98,7 +105,32 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> perm(off.size());
     std::iota(perm.begin(), perm.end(), 0u);
     if (shuffle) { std::mt19937_64 rng(seed); std::shuffle(perm.begin(), perm.end(), rng); }
-    else std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    else if (name_order) {
+        namespace nsc = sbx::nsc;
+        // the -M word of every record once (a record whose tags cannot be read counts as HI 0: a timing tool)
+        std::vector<uint64_t> mate(off.size(), 0);
+        if (match_mates)
+            for (size_t i = 0; i < off.size(); ++i) {
+                const uint8_t* rec = u.data() + off[i];
+                nsc::NameFrame f;
+                int32_t hi = 0;
+                if (nsc::name_frame(rec, 4 + (uint64_t)rd32(rec), &f)) {
+                    if (f.aux_ok) nsc::find_hi(rec, f.aux, 4 + (uint64_t)rd32(rec), &hi);
+                    mate[i] = nsc::mate_word(hi, f.flag);
+                }
+            }
+        std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
+            const uint8_t *p = u.data() + off[a], *q = u.data() + off[b];
+            const uint32_t np = p[12] ? p[12] - 1u : 0u, nq = q[12] ? q[12] - 1u : 0u;
+            if (name_order == nsc::kOrderNatural) {
+                const int c = nsc::mixed_str_compare(p + 36, np, q + 36, nq);
+                return c != 0 ? c < 0 : mate[a] < mate[b];
+            }
+            if (nsc::name_less(p + 36, np, q + 36, nq)) return true;
+            if (nsc::name_less(q + 36, nq, p + 36, np)) return false;
+            return mate[a] < mate[b];
+        });
+    } else std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
     const double t3 = now();
     // ---- the sorted stream ----
     std::vector<uint8_t> s(total);
