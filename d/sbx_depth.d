@@ -130,6 +130,14 @@ extern (C) nothrow @nogc {
                      sbx_view_stats* stats, char* err, size_t errlen);
     int sbx_view_num_filter(const(char)* text, ushort* flags_set, ushort* flags_unset);
     int sbx_view_reference_info(sbx_ctx*, char* out_, size_t cap, size_t* out_len);
+    struct sbx_import_stats {
+        ulong n_lines; ulong n_records; ulong text_bytes; ulong stream_bytes; ulong compressed_bytes;
+        uint n_chunks; uint reserved;
+        double ms_index; double ms_measure; double ms_emit; double ms_deflate; double ms_total_wall;
+    }
+    // `sambamba view -S -f bam`: in_path "-" is stdin, out_path null or "-" stdout
+    int sbx_import_sam(const(char)* in_path, const(char)* out_path, const(char)* pg_command_line, int level, int with_index, int device,
+                       sbx_import_stats* stats, char* err, size_t errlen);
     int sbx_inflate_blocks(const(ubyte)* comp, const(ulong)* comp_off, const(uint)* comp_len, const(uint)* isize,
                            uint n_blocks, ubyte* out_, const(ulong)* out_off, char* err, size_t errlen);
     sbx_ctx* sbx_open(const(char*)* bam_paths, int n_bams, int device, char* err, size_t errlen);

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -357,6 +357,31 @@ int sbx_view_num_filter(const char* text, uint16_t* flags_set, uint16_t* flags_u
  * prints it -- the quote in front of the brace included: [{"name":"chr1","length":1000}] is what a correct writer would print,
  * ["{name":"chr1","length":1000}] plus a newline is what comes out.  Lengths as sbx_sort_header_text. */
 int sbx_view_reference_info(sbx_ctx*, char* out, size_t cap, size_t* out_len);
+
+/* ---- import: SAM text in, BAM out (`sambamba view -S -f bam in.sam -o out.bam`, view.d:216-218, 292-311) ----
+ * The lines are parsed on the device (K15) by the grammar of parseAlignmentLine (BioD bio/etc/ragel/sam_alignment.rl): QNAME, FLAG,
+ * RNAME, POS, MAPQ, CIGAR, RNEXT, PNEXT, TLEN, SEQ, QUAL and the tags A i f Z H B; the bin is reg2bin of POS and the reference bases
+ * of the CIGAR, integer tags take the smallest type, floats are the correctly rounded binary32 of their text (what glibc's strtof
+ * returns).  in_path: a path or "-" (stdin); it is read sequentially, so a pipe works.  The header is the run of lines starting with
+ * '@' at the top; the output header is what sbx_view_bam writes for a BAM with this text and these @SQ lines (pg_command_line as there).
+ * out_path NULL or "-": stdout (never indexed).  level as sbx_bgzf_compress; with_index != 0: out_path + ".bai" too.
+ * Deliberate divergences: the reference recovers silently from an invalid field (it skips to the next tab, drops the tag, fills
+ * the qualities with 0xFF); here any line outside the grammar -- a QUAL whose length is not SEQ's (other than a lone '*'), a
+ * reference name the header lacks, a '\r', an empty line included -- fails the call with SBX_EFORMAT, the message carrying the
+ * number of such lines and the 1-based number of the first, and no output file is left.  Two texts sbx_view_sam writes and the
+ * grammar lacks are read: "B:<type>," (an array without elements) and "-nan" (0xFFC00000).
+ * The records are resident on the device as for sbx_sort_bam: SBX_ENOMEM, naming the bytes needed and the bytes free, when the store
+ * cannot grow; more than 2^32 records are SBX_EUNSUPPORTED; an out_path that is the input is SBX_EINVAL.  The text is uploaded in
+ * chunks cut at line ends (64 MiB, not tuned; SBX_IMPORT_CHUNK_BYTES overrides it for tests); the output does not depend on the size.
+ * n_lines: lines behind the header; text_bytes: their bytes.  Milliseconds are device time (index = K15a, measure = K15b + scan,
+ * emit = K15c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index. */
+typedef struct {
+    uint64_t n_lines, n_records, text_bytes, stream_bytes, compressed_bytes;
+    uint32_t n_chunks, reserved;
+    double ms_index, ms_measure, ms_emit, ms_deflate, ms_total_wall;
+} sbx_import_stats;
+int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_command_line, int level, int with_index, int device,
+                   sbx_import_stats* stats, char* err, size_t errlen);
 
 /* ---- engine seam ------------------------------------------------------------ */
 

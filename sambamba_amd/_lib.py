@@ -14,6 +14,7 @@ _MERGE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-merge")
 _VIEW_CLI_PATH = os.path.join(HERE, "csrc", "sbx-view")
 _SAM_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sam")
 _NSORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-nsort")
+_IMPORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-import")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -113,6 +114,11 @@ class ViewStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_regions", "n_sort_passes", "n_batches", "reserved")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_select", "ms_emit", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
 
+class ImportStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_lines", "n_records", "text_bytes", "stream_bytes", "compressed_bytes")] +
+                [(k, C.c_uint32) for k in ("n_chunks", "reserved")] +
+                [(k, C.c_double) for k in ("ms_index", "ms_measure", "ms_emit", "ms_deflate", "ms_total_wall")])
+
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
 
 EXPORTS = [
@@ -125,6 +131,7 @@ EXPORTS = [
     "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
     "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_num_filter", "sbx_view_reference_info",
+    "sbx_import_sam",
 ]
 
 _lib = None
@@ -164,6 +171,10 @@ def sam_cli_path():
 
 def nsort_cli_path():
     return _NSORT_CLI_PATH
+
+
+def import_cli_path():
+    return _IMPORT_CLI_PATH
 
 
 def lib():
@@ -239,6 +250,7 @@ def lib():
                                C.c_int, C.c_int, C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
     L.sbx_view_num_filter.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
     L.sbx_view_reference_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sbx_import_sam.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(ImportStats), C.c_char_p, C.c_size_t]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_depth_base_tile_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -255,7 +267,7 @@ def lib():
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
                      ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats),
-                     ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats)):
+                     ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -719,6 +731,21 @@ def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, r
     if rc != 0:
         raise SbxError(rc, err.value.decode())
     return {k: getattr(st, k) for k, _ in ViewStats._fields_ if k != "reserved"}
+
+
+def import_sam(in_path, out_path, level=-1, index=False, command_line=None, device=-1):
+    """sbx_import_sam (`sambamba view -S -f bam`): the SAM text at in_path ("-": stdin) parsed on the device and written to out_path
+    ("-": stdout) as a BAM -- index=True also writes out_path + ".bai", command_line is the CL field of the @PG line that is added
+    (None: no @PG).  A line outside the grammar raises SbxError(-3) naming how many there are and the first.  Returns the fields
+    of sbx_import_stats as a dict."""
+    L = lib()
+    st = ImportStats()
+    err = C.create_string_buffer(512)
+    cl = command_line.encode() if command_line is not None else None
+    rc = L.sbx_import_sam(in_path.encode(), out_path.encode(), cl, int(level), int(index), device, C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: getattr(st, k) for k, _ in ImportStats._fields_ if k != "reserved"}
 
 
 def view_reference_info(path, device=-1):
