@@ -138,6 +138,22 @@ extern (C) nothrow @nogc {
     // `sambamba view -S -f bam`: in_path "-" is stdin, out_path null or "-" stdout
     int sbx_import_sam(const(char)* in_path, const(char)* out_path, const(char)* pg_command_line, int level, int with_index, int device,
                        sbx_import_stats* stats, char* err, size_t errlen);
+    // `sambamba index [-c]`: check_bins == 0 is sbx_build_index
+    int sbx_index_bam(const(char)* bam_path, const(char)* bai_path, int check_bins, int device, char* err, size_t errlen);
+    struct sbx_fixbins_stats {
+        ulong n_records; ulong n_bins_changed; ulong inflated_bytes; ulong stream_bytes; ulong compressed_bytes;
+        uint n_batches; uint reserved;
+        double ms_inflate; double ms_index; double ms_bins; double ms_gather; double ms_deflate; double ms_total_wall;
+    }
+    // `sambamba fixbins`
+    int sbx_fixbins(const(char)* in_path, const(char)* out_path, int level, int device, sbx_fixbins_stats* stats, char* err, size_t errlen);
+    struct sbx_fasta_stats {
+        ulong n_sequences; ulong n_lines; ulong n_bytes;
+        uint n_chunks; uint reserved;
+        double ms_lines; double ms_segments; double ms_total_wall;
+    }
+    // `sambamba index -F`
+    int sbx_index_fasta(const(char)* fasta_path, const(char)* fai_path, int device, sbx_fasta_stats* stats, char* err, size_t errlen);
     int sbx_inflate_blocks(const(ubyte)* comp, const(ulong)* comp_off, const(uint)* comp_len, const(uint)* isize,
                            uint n_blocks, ubyte* out_, const(ulong)* out_off, char* err, size_t errlen);
     sbx_ctx* sbx_open(const(char*)* bam_paths, int n_bams, int device, char* err, size_t errlen);

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -382,6 +382,46 @@ typedef struct {
 } sbx_import_stats;
 int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_command_line, int level, int with_index, int device,
                    sbx_import_stats* stats, char* err, size_t errlen);
+
+/* ---- index, fixbins (`sambamba index [-c] [-F]`, index.d; `sambamba fixbins`, fixbins.d) ----
+ * sbx_index_bam with check_bins == 0 is sbx_build_index: the same file, the same errors.  With check_bins != 0 (`index -c`) the same
+ * pass (K16a) also compares the stored bin of every PLACED record (ref_id >= 0 and pos >= 0) with reg2bin(pos, pos + basesCovered())
+ * in the reference's int arithmetic (bin.d:82-92; an unmapped read covers nothing).  A mismatch fails the call with SBX_EFORMAT and
+ * the reference's message for the first such record in file order -- "Bin in read with name 'NAME' is set incorrectly (B instead of
+ * expected E)" -- followed by "; N record(s) of the file have a wrong bin"; no .bai is written.  Deliberate divergences: the
+ * reference never checks the first placed read of a file (IndexBuilder.put returns before checkThatBinIsCorrect while _first_read is
+ * set), here it is checked; an unsorted file is SBX_ENOTSORTED as without the check, whichever of the two faults comes first. */
+int sbx_index_bam(const char* bam_path, const char* bai_path, int check_bins, int device, char* err, size_t errlen);
+/* `sambamba fixbins`: every record of in_path, placed or not, mapped or not, gets bin = reg2bin(pos, pos + basesCovered()) (4680 for
+ * ref_id -1, pos -1); nothing else changes: header text and reference list are the input's byte for byte (no @PG), the records keep
+ * their order, an EOF block ends the file.  level as sbx_bgzf_compress.  The records are resident on the device as for sbx_markdup
+ * (K16b patches the two bytes in the store): SBX_ENOMEM when they do not fit, SBX_EINVAL when out_path is the input, SBX_EFORMAT for
+ * a record whose name and CIGAR run past its block_size, SBX_EUNSUPPORTED for more than 2^32 records.  On failure no output file is
+ * left.  Milliseconds are device time (bins = K16b), ms_total_wall the wall clock of the call. */
+typedef struct {
+    uint64_t n_records, n_bins_changed, inflated_bytes, stream_bytes, compressed_bytes;
+    uint32_t n_batches, reserved;
+    double ms_inflate, ms_index, ms_bins, ms_gather, ms_deflate, ms_total_wall;
+} sbx_fixbins_stats;
+int sbx_fixbins(const char* in_path, const char* out_path, int level, int device, sbx_fixbins_stats* stats, char* err, size_t errlen);
+/* `sambamba index -F` (buildFai, BioD bio/std/file/fai.d:78-101): the .fai of a FASTA file, its lines found and added up on the
+ * device (K17).  The line terminator is "\r\n" when the first line ends in it, "\n" otherwise, for the whole file; the text is split
+ * at it only (a last line without terminator is a line; with "\n" a '\r' is a byte of its line).  A line starting with '>' opens a
+ * sequence whose name is the bytes between '>' and the first space (a tab does not end it; it may be empty) and whose offset is
+ * that of the byte behind the line's terminator; any other line adds its length to the sequence, the first one that is not empty
+ * sets the line length.  One row per sequence: name, length, offset, line length, line length + terminator, tab separated.
+ * Deliberate divergences: an empty file gives an empty .fai (the reference dies); a first line that is no header is SBX_EFORMAT
+ * naming line 1 (the reference indexes an empty array); with "\r\n" a '\n' without '\r' in front of it is SBX_EFORMAT with the number
+ * of such line ends and the 1-based number of the first line that ends so (the reference counts it as sequence).  On failure no
+ * .fai is left.  The text is uploaded in chunks cut at multiples of 16 bytes, not at line ends (64 MiB, not tuned;
+ * SBX_FASTA_CHUNK_BYTES, at least 16, overrides it for tests); the output does not depend on the size.  Milliseconds are device time
+ * (lines = K15a's newline count, scan and line starts; segments = K17's header flags, their scan and the reduction). */
+typedef struct {
+    uint64_t n_sequences, n_lines, n_bytes;
+    uint32_t n_chunks, reserved;
+    double ms_lines, ms_segments, ms_total_wall;
+} sbx_fasta_stats;
+int sbx_index_fasta(const char* fasta_path, const char* fai_path, int device, sbx_fasta_stats* stats, char* err, size_t errlen);
 
 /* ---- engine seam ------------------------------------------------------------ */
 

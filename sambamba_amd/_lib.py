@@ -15,6 +15,8 @@ _VIEW_CLI_PATH = os.path.join(HERE, "csrc", "sbx-view")
 _SAM_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sam")
 _NSORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-nsort")
 _IMPORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-import")
+_INDEX_CLI_PATH = os.path.join(HERE, "csrc", "sbx-index")
+_FIXBINS_CLI_PATH = os.path.join(HERE, "csrc", "sbx-fixbins")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -119,6 +121,16 @@ class ImportStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_chunks", "reserved")] +
                 [(k, C.c_double) for k in ("ms_index", "ms_measure", "ms_emit", "ms_deflate", "ms_total_wall")])
 
+class FixbinsStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_records", "n_bins_changed", "inflated_bytes", "stream_bytes", "compressed_bytes")] +
+                [(k, C.c_uint32) for k in ("n_batches", "reserved")] +
+                [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_bins", "ms_gather", "ms_deflate", "ms_total_wall")])
+
+class FastaStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_sequences", "n_lines", "n_bytes")] +
+                [(k, C.c_uint32) for k in ("n_chunks", "reserved")] +
+                [(k, C.c_double) for k in ("ms_lines", "ms_segments", "ms_total_wall")])
+
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
 
 EXPORTS = [
@@ -132,6 +144,7 @@ EXPORTS = [
     "sbx_merge_bam", "sbx_merge_header_text",
     "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_num_filter", "sbx_view_reference_info",
     "sbx_import_sam",
+    "sbx_index_bam", "sbx_fixbins", "sbx_index_fasta",
 ]
 
 _lib = None
@@ -175,6 +188,14 @@ def nsort_cli_path():
 
 def import_cli_path():
     return _IMPORT_CLI_PATH
+
+
+def index_cli_path():
+    return _INDEX_CLI_PATH
+
+
+def fixbins_cli_path():
+    return _FIXBINS_CLI_PATH
 
 
 def lib():
@@ -251,6 +272,9 @@ def lib():
     L.sbx_view_num_filter.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
     L.sbx_view_reference_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_import_sam.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(ImportStats), C.c_char_p, C.c_size_t]
+    L.sbx_index_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    L.sbx_fixbins.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(FixbinsStats), C.c_char_p, C.c_size_t]
+    L.sbx_index_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(FastaStats), C.c_char_p, C.c_size_t]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_depth_base_tile_device.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -267,7 +291,8 @@ def lib():
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
                      ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats),
-                     ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats)):
+                     ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats),
+                     ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -316,13 +341,43 @@ def write_bam(path, stream, level=6, with_index=True, device=-1):
         raise SbxError(rc, err.value.decode())
 
 
-def build_index(bam_path, bai_path=None, device=-1):
-    """sbx_build_index (`sambamba index`): writes bai_path (default: bam_path + ".bai")."""
+def build_index(bam_path, bai_path=None, device=-1, check_bins=False):
+    """sbx_build_index (`sambamba index`): writes bai_path (default: bam_path + ".bai").  check_bins=True is `index -c`
+    (sbx_index_bam): a placed record whose stored bin is not reg2bin of its position and CIGAR raises SbxError(-3) with the
+    reference's message for the first such record and their number, and no index is written."""
     L = lib()
     err = C.create_string_buffer(512)
-    rc = L.sbx_build_index(bam_path.encode(), (bai_path or bam_path + ".bai").encode(), device, err, 512)
+    out = (bai_path or bam_path + ".bai").encode()
+    if check_bins:
+        rc = L.sbx_index_bam(bam_path.encode(), out, 1, device, err, 512)
+    else:
+        rc = L.sbx_build_index(bam_path.encode(), out, device, err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
+
+
+def fixbins(in_path, out_path, level=-1, device=-1):
+    """sbx_fixbins (`sambamba fixbins`): in_path written to out_path with the bin of every record set to reg2bin of its position and
+    CIGAR; nothing else changes.  Returns the fields of sbx_fixbins_stats as a dict."""
+    L = lib()
+    st = FixbinsStats()
+    err = C.create_string_buffer(512)
+    rc = L.sbx_fixbins(in_path.encode(), out_path.encode(), int(level), device, C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: getattr(st, k) for k, _ in FixbinsStats._fields_ if k != "reserved"}
+
+
+def index_fasta(path, fai_path=None, device=-1):
+    """sbx_index_fasta (`sambamba index -F`): the .fai of the FASTA file at `path` (default: path + ".fai"), its lines found and
+    added up on the device.  Returns the fields of sbx_fasta_stats as a dict."""
+    L = lib()
+    st = FastaStats()
+    err = C.create_string_buffer(512)
+    rc = L.sbx_index_fasta(path.encode(), (fai_path or path + ".fai").encode(), device, C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: getattr(st, k) for k, _ in FastaStats._fields_ if k != "reserved"}
 
 
 def flagstat(path, device=-1):

@@ -6,6 +6,8 @@
 
 #include "bai_parallel.hpp"
 #include "bai_writer.hpp"
+#include "bins.hpp"
+#include "bins_core.hpp"
 #include "deflate_core.hpp"
 #include "engine_ctx.hpp"
 #include "engine_stream.hpp"
@@ -35,7 +37,10 @@ int sbx_bgzf_compress(const uint8_t* in, size_t n, int level, int with_eof, int 
 }
 
 // ---- index-mode passes: the record stream of one file in batches (sbx_build_index, sbx_flagstat) ---------------------------------
-int sbx_build_index(const char* bam_path, const char* bai_path, int device, char* err, size_t errlen) {
+extern "C++" {
+namespace {
+// the one body of sbx_build_index and sbx_index_bam; check_bins: `index -c` (K16a next to the pass, bins.hip)
+int build_index_impl(const char* bam_path, const char* bai_path, bool check_bins, int device, char* err, size_t errlen) {
     return run_entry(err, errlen, [&] {
         if (!bam_path || !bai_path) throw Error(SBX_EINVAL, "null argument");
         Standalone ctx;
@@ -60,7 +65,36 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
         // SBX_BAI_HOST=1, IndexBuilder's loop restated on the host (bai_writer.hpp) over descriptors copied back record by record.
         std::vector<uint8_t> bytes;
         uint32_t n_batches = 0;
+        // -c: the count of placed records with a wrong bin and the number of the first, over the batches of a pass; the first one's
+        // name and bins are fetched from the batch that holds it (the next batch overwrites U)
+        DevBuf<unsigned long long> d_bin_acc(kBinCheckWords);
+        unsigned long long bin_acc[kBinCheckWords] = {0, kBinCheckNone};
+        std::string bin_complaint;
+        auto check_batch = [&](uint64_t nrec, uint64_t rec_base, uint64_t u_end) {
+            launch_check_bins(c->U(), c->d_desc.p, c->d_rec_ref.p, nrec, rec_base, u_end, d_bin_acc.p, s);
+            SBX_HIP(hipMemcpyAsync(bin_acc, d_bin_acc.p, sizeof bin_acc, hipMemcpyDeviceToHost, s));
+            SBX_HIP(hipStreamSynchronize(s));
+            if (!bin_acc[kBinCheckBad] || !bin_complaint.empty()) return;
+            const uint64_t i = bin_acc[kBinCheckFirst] - rec_base;
+            if (i >= nrec) throw Error(SBX_EFORMAT, "internal error: the first record with a wrong bin is not in its batch");
+            RecDesc d;
+            SBX_HIP(hipMemcpy(&d, c->d_desc.p + i, sizeof d, hipMemcpyDeviceToHost));
+            std::vector<uint8_t> rec(36 + (size_t)d.l_name + 4 * (size_t)d.n_cigar);
+            SBX_HIP(hipMemcpy(rec.data(), c->U() + d.rec_off, rec.size(), hipMemcpyDeviceToHost));
+            uint32_t want = 0;
+            binc::expected_bin(rec.data(), binc::load32(rec.data()), &want);
+            const char* name = (const char*)rec.data() + 36;
+            bin_complaint = "Bin in read with name '" + std::string(name, strnlen(name, d.l_name)) + "' is set incorrectly (" +
+                            std::to_string(binc::stored_bin(rec.data())) + " instead of expected " + std::to_string(want) + ")";
+        };
         auto pass = [&](bool on_device) -> bool {
+            if (check_bins) {
+                bin_acc[kBinCheckBad] = 0; bin_acc[kBinCheckFirst] = kBinCheckNone;
+                bin_complaint.clear();
+                SBX_HIP(hipMemcpyAsync(d_bin_acc.p, bin_acc, sizeof bin_acc, hipMemcpyHostToDevice, s));
+                SBX_HIP(hipStreamSynchronize(s));
+            }
+            uint64_t checked_base = 0;
             // serial consumer
             VoffCursor vc(bt.coffset.data(), bt.out_off.data(), nbk, file_end_coff);
             BaiBuilder bb(n_ref);
@@ -95,6 +129,7 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
                 SBX_HIP(hipMemsetAsync(d_scalars.p + kBaiFirstVo, 0xFF, 8, s));
             }
             const bool whole = for_each_record_batch(c, batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+                if (check_bins) { check_batch(nrec, checked_base, next - base); checked_base += nrec; }
                 if (on_device) {
                     const uint64_t cap = nrec / 4 + 4096;
                     d_runs.ensure((size_t)cap);
@@ -165,6 +200,10 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
         bool on_device = !host_only;
         if (on_device && !pass(true)) on_device = false;
         if (!on_device) pass(false);
+        // (an unsorted file has left through the serial builder's refusal by now, whichever fault comes first in the file)
+        if (check_bins && bin_acc[kBinCheckBad])
+            throw Error(SBX_EFORMAT, bin_complaint + "; " + std::to_string(bin_acc[kBinCheckBad]) +
+                                         (bin_acc[kBinCheckBad] == 1 ? " record of the file has a wrong bin" : " records of the file have a wrong bin"));
         if (getenv("SBX_TIMING"))
             fprintf(stderr, "[sbx] build_index: %u batch(es) of <= %llu inflated bytes, records consumed %s\n", n_batches, (unsigned long long)batch_u,
                     on_device ? "on the device" : "by the serial builder on the host");
@@ -173,6 +212,16 @@ int sbx_build_index(const char* bam_path, const char* bai_path, int device, char
         const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
         if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + bai_path);
     });
+}
+}  // namespace
+}  // extern "C++"
+
+int sbx_build_index(const char* bam_path, const char* bai_path, int device, char* err, size_t errlen) {
+    return build_index_impl(bam_path, bai_path, false, device, err, errlen);
+}
+
+int sbx_index_bam(const char* bam_path, const char* bai_path, int check_bins, int device, char* err, size_t errlen) {
+    return build_index_impl(bam_path, bai_path, check_bins != 0, device, err, errlen);
 }
 
 // `sambamba flagstat` (computeFlagStatistics, flagstat.d:31-58): one pass like sbx_build_index's -- index mode, no filter, no sort
