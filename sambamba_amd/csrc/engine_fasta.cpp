@@ -3,17 +3,14 @@
 //
 // The host probes the first line for its terminator, then reads the file front to back in chunks of a fixed size -- cut at multiples
 // of 16 bytes, not at line ends: an unwrapped chromosome is one line of hundreds of megabytes.  A reader thread fills two pinned
-// buffers in turn (StageSync / StageThreads, cli_common.hpp) while the device works on the chunk before: upload into one of two device
-// buffers, K15a (line starts), K17a (header lines counted), K17b (one FastaSeg per header line).  Back come the segments -- 32 bytes
+// buffers in turn (ChunkReader, engine_chunks.hpp) while the device works on the chunk before: upload into one of two device
+// buffers, K15a (index_lines), K17a (header lines counted), K17b (one FastaSeg per header line).  Back come the segments -- 32 bytes
 // per header line of the chunk --, two line starts and two counters; fastac::FastaCarry (fasta_core.hpp) folds them into the records
 // and keeps what crosses the chunk's ends.  The names are cut on the host from the pinned text.  Every chunk is looked at even after a
 // bad line end was met, so that the refusal names how many there are.
 #include <sys/stat.h>
 
-#include <thread>
-
-#include "cli_common.hpp"
-#include "engine_ctx.hpp"
+#include "engine_chunks.hpp"
 #include "fasta.hpp"
 
 namespace {
@@ -29,12 +26,6 @@ uint64_t fasta_chunk_bytes() {
     if (*end || v < 16) return kDefault;
     return std::min<uint64_t>(v & ~15ull, fastac::kChunkLimit);
 }
-
-struct FastaSlot {
-    PinnedBuf<uint8_t> text;
-    size_t bytes = 0;
-    bool full = false, last = false;        // last: the input is used up, this slot holds nothing
-};
 
 struct FileCloser {
     FILE* f;
@@ -89,55 +80,30 @@ int sbx_index_fasta(const char* fasta_path, const char* fai_path, int device, sb
         DevBuf<fastac::FastaSeg> d_seg;
         DevBuf<unsigned long long> d_acc(kFastaAccWords);
         {
-            FastaSlot slot[2];
-            StageSync sync("reading the FASTA text failed");
-            StageThreads threads(sync);
-            threads.start([&] {
-                try {
-                    SBX_HIP(hipSetDevice(dev));
-                    for (uint32_t k = 0;; ++k) {
-                        FastaSlot& c = slot[k & 1u];
-                        if (!sync.wait_for([&] { return !c.full; })) return;
-                        c.text.ensure((size_t)chunk + 64);
-                        size_t bytes = 0;
-                        while (bytes < chunk) {
-                            const size_t got = fread(c.text.p + bytes, 1, (size_t)chunk - bytes, in.f);
-                            if (!got) {
-                                if (ferror(in.f)) throw Error(SBX_EIO, std::string("error reading ") + fasta_path);
-                                break;
-                            }
-                            bytes += got;
-                        }
-                        sync.mark([&] { c.bytes = bytes; c.last = bytes == 0; c.full = true; });
-                        if (!bytes) return;
+            ChunkReader reader(dev, "reading the FASTA text failed", [&](PinnedBuf<uint8_t>& text) {
+                text.ensure((size_t)chunk + 64);
+                size_t bytes = 0;
+                while (bytes < chunk) {
+                    const size_t got = fread(text.p + bytes, 1, (size_t)chunk - bytes, in.f);
+                    if (!got) {
+                        if (ferror(in.f)) throw Error(SBX_EIO, std::string("error reading ") + fasta_path);
+                        break;
                     }
-                } catch (const Error& e) { sync.fail(e.what(), e.code); }
-                catch (const std::exception& e) { sync.fail(e.what()); }
+                    bytes += got;
+                }
+                return bytes;
             });
             EventTimer t_lines, t_segments;
-            for (uint32_t k = 0;; ++k) {
-                FastaSlot& c = slot[k & 1u];
-                if (!sync.wait_for([&] { return c.full; })) throw Error(sync.failure_code, sync.failure);
-                if (c.last) break;
-                const uint64_t size = c.bytes;
-                DevBuf<uint8_t>& d_t = d_text[k & 1u];
+            uint32_t k = 0;
+            while (ChunkSlot* c = reader.next()) {
+                const uint64_t size = c->bytes;
+                DevBuf<uint8_t>& d_t = d_text[k++ & 1u];
                 d_t.ensure((size_t)size + 64);
-                SBX_HIP(hipMemcpyAsync(d_t.p, c.text.p, size, hipMemcpyHostToDevice, s));
-                const ImportText t{d_t.p, size};
+                SBX_HIP(hipMemcpyAsync(d_t.p, c->text.p, size, hipMemcpyHostToDevice, s));
+                const TextChunk t{d_t.p, size};
                 fastac::ChunkResult r;
                 r.size = size;
-                // K15a
-                const uint32_t tiles = import_text_tiles(size);
-                d_tile.ensure(tiles + 2);
-                t_lines.start(s);
-                launch_import_count_newlines(t, d_tile.p, s);
-                launch_import_scan64(d_tile.p, tiles, s);
-                SBX_HIP(hipMemcpyAsync(&r.n_newlines, d_tile.p + tiles, 8, hipMemcpyDeviceToHost, s));
-                SBX_HIP(hipStreamSynchronize(s));
-                if (r.n_newlines > size) throw Error(SBX_EFORMAT, "internal error: more line ends than bytes");
-                d_line_start.ensure((size_t)r.n_newlines + 2);
-                launch_import_line_starts(t, d_tile.p, d_line_start.p, s);
-                t_lines.stop(s);
+                r.n_newlines = index_lines(t, d_tile, d_line_start, t_lines, s, [] {});       // K15a
                 if (r.n_newlines) {
                     SBX_HIP(hipMemcpyAsync(&r.first_start, d_line_start.p + 1, 8, hipMemcpyDeviceToHost, s));
                     SBX_HIP(hipMemcpyAsync(&r.last_start, d_line_start.p + r.n_newlines, 8, hipMemcpyDeviceToHost, s));
@@ -147,13 +113,13 @@ int sbx_index_fasta(const char* fasta_path, const char* fai_path, int device, sb
                 double ms_segments = 0;
                 if (n_inner) {
                     const FastaLines lines{t, d_line_start.p, r.n_newlines, carry.crlf ? 1u : 0u};
-                    const uint32_t groups = fasta_groups(n_inner);
+                    const uint32_t groups = group_count(n_inner);
                     d_group.ensure(groups + 2);
                     const unsigned long long acc0[kFastaAccWords] = {0, fastac::kNoLine};
                     SBX_HIP(hipMemcpyAsync(d_acc.p, acc0, sizeof acc0, hipMemcpyHostToDevice, s));
                     t_segments.start(s);
                     launch_fasta_count_headers(lines, d_group.p, s);
-                    launch_import_scan64(d_group.p, groups, s);
+                    launch_scan64(d_group.p, groups, 0, s);
                     uint64_t n_headers = 0;
                     SBX_HIP(hipMemcpyAsync(&n_headers, d_group.p + groups, 8, hipMemcpyDeviceToHost, s));
                     SBX_HIP(hipStreamSynchronize(s));
@@ -178,13 +144,12 @@ int sbx_index_fasta(const char* fasta_path, const char* fai_path, int device, sb
                 }
                 if (r.n_newlines && (r.first_start == 0 || r.first_start > size || r.last_start > size || r.last_start < r.first_start))
                     throw Error(SBX_EFORMAT, "internal error: line starts outside their chunk");
-                carry.consume(c.text.p, r);
-                sync.mark([&] { c.full = false; });            // the names are cut: the reader may fill this slot again
+                carry.consume(c->text.p, r);
+                reader.release(c);                              // the names are cut: the reader may fill this slot again
                 st.ms_lines += t_lines.ms();
                 st.ms_segments += ms_segments;
                 ++st.n_chunks;
             }
-            threads.regular = true;
         }
         carry.finish();
         if (carry.failed()) throw Error(SBX_EFORMAT, carry.complaint(fasta_path));

@@ -2,14 +2,12 @@
 // bio/std/hts/sam/reader.d, the line parser parseAlignmentLine of sam_alignment.rl) with the lines parsed on the device.
 //
 // The host reads the input sequentially (a pipe works): the header lines, then the record text in chunks cut at line ends.  A reader
-// thread fills two pinned buffers in turn (StageSync / StageThreads, cli_common.hpp), so that reading chunk k + 1 overlaps the device's
-// work on chunk k: upload into one of two device buffers, K15a (line starts), K15b (record lengths, the bad lines counted), a 64-bit
+// thread fills two pinned buffers in turn (ChunkReader, engine_chunks.hpp), so that reading chunk k + 1 overlaps the device's
+// work on chunk k: upload into one of two device buffers, K15a (index_lines), K15b (record lengths, the bad lines counted), a 64-bit
 // scan, K15c (records into the resident store of engine_store.hpp, which grows with grow_keeping).  Every chunk is measured even after
 // a bad line was met, so that the refusal names how many there are; nothing is emitted from then on.  The output tail is the one of
 // the other resident-store commands: the identity permutation through write_store_output, then index_written_bam.
-#include <thread>
-
-#include "cli_common.hpp"
+#include "engine_chunks.hpp"
 #include "engine_store.hpp"
 #include "markdup_core.hpp"
 #include "samparse.hpp"
@@ -129,13 +127,6 @@ void print_timing(const sbx_import_stats& st, uint64_t chunk_bytes) {
             st.ms_deflate, st.ms_total_wall);
 }
 
-// one of the two pinned buffers between the reader thread and the device thread
-struct ChunkSlot {
-    PinnedBuf<uint8_t> text;
-    size_t bytes = 0;
-    bool full = false, last = false;        // last: the input is used up, this slot holds nothing
-};
-
 }  // namespace
 
 extern "C" {
@@ -168,21 +159,18 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
         const std::vector<uint8_t> header = bam_header_bytes(text, refs);
         OutputGuard out_file(path, to_stdout);
 
-        // the reference names on the device: offsets, bytes, the hash slots
+        // the reference names on the device, and their hash slots
         std::vector<std::string> names;
-        std::vector<uint32_t> ref_off{0};
-        std::string ref_bytes;
-        for (const RefSeq& q : refs) { names.push_back(q.name); ref_bytes += q.name; ref_off.push_back((uint32_t)ref_bytes.size()); }
+        for (const RefSeq& q : refs) names.push_back(q.name);
         const std::vector<uint32_t> slots = sampc::ref_table_slots(names);
         Stream stream;
         stream.create();
         hipStream_t s = stream.get();
-        DevBuf<uint32_t> d_ref_off(ref_off.size()), d_slots(slots.size() + 1);
-        DevBuf<char> d_ref_bytes(ref_bytes.size() + 1);
-        SBX_HIP(hipMemcpyAsync(d_ref_off.p, ref_off.data(), ref_off.size() * 4, hipMemcpyHostToDevice, s));
+        DeviceRefNames d_names;
+        upload_ref_names(refs, s, &d_names);
+        DevBuf<uint32_t> d_slots(slots.size() + 1);
         if (!slots.empty()) SBX_HIP(hipMemcpyAsync(d_slots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, s));
-        if (!ref_bytes.empty()) SBX_HIP(hipMemcpyAsync(d_ref_bytes.p, ref_bytes.data(), ref_bytes.size(), hipMemcpyHostToDevice, s));
-        const sampc::RefTable table{d_slots.p, (uint32_t)slots.size(), d_ref_off.p, d_ref_bytes.p};
+        const sampc::RefTable table{d_slots.p, (uint32_t)slots.size(), d_names.off.p, d_names.bytes.p};
         DevBuf<unsigned long long> d_acc(kImportAccWords);
         {
             const unsigned long long acc0[kImportAccWords] = {0, kImportNoBadLine, 0, 0};
@@ -199,64 +187,38 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
         uint64_t store_used = 0, n_rec = 0;
         unsigned long long acc[kImportAccWords] = {0, kImportNoBadLine, 0, 0};
         {
-            ChunkSlot slot[2];
-            StageSync sync("reading the SAM text failed");
-            StageThreads threads(sync);
-            threads.start([&] {
-                try {
-                    SBX_HIP(hipSetDevice(dev));
-                    for (uint32_t k = 0;; ++k) {
-                        ChunkSlot& c = slot[k & 1u];
-                        if (!sync.wait_for([&] { return !c.full; })) return;
-                        size_t bytes = 0;
-                        if (!in.next_chunk(budget, &bytes)) throw Error(SBX_EIO, std::string("error reading ") + in_path);
-                        if (bytes) {
-                            c.text.ensure(bytes + 64);
-                            memcpy(c.text.p, in.at(), bytes);
-                            in.consume(bytes);
-                        }
-                        sync.mark([&] { c.bytes = bytes; c.last = bytes == 0; c.full = true; });
-                        if (!bytes) return;
-                    }
-                } catch (const Error& e) { sync.fail(e.what(), e.code); }
-                catch (const std::exception& e) { sync.fail(e.what()); }
+            ChunkReader reader(dev, "reading the SAM text failed", [&](PinnedBuf<uint8_t>& text) {
+                size_t bytes = 0;
+                if (!in.next_chunk(budget, &bytes)) throw Error(SBX_EIO, std::string("error reading ") + in_path);
+                if (bytes) {
+                    text.ensure(bytes + 64);
+                    memcpy(text.p, in.at(), bytes);
+                    in.consume(bytes);
+                }
+                return bytes;
             });
             EventTimer t_index, t_measure, t_emit;
-            for (uint32_t k = 0;; ++k) {
-                ChunkSlot& c = slot[k & 1u];
-                if (!sync.wait_for([&] { return c.full; })) throw Error(sync.failure_code, sync.failure);
-                if (c.last) break;
-                const uint64_t size = c.bytes;
-                const bool open_end = c.text.p[size - 1] != '\n';
-                DevBuf<uint8_t>& d_t = d_text[k & 1u];
+            uint32_t k = 0;
+            while (ChunkSlot* c = reader.next()) {
+                const uint64_t size = c->bytes;
+                const bool open_end = c->text.p[size - 1] != '\n';
+                DevBuf<uint8_t>& d_t = d_text[k++ & 1u];
                 d_t.ensure((size_t)size + 64);
-                SBX_HIP(hipMemcpyAsync(d_t.p, c.text.p, size, hipMemcpyHostToDevice, s));
-                const ImportText t{d_t.p, size};
-                // K15a
-                const uint32_t tiles = import_text_tiles(size);
-                d_tile.ensure(tiles + 2);
-                t_index.start(s);
-                launch_import_count_newlines(t, d_tile.p, s);
-                launch_import_scan64(d_tile.p, tiles, s);
-                uint64_t n_newlines = 0;
-                SBX_HIP(hipMemcpyAsync(&n_newlines, d_tile.p + tiles, 8, hipMemcpyDeviceToHost, s));
-                SBX_HIP(hipStreamSynchronize(s));
-                sync.mark([&] { c.full = false; });            // the upload is done: the reader may fill this slot again
-                if (n_newlines > size) throw Error(SBX_EFORMAT, "internal error: more line ends than bytes");
+                SBX_HIP(hipMemcpyAsync(d_t.p, c->text.p, size, hipMemcpyHostToDevice, s));
+                const TextChunk t{d_t.p, size};
+                // K15a; the reader may fill the slot again as soon as the upload is done
+                const uint64_t n_newlines = index_lines(t, d_tile, d_line_start, t_index, s, [&] { reader.release(c); });
                 const uint64_t n_lines = n_newlines + (open_end ? 1u : 0u);
                 if (n_rec + n_lines > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-                d_line_start.ensure((size_t)n_newlines + 2);
-                launch_import_line_starts(t, d_tile.p, d_line_start.p, s);
-                t_index.stop(s);
                 // K15b and the offsets
                 grow_keeping(d_len, (size_t)n_rec, (size_t)(n_rec + n_lines) + 2, s);
                 grow_keeping(d_off, (size_t)n_rec, (size_t)(n_rec + n_lines) + 2, s);
-                const uint32_t groups = import_line_groups(n_lines);
+                const uint32_t groups = group_count(n_lines);
                 d_group.ensure(groups + 2);
                 const ImportLines lines{t, d_line_start.p, n_newlines, n_lines, n_header_lines + st.n_lines + 1, table};
                 t_measure.start(s);
                 launch_import_measure(lines, d_len.p + n_rec, d_group.p, d_acc.p, s);
-                launch_import_scan64(d_group.p, groups, s);
+                launch_scan64(d_group.p, groups, 0, s);
                 t_measure.stop(s);
                 uint64_t chunk_record_bytes = 0;
                 SBX_HIP(hipMemcpyAsync(&chunk_record_bytes, d_group.p + groups, 8, hipMemcpyDeviceToHost, s));
@@ -280,7 +242,7 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
                     grow_keeping(d_store, (size_t)store_used, (size_t)need, s);
                 }
                 t_emit.start(s);
-                launch_import_offsets(d_len.p + n_rec, d_group.p, n_lines, store_used, d_off.p + n_rec, s);
+                launch_group_offsets(d_len.p + n_rec, d_group.p, n_lines, store_used, d_off.p + n_rec, s);
                 launch_import_emit(lines, d_len.p + n_rec, d_off.p + n_rec, d_store.p, d_acc.p, s);
                 t_emit.stop(s);
                 SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
@@ -290,7 +252,6 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
                 store_used += chunk_record_bytes;
                 n_rec += n_lines;
             }
-            threads.regular = true;
         }
         if (acc[kImportAccBad])
             throw Error(SBX_EFORMAT, "malformed SAM text in " + std::string(in_path) + ": " + std::to_string(acc[kImportAccBad]) +

@@ -172,7 +172,7 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
         sorter.reserve(n);
         EventTimer t_pair, t_groups;
         t_pair.start(s);
-        launch_md_fill32(d_mate.p, kMdNone, n, s);
+        launch_fill32(d_mate.p, kMdNone, n, s);
         SBX_HIP(hipMemsetAsync(d_dup.p, 0, (size_t)n + 2, s));
         const uint64_t n_pairable = compact(kMdPredPairable, d_cls.p, d_mate.p, n, d_cnt, d_base, sorter.idx(), s);
         sorter.sort_by(d_hash.p, n_pairable, d_acc.p, s);

@@ -149,7 +149,7 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
         unsigned long long acc[kMergeAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
         SBX_HIP(hipMemcpy(d_acc.p, acc, sizeof acc, hipMemcpyHostToDevice));
         // scratch of K11, per batch
-        DevBuf<uint32_t> b_new_len, b_keep, b_patch_at, b_patch_entry, b_iota;
+        DevBuf<uint32_t> b_new_len, b_keep, b_patch_at, b_patch_entry;
         DevBuf<uint64_t> b_key, b_len_base, b_keep_base, b_tile_sum;
         const double w1 = wall_now();
 
@@ -200,13 +200,13 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
                 } else {
                     const size_t m = (size_t)nrec + 2;
                     b_new_len.ensure(m); b_keep.ensure(m); b_key.ensure(m); b_patch_at.ensure(2 * m); b_patch_entry.ensure(2 * m);
-                    b_len_base.ensure(m); b_keep_base.ensure(m); b_iota.ensure(m); b_tile_sum.ensure(len_tiles(nrec) + 2);
+                    b_len_base.ensure(m); b_keep_base.ensure(m); b_tile_sum.ensure(len_tiles(nrec) + 2);
                     MergeArgs a{};
                     a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base;
                     a.n_ref_own = in[k].n_ref; a.n_ref_merged = n_ref; a.ref_map = d_ref_map.p;
                     a.table = RenameTable{d_entries.p, d_blob.p, (uint32_t)in[k].entries.size()};
                     a.use_filter = use_filter ? 1u : 0u;
-                    a.b = MergeBatch{b_new_len.p, b_keep.p, b_key.p, b_patch_at.p, b_patch_entry.p, b_len_base.p, b_keep_base.p, b_iota.p, b_tile_sum.p};
+                    a.b = MergeBatch{b_new_len.p, b_keep.p, b_key.p, b_patch_at.p, b_patch_entry.p, b_len_base.p, b_keep_base.p, b_tile_sum.p};
                     a.acc = d_acc.p;
                     a.store = d_store.p; a.store_at = store_at; a.out_base = n_kept;
                     a.key = d_key.p; a.off = d_off.p; a.len = d_len.p;
@@ -243,7 +243,7 @@ int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_input
             throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(n_in) + " records received a key");
         const uint64_t n = n_kept;
         b_new_len.release(); b_keep.release(); b_key.release(); b_patch_at.release(); b_patch_entry.release();
-        b_len_base.release(); b_keep_base.release(); b_iota.release(); b_tile_sum.release();
+        b_len_base.release(); b_keep_base.release(); b_tile_sum.release();
         const double w2 = wall_now();
 
         // ---- K9b: the merge ----

@@ -57,7 +57,7 @@ struct NameKeys {
         EventTimer t;
         t.start(s);
         launch_name_key_measure(a, s);
-        launch_count_scan(words.p, (uint32_t)n, word_base.p, nullptr, 0, s);
+        launch_count_scan(words.p, (uint32_t)n, word_base.p, s);
         t.stop(s);
         uint64_t batch_words = 0;
         SBX_HIP(hipMemcpyAsync(&batch_words, word_base.p + n, 8, hipMemcpyDeviceToHost, s));

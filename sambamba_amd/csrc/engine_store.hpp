@@ -150,6 +150,22 @@ inline void continue_resident_order(uint64_t* d_key, uint64_t n, uint64_t varyin
     o->ms_sort += t.ms();
 }
 
+// ---- the reference names on the device (K13, K15): name r is bytes[off[r], off[r + 1]) ----
+struct DeviceRefNames {             // (the host side stays alive with the copies queued from it)
+    std::vector<uint32_t> h_off{0};
+    std::string h_bytes;
+    DevBuf<uint32_t> off;
+    DevBuf<char> bytes;
+    int32_t n() const { return (int32_t)h_off.size() - 1; }
+};
+inline void upload_ref_names(const std::vector<RefSeq>& refs, hipStream_t s, DeviceRefNames* d) {
+    for (const RefSeq& q : refs) { d->h_bytes += q.name; d->h_off.push_back((uint32_t)d->h_bytes.size()); }
+    d->off.alloc(d->h_off.size());
+    d->bytes.alloc(d->h_bytes.size() + 1);
+    SBX_HIP(hipMemcpyAsync(d->off.p, d->h_off.data(), d->h_off.size() * 4, hipMemcpyHostToDevice, s));
+    if (!d->h_bytes.empty()) SBX_HIP(hipMemcpyAsync(d->bytes.p, d->h_bytes.data(), d->h_bytes.size(), hipMemcpyHostToDevice, s));
+}
+
 // ---- the writer ----
 struct OutputPlan {
     uint64_t total = 0;             // bytes of the stream: header + records

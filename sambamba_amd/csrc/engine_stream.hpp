@@ -60,7 +60,7 @@ void bgzf_compress_pieces(size_t n, size_t piece_blocks, int level, bool pinned,
         launch_bgzf_deflate(d_in.p, bytes, nb, level, d_slots.p, d_tab.p, d_work.p, d_len.p, s);
         t_def.stop(s);
         t_pack.start(s);
-        launch_count_scan(d_len.p, nb, d_off.p, nullptr, 0, s);
+        launch_count_scan(d_len.p, nb, d_off.p, s);
         launch_pack_blocks(d_slots.p, d_len.p, d_off.p, nb, d_out.p, s);
         t_pack.stop(s);
         uint64_t total = 0;

@@ -64,7 +64,7 @@ static uint64_t format_measure(sbx_ctx* c, const FormatArgs& a, uint32_t* n_chun
     c->d_fmt_len.ensure(n_chunks);
     c->d_fmt_off.ensure((size_t)n_chunks + 1);
     launch_format_measure(a, n_chunks, c->d_fmt_len.p, s);
-    launch_count_scan(c->d_fmt_len.p, n_chunks, c->d_fmt_off.p, nullptr, 0, s);
+    launch_count_scan(c->d_fmt_len.p, n_chunks, c->d_fmt_off.p, s);
     HostResults& R = results(c);
     SBX_HIP(hipMemcpyAsync(&R.last_state, c->d_fmt_off.p + n_chunks, 8, hipMemcpyDeviceToHost, s));
     SBX_HIP(hipStreamSynchronize(s));

@@ -152,8 +152,8 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
         a.count = d_count.p; a.group_entries = d_group_entries.p; a.group_records = d_group_records.p;
         launch_view_select(a, s);
         if (nrec) {
-            launch_count_scan(d_group_entries.p, groups, d_group_entry_base.p, nullptr, 0, s);
-            launch_count_scan(d_group_records.p, groups, d_group_record_base.p, nullptr, 0, s);
+            launch_count_scan(d_group_entries.p, groups, d_group_entry_base.p, s);
+            launch_count_scan(d_group_records.p, groups, d_group_record_base.p, s);
         }
         t_a.stop(s);
         SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
@@ -356,34 +356,28 @@ int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* fi
         std::string text, why;
         if (with_header && !mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why))
             throw Error(SBX_EFORMAT, "SAM header: " + why);
-        // the reference names, once: offsets + bytes
-        std::vector<uint32_t> ref_off{0};
-        std::string ref_bytes;
-        for (const RefSeq& q : c->hdr.refs) { ref_bytes += q.name; ref_off.push_back((uint32_t)ref_bytes.size()); }
-
+        const std::vector<RefSeq> refs = c->hdr.refs;       // (select_resident lets go of the context)
         sbx_view_stats st{};
         SelectedRecords r;
         select_resident(c, opts, threshold, sel, text.size(), 48 + 12, &r, &st);       // (+ length and offset of every line)
         const uint64_t n = r.n;
         hipStream_t s = r.stream.get();
-        DevBuf<uint32_t> d_ref_off(ref_off.size());
-        DevBuf<char> d_ref_bytes(ref_bytes.size() + 1);
-        SBX_HIP(hipMemcpyAsync(d_ref_off.p, ref_off.data(), ref_off.size() * 4, hipMemcpyHostToDevice, s));
-        if (!ref_bytes.empty()) SBX_HIP(hipMemcpyAsync(d_ref_bytes.p, ref_bytes.data(), ref_bytes.size(), hipMemcpyHostToDevice, s));
-        const SamEntries e{r.store.p, r.off.p, r.len.p, r.perm.p, n, samc::RefNames{d_ref_off.p, d_ref_bytes.p, (int32_t)ref_off.size() - 1}};
+        DeviceRefNames names;
+        upload_ref_names(refs, s, &names);
+        const SamEntries e{r.store.p, r.off.p, r.len.p, r.perm.p, n, samc::RefNames{names.off.p, names.bytes.p, names.n()}};
 
         // ---- K13a over all entries, the offsets of the lines, the pieces ----
-        const uint32_t groups = sam_groups(n);
-        DevBuf<uint32_t> d_line_len((size_t)n + 2), d_group_sum(groups + 2), d_n_pieces(1);
-        DevBuf<uint64_t> d_group_base(groups + 2), d_line_off((size_t)n + 2);
+        const uint32_t groups = group_count(n);
+        DevBuf<uint32_t> d_line_len((size_t)n + 2), d_n_pieces(1);
+        DevBuf<uint64_t> d_group(groups + 2), d_line_off((size_t)n + 2);
         DevBuf<unsigned long long> d_acc(kSamAccWords);
         SBX_HIP(hipMemsetAsync(d_acc.p, 0, kSamAccWords * sizeof(unsigned long long), s));
         EventTimer t_a;
         t_a.start(s);
-        launch_sam_measure(e, d_line_len.p, d_group_sum.p, d_acc.p, s);
+        launch_sam_measure(e, d_line_len.p, d_group.p, d_acc.p, s);
         if (n) {
-            launch_count_scan(d_group_sum.p, groups, d_group_base.p, nullptr, 0, s);
-            launch_sam_offsets(d_line_len.p, d_group_base.p, n, d_line_off.p, s);
+            launch_scan64(d_group.p, groups, 0, s);
+            launch_group_offsets(d_line_len.p, d_group.p, n, 0, d_line_off.p, s);
         }
         t_a.stop(s);
         const uint64_t budget = sam_piece_bytes();

@@ -239,54 +239,7 @@ __global__ __launch_bounds__(64) void k_chain_repair(const uint8_t* __restrict__
     if (lane == 0) *n_rewalked += rewalked;
 }
 
-// ---- scan of the per-block counts (single workgroup, 3 phases; n_blocks is ~1e5..1e6) -----------
-constexpr int kScanThreads = 1024;
-__global__ __launch_bounds__(kScanThreads) void k_count_scan(const uint32_t* __restrict__ count, uint32_t n,
-                                                              uint64_t* __restrict__ base) {
-    // tiles of 4 x kScanThreads counts, four consecutive ones per thread (one 16-byte load, coalesced); a shuffle scan inside the
-    // wavefront, the sixteen wave totals through LDS, the running sum carried from tile to tile.  (Until round 6 every thread summed its
-    // own stretch of n / 1024 counts, one strided load at a time, around a Hillis-Steele scan of the 1024 partials: 58 us for the 32 k
-    // chunk lengths of a piece of K6's text, a sixth of what formatting the piece took.)
-    __shared__ uint64_t wtot[kScanThreads / 64];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-    uint64_t carry = 0;
-    for (uint32_t i0 = 0; i0 < n; i0 += 4u * kScanThreads) {
-        const uint32_t i = i0 + 4u * t;
-        uint32_t v[4] = {0, 0, 0, 0};
-        if (i + 4u <= n) {
-            const uint4 q = *(const uint4*)(count + i);
-            v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        } else {
-            for (uint32_t k = 0; k < 4u; ++k) if (i + k < n) v[k] = count[i + k];
-        }
-        const uint64_t s = (uint64_t)v[0] + v[1] + v[2] + v[3];
-        uint64_t incl = s;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t o = (uint64_t)__shfl_up((unsigned long long)incl, d, 64);
-            if ((int)lane >= d) incl += o;
-        }
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        uint64_t before = carry, tile = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kScanThreads / 64; ++w) {
-            const uint64_t x = wtot[w];
-            if (w < wv) before += x;
-            tile += x;
-        }
-        uint64_t run = before + incl - s;
-#pragma unroll
-        for (uint32_t k = 0; k < 4u; ++k) {
-            if (i + k < n) base[i + k] = run;
-            run += v[k];
-        }
-        carry += tile;
-        __syncthreads();
-    }
-    if (t == 0) base[n] = carry;
-}
-
+constexpr int kScanThreads = 1024;      // (the scan of counts itself: launch_count_scan, scan.hip)
 // ---- aux fields, the -F program, RG lookup -------------------------------------------------------
 // first aux field with the given key (BamRead.opIndex, read.d:1070-1087; skipValue read.d:1219-1230):
 // returns its type character and value pointer, 0 when absent or when the tag area is malformed before it
@@ -1372,13 +1325,6 @@ void launch_chain_repair(const uint8_t* d_U, const uint64_t* d_out_off, const ui
                          uint32_t* d_count, uint32_t* d_n_rewalked, hipStream_t stream) {
     hipLaunchKernelGGL(k_chain_repair, dim3(1), dim3(64), 0, stream, d_U, d_out_off, d_isize, d_run_of, d_runs, n_blocks, from,
                        d_entry, d_exit, d_count, d_n_rewalked);
-    SBX_HIP(hipGetLastError());
-}
-
-size_t count_scan_tmp_bytes(uint32_t) { return 0; }
-
-void launch_count_scan(const uint32_t* d_count, uint32_t n_blocks, uint64_t* d_base, void*, size_t, hipStream_t stream) {
-    hipLaunchKernelGGL(k_count_scan, dim3(1), dim3(kScanThreads), 0, stream, d_count, n_blocks, d_base);
     SBX_HIP(hipGetLastError());
 }
 

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/sbx_depth.h"
+#include "scan.hpp"
 
 namespace sbx {
 
@@ -173,10 +174,6 @@ void launch_rewalk_mismatched(const IndexArgs& a, uint32_t* d_n_changed, hipStre
 void launch_chain_repair(const uint8_t* d_U, const uint64_t* d_out_off, const uint32_t* d_isize, const uint32_t* d_run_of,
                          const ChainRun* d_runs, uint32_t n_blocks, uint32_t from, uint64_t* d_entry, uint64_t* d_exit,
                          uint32_t* d_count, uint32_t* d_n_rewalked, hipStream_t stream);
-// exclusive scan of per-chunk counts -> d_base[n + 1] (used by K6)
-void launch_count_scan(const uint32_t* d_count, uint32_t n_blocks, uint64_t* d_base, void* d_tmp, size_t tmp_bytes,
-                       hipStream_t stream);
-size_t count_scan_tmp_bytes(uint32_t n_blocks);
 // compact the tiles that have work: active[] = tile ids, slot_of[t] = index into active or ~0u;
 // d_n_active[0] = number of active tiles, [1] = how many of them have >= 65536 records
 void launch_tile_compact(const uint32_t* d_tile_lo, const uint32_t* d_tile_hi, uint32_t n_tiles, uint32_t deep_thr, uint32_t* d_active,

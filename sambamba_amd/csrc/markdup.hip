@@ -150,11 +150,6 @@ __global__ __launch_bounds__(kMdThreads) void k_md_gather_keys(const uint64_t* _
     }
 }
 
-__global__ __launch_bounds__(kMdThreads) void k_md_fill32(uint32_t* __restrict__ d, uint32_t v, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * kMdThreads + threadIdx.x;
-    if (i < n) d[i] = v;
-}
-
 // ---- K10b -----------------------------------------------------------------------------------------------------------------
 // name and RG string of two records of the store, byte for byte (readsArePaired; an absent RG is the empty string)
 __device__ bool md_same_key(const uint8_t* store, const MdRecords& r, uint32_t x, uint32_t y) {
@@ -286,15 +281,13 @@ void launch_md_compact(MdPred pred, const uint8_t* d_c, const uint32_t* d_mate, 
     if (!n) return;
     const uint32_t groups = md_groups(n);
     md_launch(k_md_compact_count, n, stream, (uint32_t)pred, d_c, d_mate, n, d_group_count);
-    launch_count_scan(d_group_count, groups, d_group_base, nullptr, 0, stream);
+    launch_count_scan(d_group_count, groups, d_group_base, stream);
     md_launch(k_md_compact_write, n, stream, (uint32_t)pred, d_c, d_mate, n, (const uint64_t*)d_group_base, d_out);
 }
 
 void launch_md_gather_keys(const uint64_t* d_word, const uint32_t* d_idx, uint64_t n, uint64_t* d_key, unsigned long long* d_acc, hipStream_t stream) {
     md_launch(k_md_gather_keys, n, stream, d_word, d_idx, n, d_key, d_acc);
 }
-
-void launch_md_fill32(uint32_t* d, uint32_t v, uint64_t n, hipStream_t stream) { md_launch(k_md_fill32, n, stream, d, v, n); }
 
 void launch_md_pair_runs(const uint64_t* d_hash, const uint32_t* d_rec, uint64_t n, const uint8_t* d_store, const MdRecords& r, uint32_t* d_mate,
                          hipStream_t stream) {

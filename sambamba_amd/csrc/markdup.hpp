@@ -55,7 +55,6 @@ void launch_md_compact(MdPred pred, const uint8_t* d_cls_or_keep, const uint32_t
 
 // d_key[j] = d_word[d_idx[j]] for j < n; ORs / ANDs them into acc[kMdAccOr / kMdAccAnd] (the digits a radix sort may skip)
 void launch_md_gather_keys(const uint64_t* d_word, const uint32_t* d_idx, uint64_t n, uint64_t* d_key, unsigned long long* d_acc, hipStream_t stream);
-void launch_md_fill32(uint32_t* d, uint32_t v, uint64_t n, hipStream_t stream);
 
 // K10b: (d_hash, d_rec) sorted by hash, runs in file order.  Inside a run of equal hashes the records whose name and RG bytes are equal
 // pair up 1st with 2nd, 3rd with 4th ...: d_mate[record] = its partner (kMdNone stays for a leftover).

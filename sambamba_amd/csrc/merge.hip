@@ -11,7 +11,7 @@
 //                          (sort_core.hpp) of the REWRITTEN record: merged reference id, merged number of references.  A record
 //                          that fails a check is counted and the call ends with SBX_EFORMAT.  With -F the verdict K2 left in
 //                          RecDesc::pad decides, on the record as it is in its input.
-//   scans                  launch_sorted_offsets (sort.hip) over the new lengths and over the keep flags: where a record starts
+//   scans                  launch_sorted_offsets (scan.hip) over the new lengths and over the keep flags: where a record starts
 //                          behind the store's fill, and its record number behind the records kept before.
 //   K11b k_merge_rewrite   sixteen lanes per record (K9c's partition).  The first 36 bytes go out byte by byte with block_size,
 //                          ref_id and next_ref_id replaced (-1 stays -1; a next_ref_id outside the input's dictionary stays as it
@@ -188,9 +188,8 @@ void launch_merge_describe(const MergeArgs& a, hipStream_t stream) {
     if (!a.n) return;
     hipLaunchKernelGGL(k_merge_describe, dim3((uint32_t)((a.n + kMergeThreads - 1) / kMergeThreads)), dim3(kMergeThreads), 0, stream, a);
     SBX_HIP(hipGetLastError());
-    launch_iota(a.b.iota, a.n, stream);
-    launch_sorted_offsets(a.b.new_len, a.b.iota, a.n, 0, a.b.tile_sum, a.b.len_base, stream);
-    launch_sorted_offsets(a.b.keep, a.b.iota, a.n, 0, a.b.tile_sum, a.b.keep_base, stream);
+    launch_sorted_offsets(a.b.new_len, nullptr, a.n, 0, a.b.tile_sum, a.b.len_base, stream);
+    launch_sorted_offsets(a.b.keep, nullptr, a.n, 0, a.b.tile_sum, a.b.keep_base, stream);
 }
 
 void launch_merge_rewrite(const MergeArgs& a, hipStream_t stream) {

@@ -32,7 +32,6 @@ struct MergeBatch {
     uint32_t* patch_entry;          // [2 n] its RenameEntry, kMergeNone: no (further) patch; ascending patch_at
     uint64_t* len_base;             // [n + 1] exclusive scan of new_len: offsets behind the store's fill; [n]: the batch's bytes
     uint64_t* keep_base;            // [n + 1] exclusive scan of keep: record numbers behind those of the batches before
-    uint32_t* iota;                 // [n] 0, 1, 2 ...: the order in which launch_sorted_offsets takes the lengths
     uint64_t* tile_sum;             // [len_tiles(n) + 2] scratch of the scans
 };
 

@@ -24,17 +24,6 @@ namespace sbx {
 
 namespace {
 
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(v, d, 64); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = __shfl_xor(v, d, 64); v = o > v ? o : v; }
-    return v;
-}
-
 // ---- K14a ----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kNameKeyThreads) void k_name_key_measure(NameKeyArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * kNameKeyThreads + threadIdx.x;
@@ -60,7 +49,7 @@ __global__ __launch_bounds__(kNameKeyThreads) void k_name_key_measure(NameKeyArg
         if (a.match_mates) a.mate_word[j] = mw;
     }
     const unsigned long long m_live = __ballot(live), m_name = __ballot(bad_name), m_hi = __ballot(bad_hi);
-    const uint32_t w_min = wave_min32(live ? nw : 0xFFFFFFFFu), w_max = wave_max32(nw);
+    const uint32_t w_min = wave_min<uint32_t>(live ? nw : 0xFFFFFFFFu), w_max = wave_max<uint32_t>(nw);
     unsigned long long m_or = 0, m_and = ~0ull;
     if (a.match_mates) { m_or = wave_or(live ? mw : 0ull); m_and = wave_and(live ? mw : ~0ull); }      // (a.match_mates is uniform)
     if ((threadIdx.x & 63u) == 0 && m_live) {
@@ -93,7 +82,7 @@ __global__ __launch_bounds__(kNameKeyThreads) void k_name_key_emit(NameKeyArgs a
             nsc::key_emit(rec + 36, (uint32_t)rec[12] - 1u, a.order, a.key_store + dst, nw, &got);
         }
     }
-    uint32_t w_max = wave_max32(nw);
+    uint32_t w_max = wave_max<uint32_t>(nw);
     if (w_max > nsc::kMaxKeyWords) w_max = nsc::kMaxKeyWords;
     for (uint32_t w = 0; w < w_max; ++w) {               // (wave-uniform)
         const unsigned long long v = w < nw ? a.key_store[dst + w] : 0ull;

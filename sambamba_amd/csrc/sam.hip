@@ -1,9 +1,9 @@
 // sam.hip -- K13: the SAM text of `sambamba view` (BamRead.toSam, read.d:695-760) for the entries sbx_view_sam selected.
 //
 //   K13a k_sam_measure   one lane per entry: the record walker of sam_core.hpp with the sink that only adds lengths up.  The line's
-//                        length is stored, the lengths of a workgroup are summed (block_sum) for the scan of the host
-//                        (launch_count_scan), malformed records are counted once per wave.
-//   k_sam_offsets        the same lanes: 64-bit offset of every line = the scanned base of the workgroup + block_exclusive.
+//                        length is stored, the lengths of a workgroup are summed (block_sum) in 64 bits, malformed records are
+//                        counted once per wave.  launch_scan64 over the sums and launch_group_offsets (scan.hip) give every line
+//                        its 64-bit offset.
 //   k_sam_pieces         one lane: cuts the text into pieces of at most `budget` bytes at line ends -- a binary search over the
 //                        offsets per piece, a few hundred pieces for a whole genome.
 //   K13b k_sam_emit      one lane per entry of a piece: the walker again, with the sink that writes (fmt::RowSink: eight bytes per
@@ -14,7 +14,7 @@
 // lines of different lengths inside a wave; neither layout has been timed, this is the simpler one.
 //
 // Bytes moved per entry of r record bytes and t text bytes: K13a reads 16 + r (the tags are walked for their lengths; sequence and
-// qualities are not touched) and writes 4; k_sam_offsets 4 in, 8 out; K13b reads 28 + r and writes t.
+// qualities are not touched) and writes 4; the offsets 4 in, 8 out; K13b reads 28 + r and writes t.
 #include "common.hpp"
 #include "sam.hpp"
 #include "wave_prims.hpp"
@@ -23,10 +23,10 @@ namespace sbx {
 
 namespace {
 
-__global__ __launch_bounds__(kSamThreads) void k_sam_measure(SamEntries e, uint32_t* __restrict__ line_len, uint32_t* __restrict__ group_sum,
+__global__ __launch_bounds__(kGroupThreads) void k_sam_measure(SamEntries e, uint32_t* __restrict__ line_len, uint64_t* __restrict__ group_sum,
                                                             unsigned long long* __restrict__ acc) {
-    __shared__ unsigned long long w_sum[kSamThreads / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kSamThreads + threadIdx.x;
+    __shared__ unsigned long long w_sum[kGroupThreads / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kGroupThreads + threadIdx.x;
     uint64_t length = 0;
     bool bad = false, too_long = false;
     if (i < e.n) {
@@ -37,23 +37,12 @@ __global__ __launch_bounds__(kSamThreads) void k_sam_measure(SamEntries e, uint3
         line_len[i] = (uint32_t)length;
     }
     const unsigned long long all = block_sum<unsigned long long>(length, w_sum);
-    if (all > 0xFFFFFFFFull) too_long = true;          // (every lane of the workgroup says so)
     const unsigned long long mb = __ballot(bad), ml = __ballot(too_long);
     if ((threadIdx.x & 63u) == 0) {
         if (mb) atomicAdd(acc + kSamAccBad, (unsigned long long)__popcll(mb));
         if (ml) atomicAdd(acc + kSamAccTooLong, 1ull);
     }
-    if (threadIdx.x == 0) group_sum[blockIdx.x] = (uint32_t)all;
-}
-
-__global__ __launch_bounds__(kSamThreads) void k_sam_offsets(const uint32_t* __restrict__ line_len, const uint64_t* __restrict__ group_base,
-                                                            uint64_t n, uint64_t* __restrict__ line_off) {
-    __shared__ uint32_t w_sum[kSamThreads / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * kSamThreads + threadIdx.x;
-    uint32_t all;
-    const uint32_t before = block_exclusive<uint32_t>(i < n ? line_len[i] : 0u, w_sum, &all);
-    if (i < n) line_off[i] = group_base[blockIdx.x] + before;
-    if (i == n - 1) line_off[n] = group_base[blockIdx.x] + all;
+    if (threadIdx.x == 0) group_sum[blockIdx.x] = all;
 }
 
 __global__ void k_sam_pieces(const uint64_t* __restrict__ line_off, uint64_t n, uint64_t budget, uint32_t* __restrict__ first,
@@ -77,9 +66,9 @@ __global__ void k_sam_pieces(const uint64_t* __restrict__ line_off, uint64_t n, 
     *n_pieces = k;
 }
 
-__global__ __launch_bounds__(kSamThreads) void k_sam_emit(SamEntries e, const uint32_t* __restrict__ line_len, const uint64_t* __restrict__ line_off,
+__global__ __launch_bounds__(kGroupThreads) void k_sam_emit(SamEntries e, const uint32_t* __restrict__ line_len, const uint64_t* __restrict__ line_off,
                                                          uint64_t i0, uint64_t i1, uint8_t* __restrict__ piece, unsigned long long* __restrict__ acc) {
-    const uint64_t i = i0 + (uint64_t)blockIdx.x * kSamThreads + threadIdx.x;
+    const uint64_t i = i0 + (uint64_t)blockIdx.x * kGroupThreads + threadIdx.x;
     bool wrong = false;
     if (i < i1) {
         const uint32_t r = e.perm[i];
@@ -92,15 +81,9 @@ __global__ __launch_bounds__(kSamThreads) void k_sam_emit(SamEntries e, const ui
 
 }  // namespace
 
-void launch_sam_measure(const SamEntries& e, uint32_t* d_line_len, uint32_t* d_group_sum, unsigned long long* d_acc, hipStream_t stream) {
+void launch_sam_measure(const SamEntries& e, uint32_t* d_line_len, uint64_t* d_group_sum, unsigned long long* d_acc, hipStream_t stream) {
     if (!e.n) return;
-    hipLaunchKernelGGL(k_sam_measure, dim3(sam_groups(e.n)), dim3(kSamThreads), 0, stream, e, d_line_len, d_group_sum, d_acc);
-    SBX_HIP(hipGetLastError());
-}
-
-void launch_sam_offsets(const uint32_t* d_line_len, const uint64_t* d_group_base, uint64_t n, uint64_t* d_line_off, hipStream_t stream) {
-    if (!n) return;
-    hipLaunchKernelGGL(k_sam_offsets, dim3(sam_groups(n)), dim3(kSamThreads), 0, stream, d_line_len, d_group_base, n, d_line_off);
+    hipLaunchKernelGGL(k_sam_measure, dim3(group_count(e.n)), dim3(kGroupThreads), 0, stream, e, d_line_len, d_group_sum, d_acc);
     SBX_HIP(hipGetLastError());
 }
 
@@ -113,7 +96,7 @@ void launch_sam_pieces(const uint64_t* d_line_off, uint64_t n, uint64_t budget, 
 void launch_sam_emit(const SamEntries& e, const uint32_t* d_line_len, const uint64_t* d_line_off, uint64_t i0, uint64_t i1, uint8_t* d_piece,
                      unsigned long long* d_acc, hipStream_t stream) {
     if (i1 <= i0) return;
-    hipLaunchKernelGGL(k_sam_emit, dim3(sam_groups(i1 - i0)), dim3(kSamThreads), 0, stream, e, d_line_len, d_line_off, i0, i1, d_piece, d_acc);
+    hipLaunchKernelGGL(k_sam_emit, dim3(group_count(i1 - i0)), dim3(kGroupThreads), 0, stream, e, d_line_len, d_line_off, i0, i1, d_piece, d_acc);
     SBX_HIP(hipGetLastError());
 }
 

@@ -17,15 +17,11 @@ struct SamEntries {
     uint64_t n;
     samc::RefNames refs;            // device pointers
 };
-constexpr uint32_t kSamThreads = 256;
-inline uint32_t sam_groups(uint64_t n) { return (uint32_t)((n + kSamThreads - 1) / kSamThreads); }
 
-// K13a: line_len[i] = bytes of the line of entry i (0 for a malformed record, counted in acc[kSamAccBad]; a line of 2^32 bytes or more,
-// or a workgroup whose lines add up to that, counts in acc[kSamAccTooLong]); group_sum[g] = the bytes of workgroup g.
-void launch_sam_measure(const SamEntries& e, uint32_t* d_line_len, uint32_t* d_group_sum, unsigned long long* d_acc, hipStream_t stream);
-// line_off[i] = group_base[i / kSamThreads] + the lengths in front of i inside its workgroup, i < n; line_off[n] = all bytes
-// (group_base: the exclusive scan of group_sum, sam_groups(n) + 1 words)
-void launch_sam_offsets(const uint32_t* d_line_len, const uint64_t* d_group_base, uint64_t n, uint64_t* d_line_off, hipStream_t stream);
+// K13a: line_len[i] = bytes of the line of entry i (0 for a malformed record, counted in acc[kSamAccBad]; a line of 2^32 bytes or more
+// counts in acc[kSamAccTooLong]); group_sum[g] = the bytes of workgroup g -- kGroupThreads entries, group_count(n) words: launch_scan64
+// and launch_group_offsets (scan.hpp) turn them into line_off[0, n], the offset of every line and in line_off[n] all bytes.
+void launch_sam_measure(const SamEntries& e, uint32_t* d_line_len, uint64_t* d_group_sum, unsigned long long* d_acc, hipStream_t stream);
 // The pieces of the text: piece k holds the lines [first[k], first[k + 1]), as many consecutive lines as fit `budget` bytes and at
 // least one.  d_first == nullptr: only *d_n_pieces is written; otherwise d_first[0 .. *d_n_pieces] (the last word = n) and the
 // offsets of those lines, d_first_off[0 .. *d_n_pieces], too.

@@ -19,7 +19,7 @@
 //                         of BGZF payloads; a record that straddles a piece boundary is copied in part by both pieces.
 //
 // Bytes moved (n records, b bytes of records): K9a reads 36 n (descriptor, rec_ref) + 4 n scattered words of U and writes 20 n; a pass of
-// K9b reads 12 n twice (histogram: keys only, 8 n) and writes 12 n; the offsets read 8 n and write 8 n; K9c reads and writes b.
+// K9b reads 12 n twice (histogram: keys only, 8 n) and writes 12 n; the offsets (scan.hip) read 8 n and write 8 n; K9c reads and writes b.
 #include "common.hpp"
 #include "sort.hpp"
 #include "sort_core.hpp"
@@ -86,11 +86,6 @@ __global__ __launch_bounds__(kSortKeysThreads) void k_sort_keys(SortKeysArgs a, 
 // ---- K9b -----------------------------------------------------------------------------------------------------------------
 constexpr uint32_t kRadixThreads = 256, kRadixWaves = kRadixThreads / 64, kRadixRounds = kRadixTile / kRadixThreads;
 
-__global__ __launch_bounds__(256) void k_iota(uint32_t* __restrict__ v, uint64_t n) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) v[i] = (uint32_t)i;
-}
-
 __global__ __launch_bounds__(kRadixThreads) void k_radix_hist(const uint64_t* __restrict__ key, uint64_t n, uint32_t shift, uint32_t n_tiles,
                                                               uint32_t* __restrict__ hist) {
     __shared__ uint32_t h[256];
@@ -152,53 +147,7 @@ __global__ __launch_bounds__(kRadixThreads) void k_radix_scatter(const uint64_t*
     }
 }
 
-// ---- offsets of the sorted records ---------------------------------------------------------------------------------------------
-constexpr uint32_t kLenThreads = 256, kLenItems = kLenTile / kLenThreads;
-
-__global__ __launch_bounds__(kLenThreads) void k_len_tile_sum(const uint32_t* __restrict__ len, const uint32_t* __restrict__ perm, uint64_t n,
-                                                              uint64_t* __restrict__ tile_sum) {
-    __shared__ uint64_t wsum[kLenThreads / 64];
-    const uint64_t i0 = (uint64_t)blockIdx.x * kLenTile + (uint64_t)threadIdx.x * kLenItems;
-    uint64_t s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kLenItems; ++k) if (i0 + k < n) s += len[perm[i0 + k]];
-    s = block_sum(s, wsum);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
-}
-
-// in place: x[i] = first + sum of x[j], j < i, for i in [0, m]; one workgroup
-__global__ __launch_bounds__(1024) void k_scan64(uint64_t* __restrict__ x, uint64_t m, uint64_t first) {
-    __shared__ uint64_t wsum[1024 / 64];
-    uint64_t carry = first;
-    for (uint64_t i0 = 0; i0 < m; i0 += 1024) {
-        const uint64_t i = i0 + threadIdx.x;
-        const uint64_t v = i < m ? x[i] : 0;
-        uint64_t total;
-        const uint64_t ex = block_exclusive(v, wsum, &total);
-        if (i < m) x[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) x[m] = carry;
-}
-
-__global__ __launch_bounds__(kLenThreads) void k_len_apply(const uint32_t* __restrict__ len, const uint32_t* __restrict__ perm, uint64_t n,
-                                                           const uint64_t* __restrict__ tile_base, uint64_t* __restrict__ out_off) {
-    __shared__ uint64_t wsum[kLenThreads / 64];
-    const uint64_t i0 = (uint64_t)blockIdx.x * kLenTile + (uint64_t)threadIdx.x * kLenItems;
-    uint32_t l[kLenItems];
-    uint64_t s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < kLenItems; ++k) { l[k] = i0 + k < n ? len[perm[i0 + k]] : 0u; s += l[k]; }
-    uint64_t total;
-    uint64_t run = tile_base[blockIdx.x] + block_exclusive(s, wsum, &total);
-#pragma unroll
-    for (uint32_t k = 0; k < kLenItems; ++k) {
-        if (i0 + k < n) out_off[i0 + k] = run;
-        run += l[k];
-        if (i0 + k + 1 == n) out_off[n] = run;
-    }
-}
-
+// ---- the pieces of the sorted stream (its offsets: launch_sorted_offsets, scan.hip) ------------------------------------------------
 __global__ __launch_bounds__(256) void k_piece_bounds(const uint64_t* __restrict__ out_off, uint64_t n, uint64_t piece_bytes, uint32_t n_bounds,
                                                       uint32_t* __restrict__ rec) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
@@ -227,15 +176,9 @@ void launch_sort_keys(const SortKeysArgs& a, uint32_t* d_group_count, uint64_t* 
     if (a.use_filter) {
         hipLaunchKernelGGL(k_sort_group_count, dim3(groups), dim3(kSortKeysThreads), 0, stream, a.desc, a.n, d_group_count);
         SBX_HIP(hipGetLastError());
-        launch_count_scan(d_group_count, groups, d_group_base, nullptr, 0, stream);
+        launch_count_scan(d_group_count, groups, d_group_base, stream);
     }
     hipLaunchKernelGGL(k_sort_keys, dim3(groups), dim3(kSortKeysThreads), 0, stream, a, a.use_filter ? d_group_base : nullptr);
-    SBX_HIP(hipGetLastError());
-}
-
-void launch_iota(uint32_t* d_val, uint64_t n, hipStream_t stream) {
-    if (!n) return;
-    hipLaunchKernelGGL(k_iota, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_val, n);
     SBX_HIP(hipGetLastError());
 }
 
@@ -245,21 +188,9 @@ void launch_radix_pass(const uint64_t* d_key_in, const uint32_t* d_val_in, uint6
     const uint32_t tiles = radix_tiles(n);
     hipLaunchKernelGGL(k_radix_hist, dim3(tiles), dim3(kRadixThreads), 0, stream, d_key_in, n, shift, tiles, d_hist);
     SBX_HIP(hipGetLastError());
-    launch_count_scan(d_hist, tiles * 256u, d_hist_base, nullptr, 0, stream);
+    launch_count_scan(d_hist, tiles * 256u, d_hist_base, stream);
     hipLaunchKernelGGL(k_radix_scatter, dim3(tiles), dim3(kRadixThreads), 0, stream, d_key_in, d_val_in, d_key_out, d_val_out, n, shift, tiles,
                        d_hist_base);
-    SBX_HIP(hipGetLastError());
-}
-
-void launch_sorted_offsets(const uint32_t* d_len, const uint32_t* d_perm, uint64_t n, uint64_t first, uint64_t* d_tile_sum, uint64_t* d_out_off,
-                           hipStream_t stream) {
-    if (!n) return;
-    const uint32_t tiles = (uint32_t)len_tiles(n);
-    hipLaunchKernelGGL(k_len_tile_sum, dim3(tiles), dim3(kLenThreads), 0, stream, d_len, d_perm, n, d_tile_sum);
-    SBX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_scan64, dim3(1), dim3(1024), 0, stream, d_tile_sum, (uint64_t)tiles, first);
-    SBX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_len_apply, dim3(tiles), dim3(kLenThreads), 0, stream, d_len, d_perm, n, d_tile_sum, d_out_off);
     SBX_HIP(hipGetLastError());
 }
 

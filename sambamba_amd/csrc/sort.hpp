@@ -34,15 +34,9 @@ void launch_sort_keys(const SortKeysArgs& a, uint32_t* d_group_count, uint64_t* 
 constexpr uint32_t kRadixTile = 4096;
 inline uint32_t radix_tiles(uint64_t n) { return (uint32_t)((n + kRadixTile - 1) / kRadixTile); }
 inline size_t radix_hist_entries(uint64_t n) { return (size_t)radix_tiles(n) * 256; }
-void launch_iota(uint32_t* d_val, uint64_t n, hipStream_t stream);
 void launch_radix_pass(const uint64_t* d_key_in, const uint32_t* d_val_in, uint64_t* d_key_out, uint32_t* d_val_out, uint64_t n, uint32_t shift,
                        uint32_t* d_hist, uint64_t* d_hist_base, hipStream_t stream);
 
-// offsets of the records in the sorted stream: d_out_off[i] = first + sum of d_len[d_perm[j]], j < i, for i in [0, n]
-constexpr uint32_t kLenTile = 2048;
-inline size_t len_tiles(uint64_t n) { return (size_t)((n + kLenTile - 1) / kLenTile); }
-void launch_sorted_offsets(const uint32_t* d_len, const uint32_t* d_perm, uint64_t n, uint64_t first, uint64_t* d_tile_sum /* len_tiles + 2 */,
-                           uint64_t* d_out_off, hipStream_t stream);
 // d_rec[k], k in [0, n_bounds): the first record that ends behind byte k * piece_bytes of the sorted stream (n: none)
 void launch_piece_bounds(const uint64_t* d_out_off, uint64_t n, uint64_t piece_bytes, uint32_t n_bounds, uint32_t* d_rec, hipStream_t stream);
 // K9c: the bytes of sorted records [r0, r1) that lie in [p0, p1) of the sorted stream go to d_dst[0, p1 - p0)

@@ -1,7 +1,8 @@
-// wave_prims.hpp -- the wave and workgroup idioms the kernels of the resident-store commands share: sort.hip (K9), markdup.hip (K10),
-// merge.hip (K11), view.hip (K12) and namesort.hip (K14), and no other file.  (The depth path -- inflate, index, depth, reduce, mates, format, deflate,
-// flagstat -- keeps private helpers with similar names and does not include this.)  A wave is 64 lanes; a workgroup a whole number
-// of waves, its threads numbered by threadIdx.x.
+// wave_prims.hpp -- the wave and workgroup idioms the kernels of the resident-store commands and of the text commands share.  Included by
+// scan.hip, lines.hip, sort.hip (K9), markdup.hip (K10), merge.hip (K11), view.hip (K12), sam.hip (K13), namesort.hip (K14), samparse.hip
+// (K15), bins.hip (K16) and fasta.hip (K17).  (The depth path -- inflate, index, depth, reduce, mates, format, deflate, flagstat -- keeps
+// private helpers with similar names and does not include this.)  A wave is 64 lanes; a workgroup a whole number of waves, its threads
+// numbered by threadIdx.x.
 #pragma once
 #include <type_traits>
 
@@ -16,22 +17,17 @@ __device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << (threadIdx.x
 template <class T>
 using shfl_t = std::conditional_t<sizeof(T) == 8, unsigned long long, unsigned int>;
 
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (T)__shfl_xor((shfl_t<T>)v, d, 64);
+    for (int d = 32; d >= 1; d >>= 1) v = op(v, (T)__shfl_xor((shfl_t<T>)v, d, 64));
     return v;
 }
-__device__ __forceinline__ unsigned long long wave_or(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v |= __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_and(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v &= __shfl_xor(v, d, 64);
-    return v;
-}
+template <class T> __device__ __forceinline__ T wave_sum(T v) { return wave_reduce(v, [](T a, T b) { return a + b; }); }
+template <class T> __device__ __forceinline__ T wave_min(T v) { return wave_reduce(v, [](T a, T b) { return b < a ? b : a; }); }
+template <class T> __device__ __forceinline__ T wave_max(T v) { return wave_reduce(v, [](T a, T b) { return b > a ? b : a; }); }
+__device__ __forceinline__ unsigned long long wave_or(unsigned long long v) { return wave_reduce(v, [](unsigned long long a, unsigned long long b) { return a | b; }); }
+__device__ __forceinline__ unsigned long long wave_and(unsigned long long v) { return wave_reduce(v, [](unsigned long long a, unsigned long long b) { return a & b; }); }
 
 // inclusive prefix sum over the lanes of the wave (uint32_t or uint64_t): the __shfl_up ladder
 template <class T>

@@ -146,6 +146,43 @@ def test_three_mebibytes_in_chunks_and_whole(kind, tmp_path, monkeypatch):
     assert cut[2]["n_lines"] == whole[2]["n_lines"] == len(ref.lines_of(text, ref.terminator(text)))
 
 
+# ---- the scans behind K15a and K17a (launch_scan64) ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("chunk", ["4096", None], ids=["4096", "default"])
+def test_line_counts_around_the_group_of_256(chunk, tmp_path, monkeypatch):
+    """255 .. 258 lines: 0, 1 and 2 groups of inner lines (0 and 1 lines are "empty" and "only_header_nl" of the edge texts)"""
+    set_chunk(monkeypatch, chunk)
+    named = {}
+    for n in (2, 255, 256, 257, 258):
+        lines = [b">s%d" % k if k % 3 == 0 else b"ACGTACGTAC" for k in range(n)]
+        named["%d lines" % n] = b"\n".join(lines) + b"\n"
+        named["%d lines, open end" % n] = b"\n".join(lines)
+    check(named, tmp_path)
+
+
+def test_more_tiles_and_groups_than_one_round_of_the_scan(tmp_path, monkeypatch):
+    """One chunk of more than 1024 text tiles of 4096 bytes and more than 1024 groups of 256 inner lines: launch_scan64 carries its sum
+    from one round of 1024 values into the next, for the tile bases of K15a and for the segment numbers of K17a.  The same file in
+    chunks of 1 MiB keeps every scan inside one round."""
+    rng = random.Random(11)
+    out = []
+    for k in range(125000):
+        out.append(b">s%d" % k)
+        out += [b"ACGTTGCAAC"] * rng.choice((2, 3)) if k % 1000 else [b"ACGTTGCAAC", b"ACG"]
+    text = b"\n".join(out) + b"\n"
+    n_lines = len(out)
+    assert len(text) > 1024 * 4096 + 4096 and n_lines - 1 > 1024 * 256 + 256
+    want = ref.fai(text)
+    assert want.count(b"\n") == 125000
+    path = str(tmp_path / "many.fa")
+    monkeypatch.delenv("SBX_FASTA_CHUNK_BYTES", raising=False)
+    whole = index(path, text, str(tmp_path / "whole.fai"))
+    assert whole[:2] == ("ok", want) and whole[2]["n_chunks"] == 1 and whole[2]["n_lines"] == n_lines
+    monkeypatch.setenv("SBX_FASTA_CHUNK_BYTES", str(1 << 20))
+    assert (1 << 20) < 1024 * 4096 and max(text[i:i + (1 << 20)].count(b"\n") for i in range(0, len(text), 1 << 20)) < 1024 * 256
+    cut = index(path, text, str(tmp_path / "cut.fai"))
+    assert cut[:2] == ("ok", want) and cut[2]["n_chunks"] == (len(text) + (1 << 20) - 1) >> 20
+
+
 def test_output_must_not_be_the_input(tmp_path):
     import sambamba_amd
     path = str(tmp_path / "in.fa")

@@ -271,3 +271,29 @@ def test_command_line(sorted_sam, tmp_path):
     open(bad, "wb").write(data + b"not a line\n")
     r = subprocess.run([imp, "-o", str(tmp_path / "bad.bam"), bad], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 1 and r.stderr.decode().startswith("sbx-import: malformed SAM text") and not os.path.exists(str(tmp_path / "bad.bam"))
+
+
+# ---- the scans behind K15a and K15b (launch_scan64, launch_group_offsets) at the edges of the workgroup of 256 lines ----
+@pytest.mark.parametrize("final_newline", [False, True])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 513])
+def test_line_counts_around_the_offset_group(n, final_newline, tmp_path):
+    lines = [_line_of(22 + (37 * k) % 300, k) for k in range(n)]
+    data = cases.sam_text(lines, final_newline=final_newline)
+    bam, st = do_import(data, tmp_path)
+    got, want = inflate(bam), expected_stream(data)
+    assert st["n_records"] == st["n_lines"] == n and st["n_chunks"] == 1
+    assert got == want, first_difference(got, want)
+
+
+def test_input_that_ends_at_a_chunk_end(tmp_path, monkeypatch):
+    """every chunk is filled to its last byte, so the reader meets the end of the input with an empty slot in its hands"""
+    lines = [_line_of(100, k) for k in range(6)]
+    data = cases.sam_text(lines)
+    monkeypatch.delenv("SBX_IMPORT_CHUNK_BYTES", raising=False)
+    want = inflate(do_import(data, tmp_path, tag="default")[0])
+    assert want == expected_stream(data)
+    for per_chunk in (6, 2, 1):
+        monkeypatch.setenv("SBX_IMPORT_CHUNK_BYTES", str(100 * per_chunk))
+        bam, st = do_import(data, tmp_path, tag="c%d" % per_chunk)
+        assert st["n_chunks"] == 6 // per_chunk and st["n_records"] == 6 and st["text_bytes"] == 600
+        assert inflate(bam) == want

@@ -344,3 +344,17 @@ def test_abi_sizeof_merge_stats():
     from sambamba_amd._lib import MergeStats
     L = sambamba_amd.lib()
     assert L.sbx_abi_sizeof(b"sbx_merge_stats") == C.sizeof(MergeStats) == 7 * 8 + 4 * 4 + 7 * 8
+
+
+# ---- the offsets of the rewritten records (launch_sorted_offsets without a permutation) at the edges of its tile of 2048 ----
+@pytest.mark.parametrize("n_a,n_b", [(1, 2046), (1, 2047), (1, 2048), (2048, 2049)], ids=["2047", "2048", "2049", "4097"])
+def test_rewritten_batch_around_the_offset_tile(tmp_path, n_a, n_b, monkeypatch):
+    """The scans run over the records of one input at a time: the inputs have 2046 .. 2049 records, 2047 .. 4097 together."""
+    refs = POOL[:3]
+    # both inputs have a read group "g": b's becomes "g.1", two bytes longer in every record that carries it
+    a = write(str(tmp_path / "a.bam"), refs, records(n_a, 3, 31, rgs=["g"]), text=text_of(refs, rg=[("g", "s1")]))
+    b = write(str(tmp_path / "b.bam"), refs, records(n_b, 3, 32, rgs=["g"]), text=text_of(refs, rg=[("g", "s2")]))
+    monkeypatch.setenv("SBX_MERGE_FORCE_REWRITE", "1")
+    st, want = check([a, b], tmp_path, with_cli=False)
+    renamed = want.count(bamgen.tag_z("RG", "g.1"))
+    assert st["n_records_out"] == n_a + n_b and renamed > 1000 and st["bytes_grown"] == 2 * renamed

@@ -275,3 +275,19 @@ def test_coordinate_order_is_unchanged(generated, tmp_path):
     assert open(c, "rb").read() == open(d, "rb").read()
     assert open(c + ".bai", "rb").read() == open(d + ".bai", "rb").read()
     check_file(d, sort_ref.expected(path, _reverse))
+
+
+# ---- the scan of the word counts (launch_count_scan) at the edges of its round of 4096 counts ----
+@pytest.fixture(scope="module")
+def scan_round_records():
+    rng = random.Random(20241019)
+    return _records(_names(rng, 8193), rng)
+
+
+@pytest.mark.parametrize("order", [ref.LEX, ref.NATURAL])
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 8193])
+def test_record_counts_around_the_scan_round(scan_round_records, n, order, tmp_path):
+    path = str(tmp_path / "n.bam")
+    bamgen.write_bam(path, REFS, scan_round_records[:n], text=UNSORTED, write_index=False)
+    st, _ = check(path, tmp_path, order)
+    assert st["n_records_out"] == n and st["n_batches"] == 1

@@ -316,3 +316,16 @@ def test_python_api(ties, tmp_path):
     sambamba_amd.view(path, out, regions=["c2"])
     assert open(out, "rb").read(4) == b"\x1f\x8b\x08\x04"
     assert "sbx_view_sam" in sambamba_amd._lib.EXPORTS and os.path.exists(sambamba_amd.sam_cli_path())
+
+
+# ---- the offsets of the lines (launch_group_offsets) at the edges of the workgroup of 256 ----
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 513])
+def test_entry_counts_around_the_offset_group(n, tmp_path):
+    pool = cases.edge_records() + cases.tag_records()
+    recs = [pool[k % len(pool)] for k in range(n)]
+    path = str(tmp_path / "n.bam")
+    bamgen.write_bam(path, cases.REFS, recs, text=cases.TEXT, write_index=False)
+    want, n_want = expected_text(path)
+    got, st = view_sam(path, tmp_path)
+    assert got == want, first_difference(got, want)
+    assert n_want == st["n_entries_out"] == n and st["stream_bytes"] == len(want)
