@@ -321,8 +321,8 @@ static IndexResult index_pass(sbx_ctx* c, const std::vector<sbx_region>& sel, bo
         SBX_HIP(hipMemsetAsync(c->d_flag.p + kFlagStraddler, 0xFF, 8, s));
         const IndexArgs a = fill_index_args(c, tab->refs, tab->rg, T, entries_given);
         launch_index_blocks(a, s);
-        launch_tile_compact(c->d_tile_lo.p, c->d_tile_hi.p, (uint32_t)nt, deep_thr, c->d_active.p, c->d_slot_of.p, c->d_n_active.p, s,
-                            c->d_scan_part.p);
+        launch_tile_compact(c->d_tile_lo.p, c->d_tile_hi.p, (uint32_t)nt, deep_thr, c->d_active.p, c->d_slot_of.p, c->d_n_active.p,
+                            c->d_scan_part.p, s);
         if (attempt == 0) t_index->stop(s);
         R.last_state = 0;
         SBX_HIP(hipMemcpyAsync(R.flags, c->d_flag.p, sizeof R.flags, hipMemcpyDeviceToHost, s));

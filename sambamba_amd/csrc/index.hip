@@ -18,8 +18,9 @@
 //      dead once the block is inflated -- no extra memory;
 //   2. `k_check_scan` -- the guesses are VERIFIED, never trusted: the entry of block b must equal the exit of block b-1
 //      (by induction from the exactly known start of the run a consistent chain IS the true chain; an inconsistency is
-//      reported to the host, which repairs the chain serially -- `k_chain_repair`, rare -- and launches again with the
-//      entries given); the same single workgroup scans the per-block record counts into slot ranges;
+//      reported to the host, which repairs the chain -- `k_rewalk_mismatched`, then `k_chain_repair`, rare -- and launches
+//      again with the entries given); the same launch scans the per-block record counts into slot ranges: several
+//      workgroups of 4096 blocks each with a ticket-ordered look-back, or one workgroup that loops (one kernel template);
 //   3. `k_describe_blocks` -- one wave per block, ONE LANE PER RECORD: fixed part, CIGAR span and shape, the -F program,
 //      RG -> sample, name hash; writes the 32-byte RecDesc and marks the [lo,hi) record range of every position tile the
 //      record overlaps (one atomic per tile change inside a wave).
@@ -28,8 +29,6 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "regex_nfa.hpp"
-
-#include <algorithm>
 
 namespace sbx {
 
@@ -239,7 +238,6 @@ __global__ __launch_bounds__(64) void k_chain_repair(const uint8_t* __restrict__
     if (lane == 0) *n_rewalked += rewalked;
 }
 
-constexpr int kScanThreads = 1024;      // (the scan of counts itself: launch_count_scan, scan.hip)
 // ---- aux fields, the -F program, RG lookup -------------------------------------------------------
 // first aux field with the given key (BamRead.opIndex, read.d:1070-1087; skipValue read.d:1219-1230):
 // returns its type character and value pointer, 0 when absent or when the tag area is malformed before it
@@ -806,68 +804,21 @@ __global__ __launch_bounds__(kWalkThreads) void k_rewalk_mismatched(IndexArgs a,
     atomicAdd(n_changed, 1u);
 }
 
-// ---- 2. chain check + scan of the per-block counts (single workgroup; n_blocks is ~1e5..1e6) ------------------
-// state[b] = 2 << 62 | records in blocks 0..b (the engine reads the last one); flags[0] = lowest inconsistent block,
-// flags[2] != 0: the descriptor array is too small for the total
-__global__ __launch_bounds__(kScanThreads) void k_check_scan(IndexArgs a) {
-    // 4 x 1024 blocks per step, coalesced; the loads of all four sub-steps are issued before the first scan, so that the single
-    // workgroup pays one memory round trip per 4096 blocks (it is the serial link between the walk and the describe launches);
-    // inclusive scan inside the wave by shuffles, wave totals through LDS
-    constexpr int kSub = 4;
-    __shared__ uint64_t wtot[kSub][kScanThreads / 64];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6, n = a.n_blocks;
-    uint64_t run = 0;                    // records in the blocks before this step (workgroup-uniform)
-    uint32_t first_bad = 0xFFFFFFFFu;
-    for (uint32_t i0 = 0; i0 < n; i0 += kSub * kScanThreads) {
-        uint64_t v[kSub], incl[kSub];
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
-            v[u] = 0;
-            if (i < n) {
-                v[u] = a.count[i];
-                const ChainRun r = a.runs[a.run_of[i]];
-                if (i != r.blk_first && a.exit_[i - 1] != a.entry[i] && first_bad == 0xFFFFFFFFu) first_bad = i;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            uint64_t x = v[u];
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint64_t o = (uint64_t)__shfl_up((unsigned long long)x, d, 64);
-                if ((int)lane >= d) x += o;
-            }
-            incl[u] = x;
-            if (lane == 63) wtot[u][wv] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
-            uint64_t before = 0, all = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kScanThreads / 64; ++w) {
-                const uint64_t x = wtot[u][w];
-                before += w < wv ? x : 0;
-                all += x;
-            }
-            if (i < n) a.state[i] = (2ull << 62) | (run + before + incl[u]);
-            run += all;
-        }
-        __syncthreads();
-    }
-    if (first_bad != 0xFFFFFFFFu) atomicMin(a.flags + 0, first_bad);
-    if (t == 0 && run > a.desc_cap) atomicOr(a.flags + 2, 1u);
-}
-
-// The same over SEVERAL workgroups in one launch (round 5: the single workgroup above is a serial link of 0.5 ms between the walk and the
-// describe launches of a chromosome).  Workgroup g takes blocks [4096 g, 4096 g + 4096): chain check, local scan, then it PUBLISHES its total
-// (`part[g]` = total | ready bit) and adds up the totals of the workgroups before it.  g is a TICKET taken on entry (scan_ticket), so
-// the workgroups g waits for hold earlier tickets: they are running -- a workgroup takes its ticket when it starts -- and never wait for
-// a later one; the look-back cannot deadlock however large the grid is (a whole genome has 3.1 M tiles = 757 workgroups, more than the
-// device holds at once: the later ones simply start as the earlier ones finish).
-constexpr uint32_t kScanPerWg = 4 * kScanThreads;
+// ---- 2. the two scans of K2: chain check + scan of the per-block counts; compaction of the active tiles ----------
+// Both go over their items (n_blocks ~1e5..1e6, n_tiles ~1e3..3e6) in ROUNDS of 4 x 1024, coalesced; the loads of all four rows are issued
+// before the first rank, so that a round pays one memory round trip; rank inside the wave (shuffles / ballot), wave totals through LDS.
+// Each is ONE kernel template with two launch shapes, which differ only in where a round's carry `run` comes from:
+//   kLookback == false: a single workgroup loops over the rounds and carries `run` in a register -- a serial link of 0.5 ms between the
+//     walk and the describe launches of a chromosome (round 5), now the shape of launches of one round and of more than kScanMaxWgs;
+//   kLookback == true: several workgroups in one launch, one round each.  Workgroup g takes items [4096 g, 4096 g + 4096): local rank,
+//     then it PUBLISHES its total (`part[g]` = total | ready bit) and adds up the totals of the workgroups before it.  g is a TICKET
+//     taken on entry (scan_ticket), so the workgroups g waits for hold earlier tickets: they are running -- a workgroup takes its ticket
+//     when it starts -- and never wait for a later one; the look-back cannot deadlock however large the grid is (a whole genome has
+//     3.1 M tiles = 757 workgroups, more than the device holds at once: the later ones simply start as the earlier ones finish).
+constexpr int kScanThreads = 1024;
+constexpr int kScanSub = 4;
+constexpr uint32_t kScanWaves = kScanThreads / 64;
+constexpr uint32_t kScanPerWg = kScanSub * kScanThreads;
 constexpr unsigned long long kScanReady = 1ull << 63;
 constexpr uint32_t kScanMaxWgs = kScanPartWords - 2;      // (the last word of `part` is the ticket counter)
 
@@ -899,59 +850,158 @@ __device__ __forceinline__ uint64_t lookback_sum(unsigned long long* part, uint3
     return all;
 }
 
-__global__ __launch_bounds__(kScanThreads) void k_check_scan_mw(IndexArgs a, unsigned long long* part) {
-    constexpr int kSub = 4;
-    __shared__ uint64_t wtot[kSub][kScanThreads / 64];
-    __shared__ uint64_t red[kScanThreads / 64];
+// The step both scans share: from the four rows of wave totals in LDS, what lies in front of wave `wv` in each row of the round (the rows
+// before it and the waves before it in its own row); returns the round's total.  Four rows of sixteen waves are one value per lane:
+// every wave loads them once and scans them by shuffles (a lane that adds up all 64 words itself holds them in 128 registers).
+template <class T>
+__device__ __forceinline__ T wave_totals(const T (&wtot)[kScanSub][kScanWaves], uint32_t wv, T (&before)[kScanSub]) {
+    static_assert(kScanSub * kScanWaves == 64, "one wave total per lane");
+    const uint32_t lane = threadIdx.x & 63u;
+    const T own = (&wtot[0][0])[lane];
+    T x = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = (T)__shfl_up(x, d, 64);
+        if ((int)lane >= d) x += o;
+    }
+#pragma unroll
+    for (int u = 0; u < kScanSub; ++u) before[u] = (T)__shfl(x - own, (int)(u * kScanWaves + wv), 64);
+    return (T)__shfl(x, 63, 64);
+}
+
+// state[b] = 2 << 62 | records in blocks 0..b (the engine reads the last one); flags[0] = lowest inconsistent block,
+// flags[2] != 0: the descriptor array is too small for the total.  a.scan_part: `part` of the look-back, zeroed by the launcher.
+template <bool kLookback>
+__global__ __launch_bounds__(kScanThreads) void k_check_scan(IndexArgs a) {
+    __shared__ uint64_t wtot[kScanSub][kScanWaves];
     const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6, n = a.n_blocks;
-    const uint32_t g = scan_ticket(part);
-    const uint32_t i0 = g * kScanPerWg;
+    uint32_t g = 0;                      // the workgroup's ticket (look-back)
+    uint64_t run = 0;                    // records in the blocks before the round, after it: the round's included (workgroup-uniform)
     uint32_t first_bad = 0xFFFFFFFFu;
-    uint64_t v[kSub], incl[kSub];
+    auto round = [&](const uint32_t i0) {
+        uint64_t v[kScanSub], incl[kScanSub];
 #pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-        const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
-        v[u] = 0;
-        if (i < n) {
-            v[u] = a.count[i];
-            const ChainRun r = a.runs[a.run_of[i]];
-            if (i != r.blk_first && a.exit_[i - 1] != a.entry[i] && first_bad == 0xFFFFFFFFu) first_bad = i;
+        for (int u = 0; u < kScanSub; ++u) {
+            const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
+            v[u] = 0;
+            if (i < n) {
+                v[u] = a.count[i];
+                const ChainRun r = a.runs[a.run_of[i]];
+                if (i != r.blk_first && a.exit_[i - 1] != a.entry[i] && first_bad == 0xFFFFFFFFu) first_bad = i;
+            }
         }
-    }
 #pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-        uint64_t x = v[u];
+        for (int u = 0; u < kScanSub; ++u) {
+            uint64_t x = v[u];
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t o = (uint64_t)__shfl_up((unsigned long long)x, d, 64);
-            if ((int)lane >= d) x += o;
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint64_t o = (uint64_t)__shfl_up((unsigned long long)x, d, 64);
+                if ((int)lane >= d) x += o;
+            }
+            incl[u] = x;
+            if (lane == 63) wtot[u][wv] = x;
         }
-        incl[u] = x;
-        if (lane == 63) wtot[u][wv] = x;
-    }
-    __syncthreads();
-    uint64_t before[kSub], total = 0;
-#pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-        uint64_t b = 0, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kScanThreads / 64; ++w) {
-            const uint64_t x = wtot[u][w];
-            b += w < wv ? x : 0;
-            all += x;
+        __syncthreads();
+        uint64_t before[kScanSub];
+        const uint64_t total = wave_totals(wtot, wv, before);
+        if constexpr (kLookback) {
+            __shared__ uint64_t red[kScanWaves];
+            if (t == 0) __hip_atomic_store(a.scan_part + g, (unsigned long long)total | kScanReady, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            run = lookback_sum(a.scan_part, g, red);
         }
-        before[u] = total + b;
-        total += all;
-    }
-    if (t == 0) __hip_atomic_store(part + g, (unsigned long long)total | kScanReady, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    const uint64_t run = lookback_sum(part, g, red);
 #pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-        const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
-        if (i < n) a.state[i] = (2ull << 62) | (run + before[u] + incl[u]);
+        for (int u = 0; u < kScanSub; ++u) {
+            const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
+            if (i < n) a.state[i] = (2ull << 62) | (run + before[u] + incl[u]);
+        }
+        run += total;
+        if constexpr (!kLookback) __syncthreads();       // (the next round writes wtot again)
+    };
+    if constexpr (kLookback) {
+        g = scan_ticket(a.scan_part);
+        round(g * kScanPerWg);
+    } else {
+        for (uint32_t i0 = 0; i0 < n; i0 += kScanPerWg) round(i0);
     }
     if (first_bad != 0xFFFFFFFFu) atomicMin(a.flags + 0, first_bad);
-    if (t == 0 && g == gridDim.x - 1 && run + total > a.desc_cap) atomicOr(a.flags + 2, 1u);       // (the last ticket: run + total = all records)
+    // (look-back: behind the last ticket's round `run` is all records)
+    if (t == 0 && (!kLookback || g == gridDim.x - 1) && run > a.desc_cap) atomicOr(a.flags + 2, 1u);
+}
+
+// active[] = the tiles with records in ascending order, slot_of[tile] = its place there or ~0u; n_active[0] = how many,
+// n_active[1] = how many of them hold deep_thr records or more (K3 keeps 32-bit counters for them).  part: look-back only;
+// its launcher zeroes `part` and n_active[0 .. 1], which collect the totals there.
+template <bool kLookback>
+__global__ __launch_bounds__(kScanThreads) void k_tile_compact(const uint32_t* __restrict__ tile_lo, const uint32_t* __restrict__ tile_hi,
+                                                                uint32_t n_tiles, uint32_t deep_thr, uint32_t* __restrict__ active,
+                                                                uint32_t* __restrict__ slot_of, uint32_t* __restrict__ n_active,
+                                                                unsigned long long* part) {
+    __shared__ uint32_t wtot[kScanSub][kScanWaves];
+    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
+    uint32_t g = 0;                      // the workgroup's ticket (look-back)
+    uint32_t run = 0;                    // active tiles before the round, after it: the round's included (workgroup-uniform)
+    uint32_t n_deep = 0;                 // this thread's deep tiles
+    auto round = [&](const uint32_t i0) {
+        uint32_t lo_i[kScanSub], hi_i[kScanSub];
+        uint64_t m[kScanSub];
+#pragma unroll
+        for (int u = 0; u < kScanSub; ++u) {
+            const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
+            lo_i[u] = i < n_tiles ? tile_lo[i] : 0u;
+            hi_i[u] = i < n_tiles ? tile_hi[i] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < kScanSub; ++u) {
+            const bool on = hi_i[u] > lo_i[u];
+            n_deep += on && hi_i[u] - lo_i[u] >= deep_thr ? 1u : 0u;
+            m[u] = __ballot(on);
+            if (lane == 0) wtot[u][wv] = (uint32_t)__popcll(m[u]);
+        }
+        __syncthreads();
+        uint32_t before[kScanSub];
+        const uint32_t total = wave_totals(wtot, wv, before);
+        if constexpr (kLookback) {
+            __shared__ uint64_t red[kScanWaves];
+            if (t == 0) __hip_atomic_store(part + g, (unsigned long long)total | kScanReady, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            run = (uint32_t)lookback_sum(part, g, red);
+        }
+#pragma unroll
+        for (int u = 0; u < kScanSub; ++u) {
+            const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
+            if (i < n_tiles) {
+                if (hi_i[u] > lo_i[u]) {
+                    const uint32_t slot = run + before[u] + (uint32_t)__popcll(m[u] & ((1ull << lane) - 1ull));
+                    active[slot] = i;
+                    slot_of[i] = slot;
+                } else {
+                    slot_of[i] = 0xFFFFFFFFu;
+                }
+            }
+        }
+        run += total;
+        if constexpr (!kLookback) __syncthreads();       // (the next round writes wtot again)
+    };
+    if constexpr (kLookback) {
+        g = scan_ticket(part);
+        round(g * kScanPerWg);
+    } else {
+        for (uint32_t i0 = 0; i0 < n_tiles; i0 += kScanPerWg) round(i0);
+    }
+    for (int d = 32; d >= 1; d >>= 1) n_deep += __shfl_down(n_deep, d, 64);
+    if constexpr (kLookback) {
+        if (lane == 0 && n_deep) atomicAdd(n_active + 1, n_deep);
+        if (t == 0 && g == gridDim.x - 1) n_active[0] = run;       // (behind the last ticket's round `run` is all active tiles)
+    } else {
+        // (nobody zeroed n_active: the waves' deep tiles through a row of wtot, which no round is using any more)
+        if (lane == 0) wtot[0][wv] = n_deep;
+        __syncthreads();
+        if (t == 0) {
+            uint32_t deep = 0;
+            for (uint32_t w = 0; w < kScanWaves; ++w) deep += wtot[0][w];
+            n_active[0] = run;
+            n_active[1] = deep;
+        }
+    }
 }
 
 // ---- 3. describe: one wave per block, one lane per record ---------------------------------------------------
@@ -1148,144 +1198,15 @@ __global__ __launch_bounds__(kDescThreads) __attribute__((amdgpu_waves_per_eu(4,
 // the same with the simple filter evaluator (IndexArgs::simple_filter: the host looked at the program)
 __global__ __launch_bounds__(kDescThreads) __attribute__((amdgpu_waves_per_eu(6, 8))) void k_describe_blocks_simple(IndexArgs a) { describe_blocks_body<true, true>(a); }
 
-// ---- active tile compaction (single workgroup ballot scan; n_tiles ~ 1e3..2e6) ---------------------
-__global__ __launch_bounds__(kScanThreads) void k_tile_compact(const uint32_t* __restrict__ tile_lo,
-                                                                const uint32_t* __restrict__ tile_hi, uint32_t n_tiles, uint32_t deep_thr,
-                                                                uint32_t* __restrict__ active, uint32_t* __restrict__ slot_of,
-                                                                uint32_t* __restrict__ n_active) {
-    // 4 x 1024 tiles per step, coalesced, the loads of the four sub-steps in flight together: rank inside the wave by ballot,
-    // wave totals through LDS
-    constexpr int kSub = 4;
-    __shared__ uint32_t wtot[kSub][kScanThreads / 64];
-    __shared__ uint32_t deep_total;
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-    if (t == 0) deep_total = 0;
-    uint32_t n_deep = 0;                 // this thread's tiles with >= 2^16 records (K3 keeps 32-bit counters for them)
-    uint32_t run = 0;                    // active tiles before this step (workgroup-uniform)
-    for (uint32_t i0 = 0; i0 < n_tiles; i0 += kSub * kScanThreads) {
-        uint32_t lo_i[kSub], hi_i[kSub];
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
-            lo_i[u] = i < n_tiles ? tile_lo[i] : 0u;
-            hi_i[u] = i < n_tiles ? tile_hi[i] : 0u;
-        }
-        uint64_t m[kSub];
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            const bool on = hi_i[u] > lo_i[u];
-            n_deep += on && hi_i[u] - lo_i[u] >= deep_thr ? 1u : 0u;
-            m[u] = __ballot(on);
-            if (lane == 0) wtot[u][wv] = (uint32_t)__popcll(m[u]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < kSub; ++u) {
-            const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
-            uint32_t before = 0, all = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kScanThreads / 64; ++w) {
-                const uint32_t x = wtot[u][w];
-                before += w < wv ? x : 0u;
-                all += x;
-            }
-            if (i < n_tiles) {
-                if (hi_i[u] > lo_i[u]) {
-                    const uint32_t slot = run + before + (uint32_t)__popcll(m[u] & ((1ull << lane) - 1ull));
-                    active[slot] = i;
-                    slot_of[i] = slot;
-                } else {
-                    slot_of[i] = 0xFFFFFFFFu;
-                }
-            }
-            run += all;
-        }
-        __syncthreads();
-    }
-    if (n_deep) atomicAdd(&deep_total, n_deep);
-    __syncthreads();
-    if (t == 0) { n_active[0] = run; n_active[1] = deep_total; }
+// The launch shape of a K2 scan over n_items blocks or tiles: the number of workgroups of the look-back launch, or 0 for the single
+// workgroup -- when the items fit one round, when there are more rounds than `part` has words for, and with SBX_K2_SCAN=0.
+uint32_t lookback_wgs(uint32_t n_items) {
+    static const bool on = [] { const char* e = getenv("SBX_K2_SCAN"); return !e || atoi(e) != 0; }();
+    const uint32_t n_wg = (n_items + kScanPerWg - 1) / kScanPerWg;
+    return on && n_wg > 1 && n_wg <= kScanMaxWgs ? n_wg : 0u;
 }
-
-// several workgroups, one launch (see k_check_scan_mw): workgroup g ranks the active tiles of [4096 g, 4096 g + 4096) behind the
-// active tiles of the workgroups before it; n_active[0] / [1] (zeroed by the launcher) collect the totals
-__global__ __launch_bounds__(kScanThreads) void k_tile_compact_mw(const uint32_t* __restrict__ tile_lo, const uint32_t* __restrict__ tile_hi,
-                                                                   uint32_t n_tiles, uint32_t deep_thr, uint32_t* __restrict__ active,
-                                                                   uint32_t* __restrict__ slot_of, uint32_t* __restrict__ n_active,
-                                                                   unsigned long long* part) {
-    constexpr int kSub = 4;
-    __shared__ uint32_t wtot[kSub][kScanThreads / 64];
-    __shared__ uint64_t red[kScanThreads / 64];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-    const uint32_t g = scan_ticket(part);
-    const uint32_t i0 = g * kScanPerWg;
-    uint32_t lo_i[kSub], hi_i[kSub], n_deep = 0;
-    uint64_t m[kSub];
-#pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-        const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
-        lo_i[u] = i < n_tiles ? tile_lo[i] : 0u;
-        hi_i[u] = i < n_tiles ? tile_hi[i] : 0u;
-    }
-#pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-        const bool on = hi_i[u] > lo_i[u];
-        n_deep += on && hi_i[u] - lo_i[u] >= deep_thr ? 1u : 0u;
-        m[u] = __ballot(on);
-        if (lane == 0) wtot[u][wv] = (uint32_t)__popcll(m[u]);
-    }
-    __syncthreads();
-    uint32_t before[kSub], total = 0;
-#pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-        uint32_t b = 0, all = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < kScanThreads / 64; ++w) {
-            const uint32_t x = wtot[u][w];
-            b += w < wv ? x : 0u;
-            all += x;
-        }
-        before[u] = total + b;
-        total += all;
-    }
-    if (t == 0) __hip_atomic_store(part + g, (unsigned long long)total | kScanReady, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    const uint32_t run = (uint32_t)lookback_sum(part, g, red);
-#pragma unroll
-    for (int u = 0; u < kSub; ++u) {
-        const uint32_t i = i0 + (uint32_t)u * kScanThreads + t;
-        if (i < n_tiles) {
-            if (hi_i[u] > lo_i[u]) {
-                const uint32_t slot = run + before[u] + (uint32_t)__popcll(m[u] & ((1ull << lane) - 1ull));
-                active[slot] = i;
-                slot_of[i] = slot;
-            } else {
-                slot_of[i] = 0xFFFFFFFFu;
-            }
-        }
-    }
-    for (int d = 32; d >= 1; d >>= 1) n_deep += __shfl_down(n_deep, d, 64);
-    if (lane == 0 && n_deep) atomicAdd(n_active + 1, n_deep);
-    if (t == 0 && g == gridDim.x - 1) n_active[0] = run + total;
-}
-
 
 }  // namespace
-
-namespace {
-__global__ __launch_bounds__(1024) void k_max_u32(const uint32_t* __restrict__ in, uint64_t n, uint32_t* out) {
-    uint32_t m = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 1024) m = in[i] > m ? in[i] : m;
-    for (int d = 32; d >= 1; d >>= 1) { uint32_t o = __shfl_down(m, d, 64); m = o > m ? o : m; }
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-}  // namespace
-
-void launch_max_u32(const uint32_t* d_in, uint64_t n, uint32_t* d_out, hipStream_t stream) {
-    if (!n) return;
-    uint32_t grid = (uint32_t)std::min<uint64_t>(2048, (n + 1023) / 1024);
-    hipLaunchKernelGGL(k_max_u32, dim3(grid), dim3(1024), 0, stream, d_in, n, d_out);
-    SBX_HIP(hipGetLastError());
-}
 
 void launch_index_blocks(const IndexArgs& a, hipStream_t stream) {
     if (!a.n_blocks) return;
@@ -1298,14 +1219,11 @@ void launch_index_blocks(const IndexArgs& a, hipStream_t stream) {
     }
     hipLaunchKernelGGL(k_walk_blocks, dim3((a.n_blocks + kWalkThreads - 1) / kWalkThreads), dim3(kWalkThreads), 0, stream, w);
     SBX_HIP(hipGetLastError());
-    // (scan_part: kScanMaxWgs words the launcher owns -- IndexArgs::scan_part; SBX_K2_SCAN=0 keeps the single workgroup)
-    static const bool mw = [] { const char* e = getenv("SBX_K2_SCAN"); return !e || atoi(e) != 0; }();
-    const uint32_t n_wg = (a.n_blocks + kScanPerWg - 1) / kScanPerWg;
-    if (mw && a.scan_part && n_wg > 1 && n_wg <= kScanMaxWgs) {
-        SBX_HIP(hipMemsetAsync(a.scan_part, 0, (size_t)kScanPartWords * 8, stream));
-        hipLaunchKernelGGL(k_check_scan_mw, dim3(n_wg), dim3(kScanThreads), 0, stream, a, a.scan_part);
+    if (const uint32_t n_wg = lookback_wgs(a.n_blocks)) {
+        SBX_HIP(hipMemsetAsync(a.scan_part, 0, (size_t)kScanPartWords * 8, stream));      // (the launcher owns these words)
+        hipLaunchKernelGGL(k_check_scan<true>, dim3(n_wg), dim3(kScanThreads), 0, stream, a);
     } else
-        hipLaunchKernelGGL(k_check_scan, dim3(1), dim3(kScanThreads), 0, stream, a);
+        hipLaunchKernelGGL(k_check_scan<false>, dim3(1), dim3(kScanThreads), 0, stream, a);
     SBX_HIP(hipGetLastError());
     const uint32_t per = kDescThreads / 64;
     const dim3 dgrid((a.n_blocks + per - 1) / per), dblock(kDescThreads);
@@ -1329,17 +1247,15 @@ void launch_chain_repair(const uint8_t* d_U, const uint64_t* d_out_off, const ui
 }
 
 void launch_tile_compact(const uint32_t* d_tile_lo, const uint32_t* d_tile_hi, uint32_t n_tiles, uint32_t deep_thr, uint32_t* d_active,
-                         uint32_t* d_slot_of, uint32_t* d_n_active, hipStream_t stream, unsigned long long* d_scan_part) {
-    static const bool mw = [] { const char* e = getenv("SBX_K2_SCAN"); return !e || atoi(e) != 0; }();
-    const uint32_t n_wg = (n_tiles + kScanPerWg - 1) / kScanPerWg;
-    if (mw && d_scan_part && n_wg > 1 && n_wg <= kScanMaxWgs) {
+                         uint32_t* d_slot_of, uint32_t* d_n_active, unsigned long long* d_scan_part, hipStream_t stream) {
+    if (const uint32_t n_wg = lookback_wgs(n_tiles)) {
         SBX_HIP(hipMemsetAsync(d_scan_part, 0, (size_t)kScanPartWords * 8, stream));
         SBX_HIP(hipMemsetAsync(d_n_active, 0, 8, stream));
-        hipLaunchKernelGGL(k_tile_compact_mw, dim3(n_wg), dim3(kScanThreads), 0, stream, d_tile_lo, d_tile_hi, n_tiles, deep_thr, d_active,
+        hipLaunchKernelGGL(k_tile_compact<true>, dim3(n_wg), dim3(kScanThreads), 0, stream, d_tile_lo, d_tile_hi, n_tiles, deep_thr, d_active,
                            d_slot_of, d_n_active, d_scan_part);
     } else
-        hipLaunchKernelGGL(k_tile_compact, dim3(1), dim3(kScanThreads), 0, stream, d_tile_lo, d_tile_hi, n_tiles, deep_thr, d_active,
-                           d_slot_of, d_n_active);
+        hipLaunchKernelGGL(k_tile_compact<false>, dim3(1), dim3(kScanThreads), 0, stream, d_tile_lo, d_tile_hi, n_tiles, deep_thr, d_active,
+                           d_slot_of, d_n_active, d_scan_part);
     SBX_HIP(hipGetLastError());
 }
 

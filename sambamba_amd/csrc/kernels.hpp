@@ -157,7 +157,7 @@ struct IndexArgs {
     // owners' runs equal the whole
     int32_t own_ref;
     uint32_t own_beg, own_end;
-    unsigned long long* scan_part;  // kScanPartWords words of scratch for the multi-workgroup scans (nullptr: single-workgroup kernels)
+    unsigned long long* scan_part;  // kScanPartWords words of scratch for the look-back of the multi-workgroup scans
     uint32_t* flags;                // [0] lowest block with an inconsistent chain (0xFFFFFFFF: none), [1] lowest block whose
                                     // inflate failed, [2] != 0: desc_cap was too small (nothing useful was written)
     uint32_t filter_every;          // != 0 (sbx_sort_bam with -F): the filter is evaluated on EVERY well-formed record, also an unmapped
@@ -177,7 +177,7 @@ void launch_chain_repair(const uint8_t* d_U, const uint64_t* d_out_off, const ui
 // compact the tiles that have work: active[] = tile ids, slot_of[t] = index into active or ~0u;
 // d_n_active[0] = number of active tiles, [1] = how many of them have >= 65536 records
 void launch_tile_compact(const uint32_t* d_tile_lo, const uint32_t* d_tile_hi, uint32_t n_tiles, uint32_t deep_thr, uint32_t* d_active,
-                         uint32_t* d_slot_of, uint32_t* d_n_active, hipStream_t stream, unsigned long long* d_scan_part = nullptr);
+                         uint32_t* d_slot_of, uint32_t* d_n_active, unsigned long long* d_scan_part, hipStream_t stream);
 
 // ---- K3: decode + accumulate (depth.hip) -------------------------------------------------
 // n_deep: active tiles with >= deep_thr (<= 65536) records, counted by tile_compact; they keep 32-bit LDS counters

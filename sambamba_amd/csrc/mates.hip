@@ -25,6 +25,7 @@
 // region / window mode, whose closed form (reduce.hip) is derived for pairs.  Ties are resolved as in the oracle: the
 // record later in the file wins (column order; parity unpinned).  Names are compared byte for byte after the hashes
 // match (depth.d:352-353).
+#include <algorithm>
 #include <cstdlib>
 
 #include "common.hpp"
@@ -641,6 +642,14 @@ __global__ __launch_bounds__(kMateThreads) void k_mates_columns(
     for (uint32_t i = threadIdx.x; i < T; i += kMateThreads) span_out[(size_t)blockIdx.x * T + i] = spn[i];
 }
 
+// the largest n_partners[] of the run: it decides between pairs and partner lists (engine_run.cpp, kFlagMaxPartners)
+__global__ __launch_bounds__(1024) void k_max_u32(const uint32_t* __restrict__ in, uint64_t n, uint32_t* out) {
+    uint32_t m = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 1024) m = in[i] > m ? in[i] : m;
+    for (int d = 32; d >= 1; d >>= 1) { uint32_t o = __shfl_down(m, d, 64); m = o > m ? o : m; }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
+}
+
 }  // namespace
 
 void launch_find_mates(const uint8_t* d_U, const RecDesc* d_desc, const uint64_t* d_hash, const int32_t* d_rec_ref, uint64_t n_records,
@@ -648,6 +657,13 @@ void launch_find_mates(const uint8_t* d_U, const RecDesc* d_desc, const uint64_t
     if (!n_records) return;
     hipLaunchKernelGGL(k_find_mates_join, dim3((uint32_t)((n_records + kMateThreads - 1) / kMateThreads)), dim3(kMateThreads), 0, stream,
                            d_U, d_desc, d_hash, d_rec_ref, n_records, d_mate, d_n_partners);
+    SBX_HIP(hipGetLastError());
+}
+
+void launch_max_u32(const uint32_t* d_in, uint64_t n, uint32_t* d_out, hipStream_t stream) {
+    if (!n) return;
+    uint32_t grid = (uint32_t)std::min<uint64_t>(2048, (n + 1023) / 1024);
+    hipLaunchKernelGGL(k_max_u32, dim3(grid), dim3(1024), 0, stream, d_in, n, d_out);
     SBX_HIP(hipGetLastError());
 }
 
