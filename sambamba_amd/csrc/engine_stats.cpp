@@ -169,7 +169,7 @@ static void range_stats(sbx_ctx* c, const std::vector<sbx_region>& ranges, bool 
         SBX_HIP(hipMemcpyAsync(d_wb.p, win_base.data(), win_base.size() * 8, hipMemcpyHostToDevice, s));
         SBX_HIP(hipMemcpyAsync(d_nw.p, n_win.data(), n_win.size() * 8, hipMemcpyHostToDevice, s));
         for (sbx_ctx* f : files)
-            launch_count_reads_windows(f->U(), f->d_desc.p, records_of(f), f->d_rec_ref.p, window, d_wb.p, d_nw.p, S, c->min_bq, d_nr.p, s);
+            launch_count_reads_windows(f->U(), f->d_desc.p, records_of(f), f->d_rec_ref.p, window, d_wb.p, d_nw.p, S, c->min_bq, d_nr.p, d_nb.p, s);
     } else {
         // (ref, start)-sorted view + prefix max of ends per contig (cached with the range list)
         const size_t n_ref = c->hdr.refs.size();
@@ -299,7 +299,7 @@ static void window_stats_all(sbx_ctx* c) {
                                 c->d_slot_of.p, c->d_tile_base.p, T, S, wc.d_thr.p, n_thr, wc.d_nb.p, wc.d_cov.p, wc.d_seen.p, s, c->compact_counters);
     for (sbx_ctx* f : files_of(c)) {
         const uint64_t nrec = (f == c && !c->members.empty()) ? c->primary_records : f->stats.n_records;
-        launch_count_reads_windows(f->U(), f->d_desc.p, nrec, f->d_rec_ref.p, w, wc.d_base.p, wc.d_nwin.p, S, c->min_bq, wc.d_nr.p, s);
+        launch_count_reads_windows(f->U(), f->d_desc.p, nrec, f->d_rec_ref.p, w, wc.d_base.p, wc.d_nwin.p, S, c->min_bq, wc.d_nr.p, wc.d_nb.p, s);
     }
     t.stop(s);
     wc.h_nb.resize(n * S); wc.h_nr.resize(n * S); wc.cov.assign(ncov, 0);

@@ -224,7 +224,7 @@ void launch_range_reduce_windows(const uint64_t* d_win_base, const uint64_t* d_n
                                  uint32_t* d_cov_counts, uint32_t* d_seen, hipStream_t stream, bool compact);
 void launch_count_reads_windows(const uint8_t* d_U, const RecDesc* d_desc, uint64_t n_records, const int32_t* d_rec_ref,
                                 uint32_t window, const uint64_t* d_win_base, const uint64_t* d_n_win, uint32_t S,
-                                uint32_t min_bq, uint32_t* d_n_reads, hipStream_t stream);
+                                uint32_t min_bq, uint32_t* d_n_reads, uint32_t* d_n_bases, hipStream_t stream);
 void launch_count_reads_regions(const uint8_t* d_U, const RecDesc* d_desc, uint64_t n_records, const int32_t* d_rec_ref,
                                 const SortedRegion* d_regs, const uint32_t* d_pmax_end, const uint32_t* d_ref_first, uint32_t S,
                                 uint32_t min_bq, uint32_t* d_n_reads, const uint32_t* d_min_start, uint32_t* d_n_bases,

@@ -5,6 +5,7 @@
 // Without -m these are closed forms over the per-position counters of K3 (SURVEY.md Appendix A,
 // verified against a literal restatement):
 //     n_bases[r]      = sum_{p in r} (# M/=/X bases at p with qual >= min_bq)      = sum of codes 0..4
+//                       (+ a per-read correction for CIGARs with a zero-length reference-consuming operation, see count_good)
 //     cov_count[r][t] = #{p in r : COV(p) >= T_t},  COV = all 7 counters (D/N count as quality 255)
 //     n_reads[r]      = # admitted reads having >= 1 M/=/X base with qual >= min_bq inside r
 // `range_reduce` does the first two as segmented reductions over the counter tiles (one wave per
@@ -107,8 +108,7 @@ __global__ __launch_bounds__(kRedThreads) void k_range_reduce(
 __device__ uint32_t count_good(const uint8_t* U, const RecDesc& d, uint32_t min_bq, int64_t lo, int64_t hi);
 
 // does the read have an M/=/X base with quality >= min_bq at a reference position inside [rs, re)?
-// (countOverlappingBases > 0, depth.d:671-698; zero-length reference-consuming ops occupy one column,
-// and the read ends at d.end, exactly as in K3)
+// (countOverlappingBases > 0, depth.d:671-698: the CIGAR's lengths as written -- see count_good)
 __device__ bool has_good_base(const uint8_t* U, const RecDesc& d, uint32_t min_bq, int64_t rs, int64_t re) {
     const uint8_t* rec = U + d.rec_off;
     const uint8_t* cig = rec + 36 + d.l_name;
@@ -131,11 +131,6 @@ __device__ bool has_good_base(const uint8_t* U, const RecDesc& d, uint32_t min_b
     for (uint32_t k = 0; k < d.n_cigar; ++k) {
         uint32_t op = ld32r(cig + 4 * k);
         uint32_t ty = (kCigarType >> ((op & 15u) * 2u)) & 3u, len = op >> 4;
-        if (ty & 2u) {
-            if (len == 0) len = 1;
-            int64_t room = (int64_t)d.end - rp;
-            if ((int64_t)len > room) len = (uint32_t)(room > 0 ? room : 0);
-        }
         if (ty == 3) {
             if (run(rp, qp, len)) return true;
             rp += len;
@@ -148,6 +143,27 @@ __device__ bool has_good_base(const uint8_t* U, const RecDesc& d, uint32_t min_b
         if (rp >= re || rp >= d.end) break;
     }
     return false;
+}
+
+// does a general CIGAR hold a zero-length reference-consuming operation (K2's `zero_ref`)?
+__device__ bool has_zero_ref(const uint8_t* U, const RecDesc& d) {
+    if (d.kind != 2) return false;
+    const uint8_t* cig = U + d.rec_off + 36 + d.l_name;
+    for (uint32_t k = 0; k < d.n_cigar; ++k) {
+        const uint32_t op = ld32r(cig + 4 * k);
+        if ((op >> 4) == 0 && ((kCigarType >> ((op & 15u) * 2u)) & 2u)) return true;
+    }
+    return false;
+}
+
+__device__ uint32_t count_good_columns(const uint8_t* U, const RecDesc& d, uint32_t min_bq, int64_t lo, int64_t hi);
+
+// The sums of k_range_reduce are sums over pileup columns, where a zero-length reference-consuming operation takes one column and
+// the read is cut at d.end (pileup.d:195-205, K3); countOverlappingBases gives it none.  For the few reads with such an operation
+// the difference of the two walks inside [lo, hi) is added to n_bases (modulo 2^32, like every sum here).
+__device__ void fix_zero_ref_bases(const uint8_t* U, const RecDesc& d, uint32_t min_bq, int64_t lo, int64_t hi, uint32_t* n_bases_rs) {
+    const uint32_t a = count_good(U, d, min_bq, lo, hi), b = count_good_columns(U, d, min_bq, lo, hi);
+    if (a != b) atomicAdd(n_bases_rs, a - b);
 }
 
 // window mode: windows [k*w, (k+1)*w), k < n_win[ref]; id = win_base[ref] + k
@@ -174,7 +190,7 @@ __device__ __forceinline__ void add_runs(uint32_t* base, uint64_t slot, bool on,
 __global__ __launch_bounds__(kRedThreads) void k_count_reads_windows(
     const uint8_t* __restrict__ U, const RecDesc* __restrict__ desc, uint64_t n_records, const int32_t* __restrict__ rec_ref,
     uint32_t window, const uint64_t* __restrict__ win_base, const uint64_t* __restrict__ n_win, uint32_t S, uint32_t min_bq,
-    uint32_t* n_reads /*[id][S]*/) {
+    uint32_t* n_reads /*[id][S]*/, uint32_t* n_bases /*[id][S]: corrected for reads with zero-length operations*/) {
     const uint64_t i = (uint64_t)blockIdx.x * kRedThreads + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     const bool live = i < n_records;
@@ -195,6 +211,9 @@ __global__ __launch_bounds__(kRedThreads) void k_count_reads_windows(
         for (uint64_t k = k0 + 2; k <= k1 && k < nw; ++k)
             if (has_good_base(U, d, min_bq, (int64_t)(k * window), (int64_t)((k + 1) * window)))
                 atomicAdd(&n_reads[(size_t)(wb + k) * S + s], 1u);
+    if (adm && has_zero_ref(U, d))
+        for (uint64_t k = k0; k <= k1 && k < nw; ++k)
+            fix_zero_ref_bases(U, d, min_bq, (int64_t)(k * window), (int64_t)((k + 1) * window), &n_bases[(size_t)(wb + k) * S + s]);
 }
 
 // region mode: regions sorted by (ref, start); pmax_end[j] = max end over the contig's regions 0..j
@@ -214,6 +233,7 @@ __global__ __launch_bounds__(kRedThreads) void k_count_reads_regions(
     uint32_t a = lo0, c = hi0;
     while (a < c) { uint32_t m = (a + c) >> 1; if ((int64_t)regs[m].start < (int64_t)d.end) a = m + 1; else c = m; }
     const uint32_t s = S > 1 ? d.sample : 0u;
+    const bool zero_ref = has_zero_ref(U, d);
     for (uint32_t j = a; j > lo0;) {
         --j;
         if ((int64_t)pmax_end[j] <= (int64_t)d.pos) break;      // nothing at or before j reaches the read
@@ -225,8 +245,9 @@ __global__ __launch_bounds__(kRedThreads) void k_count_reads_regions(
             if ((int64_t)d.pos < (int64_t)ms) continue;
             const uint32_t B = count_good(U, d, min_bq, (int64_t)regs[j].start, (int64_t)regs[j].end);
             if (B) { atomicAdd(&n_reads[(size_t)regs[j].id * S + s], 1u); atomicAdd(&n_bases[(size_t)regs[j].id * S + s], B); }
-        } else if (has_good_base(U, d, min_bq, (int64_t)regs[j].start, (int64_t)regs[j].end)) {
-            atomicAdd(&n_reads[(size_t)regs[j].id * S + s], 1u);
+        } else {
+            if (has_good_base(U, d, min_bq, (int64_t)regs[j].start, (int64_t)regs[j].end)) atomicAdd(&n_reads[(size_t)regs[j].id * S + s], 1u);
+            if (zero_ref) fix_zero_ref_bases(U, d, min_bq, (int64_t)regs[j].start, (int64_t)regs[j].end, &n_bases[(size_t)regs[j].id * S + s]);
         }
     }
 }
@@ -246,8 +267,10 @@ __global__ __launch_bounds__(kRedThreads) void k_count_reads_regions(
 // B(r, [lo, hi)) = number of M/=/X bases of r at reference positions in [lo, hi) with quality >= min_bq.
 
 // number of M/=/X bases of the read at reference positions in [lo, hi) with quality >= min_bq (countOverlappingBases,
-// depth.d:671-698; zero-length reference-consuming ops occupy one column and the read ends at d.end, as in K3)
-__device__ uint32_t count_good(const uint8_t* U, const RecDesc& d, uint32_t min_bq, int64_t lo, int64_t hi) {
+// depth.d:671-698: the lengths of the CIGAR as written).  kColumns: as the pileup's columns see the read instead -- a zero-length
+// reference-consuming operation occupies one column and the read ends at d.end, as in K3.
+template <bool kColumns>
+__device__ uint32_t count_good_walk(const uint8_t* U, const RecDesc& d, uint32_t min_bq, int64_t lo, int64_t hi) {
     const uint8_t* rec = U + d.rec_off;
     const uint8_t* cig = rec + 36 + d.l_name;
     const uint8_t* seq = cig + 4 * (uint32_t)d.n_cigar;
@@ -267,7 +290,7 @@ __device__ uint32_t count_good(const uint8_t* U, const RecDesc& d, uint32_t min_
     for (uint32_t k = 0; k < d.n_cigar; ++k) {
         uint32_t op = ld32r(cig + 4 * k);
         uint32_t ty = (kCigarType >> ((op & 15u) * 2u)) & 3u, len = op >> 4;
-        if (ty & 2u) {
+        if (kColumns && (ty & 2u)) {
             if (len == 0) len = 1;
             int64_t room = (int64_t)d.end - rp;
             if ((int64_t)len > room) len = (uint32_t)(room > 0 ? room : 0);
@@ -285,6 +308,9 @@ __device__ uint32_t count_good(const uint8_t* U, const RecDesc& d, uint32_t min_
     }
     return n;
 }
+
+__device__ uint32_t count_good(const uint8_t* U, const RecDesc& d, uint32_t min_bq, int64_t lo, int64_t hi) { return count_good_walk<false>(U, d, min_bq, lo, hi); }
+__device__ uint32_t count_good_columns(const uint8_t* U, const RecDesc& d, uint32_t min_bq, int64_t lo, int64_t hi) { return count_good_walk<true>(U, d, min_bq, lo, hi); }
 
 // first pileup column of every range: atomicMin over the positions with span > 0
 __global__ __launch_bounds__(kRedThreads) void k_range_first(const RangeChunk* __restrict__ chunks, uint32_t n_chunks,
@@ -445,10 +471,10 @@ void launch_range_reduce_windows(const uint64_t* d_win_base, const uint64_t* d_n
 
 void launch_count_reads_windows(const uint8_t* d_U, const RecDesc* d_desc, uint64_t n_records, const int32_t* d_rec_ref,
                                 uint32_t window, const uint64_t* d_win_base, const uint64_t* d_n_win, uint32_t S,
-                                uint32_t min_bq, uint32_t* d_n_reads, hipStream_t stream) {
+                                uint32_t min_bq, uint32_t* d_n_reads, uint32_t* d_n_bases, hipStream_t stream) {
     if (!n_records) return;
     hipLaunchKernelGGL(k_count_reads_windows, dim3((uint32_t)((n_records + kRedThreads - 1) / kRedThreads)), dim3(kRedThreads), 0,
-                       stream, d_U, d_desc, n_records, d_rec_ref, window, d_win_base, d_n_win, S, min_bq, d_n_reads);
+                       stream, d_U, d_desc, n_records, d_rec_ref, window, d_win_base, d_n_win, S, min_bq, d_n_reads, d_n_bases);
     SBX_HIP(hipGetLastError());
 }
 
