@@ -128,6 +128,15 @@ extern (C) nothrow @nogc {
     int sbx_view_sam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, const(sbx_view_opts)* opts, const(char*)* regions,
                      size_t n_regions, const(char)* bed_path, const(char)* pg_command_line, int with_header, int device,
                      sbx_view_stats* stats, char* err, size_t errlen);
+    /* `sambamba slice`: R1 and [a, b) per region, whole BGZF blocks copied from the file (see sbx_depth.h).  Divergences from slice.d's
+       code, following its header comment: a is the first record with pos >= beg; b is the end of the contig's records when none starts
+       at or behind end; FASTA input is not provided. */
+    struct sbx_slice_stats {
+        ulong n_regions; ulong records_r1; ulong blocks_inflated; ulong blocks_copied; ulong bytes_copied; ulong stream_bytes; ulong compressed_bytes;
+        double ms_read; double ms_select; double ms_write; double ms_total_wall;
+    }
+    int sbx_slice_bam(const(char)* in_path, const(char)* out_path, const(char*)* regions, size_t n_regions, const(char)* bed_path, int device,
+                      sbx_slice_stats* stats, char* err, size_t errlen);
     int sbx_view_num_filter(const(char)* text, ushort* flags_set, ushort* flags_unset);
     int sbx_view_reference_info(sbx_ctx*, char* out_, size_t cap, size_t* out_len);
     struct sbx_import_stats {

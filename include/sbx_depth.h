@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -350,6 +350,32 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
 int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
                  size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device,
                  sbx_view_stats* stats, char* err, size_t errlen);
+/* ---- `sambamba slice` (sambamba/slice.d): regions of an indexed BAM copied with their BGZF blocks reused ----
+ * The records of in_path in file order are i = 0 .. n-1; record i occupies [u_i, u_{i+1}) of the inflated stream.  For a region
+ * (r, beg, end): R1 = the records with ref == r, pos < beg and pos + basesCovered > beg; first_ge(x) = the first record with ref < 0,
+ * ref > r, or ref == r and pos >= x (n when there is none); a = u[first_ge(beg)], b = u[first_ge(end)].  The output is the header
+ * bytes of the input unchanged (no @PG), then for every region in the order given the records of R1 and the stream bytes [a, b), then
+ * the EOF block; two regions that overlap give their common records twice.  Every BGZF block of the input that lies wholly inside
+ * [a, b) is written as it is in the file and is neither uploaded nor inflated; the head [a, next block start), the tail [start of b's
+ * block, b) and R1 are compressed on the device at the default level (an empty piece writes no block).  Only the blocks the .bai names
+ * for the two edge positions of a region are read.  `regions` as for sbx_view_bam ("chr", "chr:beg-end", at most SBX_VIEW_MAX_REGIONS);
+ * "*" alone gives the header and everything from the first record without a reference on, "*" next to other regions is SBX_EINVAL.
+ * `bed_path` (NULL or "": none) names a BED file instead (merged, in (reference, start) order, unknown contigs dropped); both, or
+ * neither, are SBX_EINVAL.  out_path NULL or "-": stdout.  SBX_ENOINDEX without a .bai, SBX_EINVAL for an unknown reference (named), an
+ * empty region or an out_path that is the input, SBX_EUNSUPPORTED for more than 2^32 R1 records.  On failure no output file is left.
+ * Deliberate divergences from the reference's code, which departs from its own header comment: a is the first record with pos >= beg
+ * (the code also copies the records behind the last R1 record that start in front of beg and do not reach it); when reads reach
+ * `end` but none of the contig starts at or behind it, b is the end of the contig's records (the code ends the copy in front of the
+ * last such read and loses it); FASTA input (-F) is not provided.
+ * stats: stream_bytes = inflated bytes that went through the device writer (the header included), compressed_bytes = what it wrote
+ * (the EOF block and the copied blocks not included), blocks_inflated = blocks of the edge runs (the header's blocks, inflated at
+ * open, not included), ms_read = K1 + K2 of the edge runs, ms_select = K18, ms_write / ms_total_wall = wall clock. */
+typedef struct {
+    uint64_t n_regions, records_r1, blocks_inflated, blocks_copied, bytes_copied, stream_bytes, compressed_bytes;
+    double ms_read, ms_select, ms_write, ms_total_wall;
+} sbx_slice_stats;
+int sbx_slice_bam(const char* in_path, const char* out_path, const char* const* regions, size_t n_regions, const char* bed_path, int device,
+                  sbx_slice_stats* stats, char* err, size_t errlen);
 /* "i1/i2" of --num-filter (view.d:271-277; host only): either number may be missing ("4/", "/4", "3", ""), each is an unsigned
  * 16-bit decimal; anything else is SBX_EINVAL. */
 int sbx_view_num_filter(const char* text, uint16_t* flags_set, uint16_t* flags_unset);

@@ -1,5 +1,5 @@
 """sambamba_amd -- Python harness around libsbx_depth.so, the MI355X (gfx950) engine behind
-`sambamba depth base|region|window`, `sambamba flagstat`, `sambamba sort`, `sambamba markdup`, `sambamba merge`, `sambamba view` (SAM input included), `sambamba index` (BAM and FASTA) and `sambamba fixbins`.
+`sambamba depth base|region|window`, `sambamba flagstat`, `sambamba sort`, `sambamba markdup`, `sambamba merge`, `sambamba view` (SAM input included), `sambamba slice`, `sambamba index` (BAM and FASTA) and `sambamba fixbins`.
 
 The product is the C-ABI library (include/sbx_depth.h) plus the `sbx-depth` CLI, both built
 from sambamba_amd/csrc/ by sambamba_amd.build.  This package only binds the C ABI with ctypes
@@ -11,6 +11,7 @@ from ._lib import (SbxError, Depth, lib, lib_path, inflate_blocks, compile_filte
                    sort_bam, sort_header_text, sort_cli_path, nsort_cli_path, markdup, markdup_header_text, markdup_cli_path,
                    merge, merge_header_text, merge_cli_path,
                    view, view_num_filter, view_reference_info, view_cli_path, sam_cli_path,
+                   slice_bam, slice_cli_path,
                    import_sam, import_cli_path,
                    fixbins, index_fasta, index_cli_path, fixbins_cli_path,
                    SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW)

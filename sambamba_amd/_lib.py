@@ -12,6 +12,7 @@ _SORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sort")
 _MARKDUP_CLI_PATH = os.path.join(HERE, "csrc", "sbx-markdup")
 _MERGE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-merge")
 _VIEW_CLI_PATH = os.path.join(HERE, "csrc", "sbx-view")
+_SLICE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-slice")
 _SAM_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sam")
 _NSORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-nsort")
 _IMPORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-import")
@@ -116,6 +117,11 @@ class ViewStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_regions", "n_sort_passes", "n_batches", "reserved")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_select", "ms_emit", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
 
+class SliceStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_regions", "records_r1", "blocks_inflated", "blocks_copied", "bytes_copied", "stream_bytes",
+                                           "compressed_bytes")] +
+                [(k, C.c_double) for k in ("ms_read", "ms_select", "ms_write", "ms_total_wall")])
+
 class ImportStats(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("n_lines", "n_records", "text_bytes", "stream_bytes", "compressed_bytes")] +
                 [(k, C.c_uint32) for k in ("n_chunks", "reserved")] +
@@ -143,6 +149,7 @@ EXPORTS = [
     "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
     "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_num_filter", "sbx_view_reference_info",
+    "sbx_slice_bam",
     "sbx_import_sam",
     "sbx_index_bam", "sbx_fixbins", "sbx_index_fasta",
 ]
@@ -176,6 +183,10 @@ def merge_cli_path():
 
 def view_cli_path():
     return _VIEW_CLI_PATH
+
+
+def slice_cli_path():
+    return _SLICE_CLI_PATH
 
 
 def sam_cli_path():
@@ -271,6 +282,8 @@ def lib():
                                C.c_int, C.c_int, C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
     L.sbx_view_num_filter.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
     L.sbx_view_reference_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.sbx_slice_bam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_int, C.POINTER(SliceStats), C.c_char_p,
+                                C.c_size_t]
     L.sbx_import_sam.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(ImportStats), C.c_char_p, C.c_size_t]
     L.sbx_index_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.sbx_fixbins.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(FixbinsStats), C.c_char_p, C.c_size_t]
@@ -292,7 +305,7 @@ def lib():
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
                      ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats),
                      ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats),
-                     ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats)):
+                     ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats), ("sbx_slice_stats", SliceStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -786,6 +799,23 @@ def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, r
     if rc != 0:
         raise SbxError(rc, err.value.decode())
     return {k: getattr(st, k) for k, _ in ViewStats._fields_ if k != "reserved"}
+
+
+def slice_bam(in_path, out_path=None, regions=(), bed=None, device=-1):
+    """sbx_slice_bam (`sambamba slice`): the regions ("chr", "chr:beg-end", or "*" alone) or the BED file `bed` of the indexed BAM
+    in_path copied to out_path (None or "-": stdout) -- per region the records that start in front of it and reach it, then the
+    stretch of the stream from the first record at or behind its start to the first at or behind its end, with every BGZF block
+    that lies wholly inside written as it is in the file.  Returns the fields of sbx_slice_stats as a dict."""
+    L = lib()
+    regions = [regions] if isinstance(regions, str) else list(regions)
+    arr = (C.c_char_p * max(1, len(regions)))(*[r.encode() for r in regions])
+    st = SliceStats()
+    err = C.create_string_buffer(512)
+    rc = L.sbx_slice_bam(in_path.encode(), out_path.encode() if out_path else None, arr, len(regions), bed.encode() if bed else None, device,
+                         C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    return {k: getattr(st, k) for k, _ in SliceStats._fields_}
 
 
 def import_sam(in_path, out_path, level=-1, index=False, command_line=None, device=-1):

@@ -60,6 +60,7 @@ size_t sbx_abi_sizeof(const char* name) {
     if (n == "sbx_merge_stats") return sizeof(sbx_merge_stats);
     if (n == "sbx_view_opts") return sizeof(sbx_view_opts);
     if (n == "sbx_view_stats") return sizeof(sbx_view_stats);
+    if (n == "sbx_slice_stats") return sizeof(sbx_slice_stats);
     if (n == "sbx_import_stats") return sizeof(sbx_import_stats);
     if (n == "sbx_fixbins_stats") return sizeof(sbx_fixbins_stats);
     if (n == "sbx_fasta_stats") return sizeof(sbx_fasta_stats);

@@ -360,6 +360,8 @@ std::vector<FileRun> build_runs(const sbx_ctx* c, const std::vector<sbx_region>&
 void make_resident(sbx_ctx* c, std::vector<FileRun> runs);
 void inflate_worklist(sbx_ctx* c, hipEvent_t ev_mid);
 void parse_header_on_device(sbx_ctx* c);
+uint64_t voffset_to_stream(const sbx_ctx* c, uint64_t v, uint32_t* blk);
+std::vector<uint8_t> inflate_stream_prefix(sbx_ctx* c, uint64_t n_bytes);
 // engine_run.cpp
 void run_impl(sbx_ctx* c, const std::vector<sbx_region>& sel, bool restricted, const std::vector<FileRun>* given_runs = nullptr);
 }  // namespace sbx

@@ -34,50 +34,70 @@ struct BgzfPieceTimes { double ms_fill = 0, ms_deflate = 0, ms_pack = 0, ms_d2h 
 // receives consecutive pieces of the BGZF stream.  Blocks are cut every kBgzfPayload bytes.  pinned: the compressed piece travels
 // through pinned host memory.  times (may be null) accumulates; the wall-clock figures (fill, device -> host) are taken only when
 // `timing`, which synchronises after the fill.
+// The buffers of one such stream; run() may be called again for further streams of at most cap_blocks payloads per piece (sbx_slice_bam
+// compresses one short stream between every two stretches it copies from the file).
+class BgzfPieceCompressor {
+    Stream stream_;
+    uint32_t cap_blocks_;
+    int level_;
+    bool pinned_;
+    DevBuf<uint8_t> d_in_, d_slots_, d_out_;
+    DevBuf<uint16_t> d_tab_;
+    DevBuf<uint8_t> d_work_;
+    DevBuf<uint32_t> d_len_;
+    DevBuf<uint64_t> d_off_;
+    std::vector<uint8_t> host_;
+    PinnedBuf<uint8_t> host_pinned_;
+    EventTimer t_def_, t_pack_;
+
+public:
+    BgzfPieceCompressor(uint32_t cap_blocks, int level, bool pinned)
+        : cap_blocks_(cap_blocks), level_(level), pinned_(pinned), d_in_((size_t)cap_blocks * kBgzfPayload + 64),
+          d_slots_((size_t)cap_blocks * kBgzfSlot), d_out_((size_t)cap_blocks * kBgzfSlot), d_tab_(deflate_table_entries(cap_blocks)),
+          d_work_(deflate_work_bytes(cap_blocks)), d_len_(cap_blocks + 1), d_off_((size_t)cap_blocks + 2) {
+        stream_.create();
+    }
+    template <class Fill, class Sink>
+    void run(size_t n, bool timing, BgzfPieceTimes* times, Fill&& fill, Sink&& sink) {
+        hipStream_t s = stream_.get();
+        for (size_t done = 0; done < n;) {
+            const size_t bytes = std::min<size_t>(n - done, (size_t)cap_blocks_ * kBgzfPayload);
+            const uint32_t nb = (uint32_t)((bytes + kBgzfPayload - 1) / kBgzfPayload);
+            const double w0 = wall_now();
+            fill(d_in_.p, done, bytes, s);
+            if (timing) SBX_HIP(hipStreamSynchronize(s));
+            const double w1 = wall_now();
+            t_def_.start(s);
+            launch_bgzf_deflate(d_in_.p, bytes, nb, level_, d_slots_.p, d_tab_.p, d_work_.p, d_len_.p, s);
+            t_def_.stop(s);
+            t_pack_.start(s);
+            launch_count_scan(d_len_.p, nb, d_off_.p, s);
+            launch_pack_blocks(d_slots_.p, d_len_.p, d_off_.p, nb, d_out_.p, s);
+            t_pack_.stop(s);
+            uint64_t total = 0;
+            SBX_HIP(hipMemcpyAsync(&total, d_off_.p + nb, 8, hipMemcpyDeviceToHost, s));
+            SBX_HIP(hipStreamSynchronize(s));
+            const double w2 = wall_now();
+            uint8_t* h;
+            if (pinned_) { host_pinned_.ensure((size_t)total + 1); h = host_pinned_.p; }
+            else { host_.resize((size_t)total); h = host_.data(); }
+            SBX_HIP(hipMemcpy(h, d_out_.p, (size_t)total, hipMemcpyDeviceToHost));
+            if (times) {
+                times->ms_deflate += t_def_.ms(); times->ms_pack += t_pack_.ms(); times->out_bytes += total; ++times->n_pieces;
+                if (timing) { times->ms_fill += (w1 - w0) * 1e3; times->ms_d2h += (wall_now() - w2) * 1e3; }
+            }
+            sink(h, (size_t)total);
+            done += bytes;
+        }
+    }
+};
+
 template <class Fill, class Sink>
 void bgzf_compress_pieces(size_t n, size_t piece_blocks, int level, bool pinned, bool timing, BgzfPieceTimes* times, Fill&& fill, Sink&& sink) {
-    Stream stream;
-    stream.create();
-    hipStream_t s = stream.get();
     const size_t n_blocks_total = (n + kBgzfPayload - 1) / kBgzfPayload;
     const uint32_t cap_blocks = (uint32_t)std::min<size_t>(piece_blocks, std::max<size_t>(1, n_blocks_total));
-    DevBuf<uint8_t> d_in((size_t)cap_blocks * kBgzfPayload + 64), d_slots((size_t)cap_blocks * kBgzfSlot), d_out((size_t)cap_blocks * kBgzfSlot);
-    DevBuf<uint16_t> d_tab(deflate_table_entries(cap_blocks));
-    DevBuf<uint8_t> d_work(deflate_work_bytes(cap_blocks));
-    DevBuf<uint32_t> d_len(cap_blocks + 1);
-    DevBuf<uint64_t> d_off((size_t)cap_blocks + 2);
-    std::vector<uint8_t> host;
-    PinnedBuf<uint8_t> host_pinned;
-    EventTimer t_def, t_pack;
-    for (size_t done = 0; done < n;) {
-        const size_t bytes = std::min<size_t>(n - done, (size_t)cap_blocks * kBgzfPayload);
-        const uint32_t nb = (uint32_t)((bytes + kBgzfPayload - 1) / kBgzfPayload);
-        const double w0 = wall_now();
-        fill(d_in.p, done, bytes, s);
-        if (timing) SBX_HIP(hipStreamSynchronize(s));
-        const double w1 = wall_now();
-        t_def.start(s);
-        launch_bgzf_deflate(d_in.p, bytes, nb, level, d_slots.p, d_tab.p, d_work.p, d_len.p, s);
-        t_def.stop(s);
-        t_pack.start(s);
-        launch_count_scan(d_len.p, nb, d_off.p, s);
-        launch_pack_blocks(d_slots.p, d_len.p, d_off.p, nb, d_out.p, s);
-        t_pack.stop(s);
-        uint64_t total = 0;
-        SBX_HIP(hipMemcpyAsync(&total, d_off.p + nb, 8, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        const double w2 = wall_now();
-        uint8_t* h;
-        if (pinned) { host_pinned.ensure((size_t)total + 1); h = host_pinned.p; }
-        else { host.resize((size_t)total); h = host.data(); }
-        SBX_HIP(hipMemcpy(h, d_out.p, (size_t)total, hipMemcpyDeviceToHost));
-        if (times) {
-            times->ms_deflate += t_def.ms(); times->ms_pack += t_pack.ms(); times->out_bytes += total; ++times->n_pieces;
-            if (timing) { times->ms_fill += (w1 - w0) * 1e3; times->ms_d2h += (wall_now() - w2) * 1e3; }
-        }
-        sink(h, (size_t)total);
-        done += bytes;
-    }
+    BgzfPieceCompressor comp(cap_blocks, level, pinned);
+    comp.run(n, timing, times, fill, sink);
 }
 
 // compresses in[0, n) (host memory) piece by piece on the device; sink(data, len) receives consecutive pieces of the BGZF stream

@@ -12,7 +12,7 @@ namespace sbx {
 
 // ---- work list ---------------------------------------------------------------------------------------
 // virtual offset -> (file block, offset in the inflated stream of the file)
-static uint64_t voffset_to_stream(const sbx_ctx* c, uint64_t v, uint32_t* blk) {
+uint64_t voffset_to_stream(const sbx_ctx* c, uint64_t v, uint32_t* blk) {
     const uint32_t nb = (uint32_t)c->blocks.size();
     const uint64_t co = v >> 16, uo = v & 0xFFFF;
     const size_t bi = (size_t)(std::lower_bound(c->blocks.coffset.begin(), c->blocks.coffset.end(), co) - c->blocks.coffset.begin());
@@ -278,6 +278,17 @@ static void inflate_prefix(sbx_ctx* c, uint32_t k, std::vector<uint8_t>* host) {
                                          inflate_status_string(st[i]));
     host->resize(out_end);
     SBX_HIP(hipMemcpy(host->data(), d_out.p, out_end, hipMemcpyDeviceToHost));
+}
+
+// the first n_bytes of the inflated stream (sbx_slice_bam: the header bytes as the file has them)
+std::vector<uint8_t> inflate_stream_prefix(sbx_ctx* c, uint64_t n_bytes) {
+    std::vector<uint8_t> host;
+    if (!n_bytes) return host;
+    if (n_bytes > c->blocks.out_off.back()) throw Error(SBX_EFORMAT, "BAM header is truncated");
+    const uint32_t k = (uint32_t)(std::lower_bound(c->blocks.out_off.begin(), c->blocks.out_off.end(), n_bytes) - c->blocks.out_off.begin());
+    inflate_prefix(c, k, &host);
+    host.resize((size_t)n_bytes);
+    return host;
 }
 
 void parse_header_on_device(sbx_ctx* c) {

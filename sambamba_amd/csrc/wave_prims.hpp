@@ -1,6 +1,6 @@
 // wave_prims.hpp -- the wave and workgroup idioms the kernels of the resident-store commands and of the text commands share.  Included by
 // scan.hip, lines.hip, sort.hip (K9), markdup.hip (K10), merge.hip (K11), view.hip (K12), sam.hip (K13), namesort.hip (K14), samparse.hip
-// (K15), bins.hip (K16) and fasta.hip (K17).  (The depth path -- inflate, index, depth, reduce, mates, format, deflate, flagstat -- keeps
+// (K15), bins.hip (K16), fasta.hip (K17) and slice.hip (K18).  (The depth path -- inflate, index, depth, reduce, mates, format, deflate, flagstat -- keeps
 // private helpers with similar names and does not include this.)  A wave is 64 lanes; a workgroup a whole number of waves, its threads
 // numbered by threadIdx.x.
 #pragma once
