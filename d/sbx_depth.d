@@ -128,6 +128,38 @@ extern (C) nothrow @nogc {
     int sbx_view_sam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, const(sbx_view_opts)* opts, const(char*)* regions,
                      size_t n_regions, const(char)* bed_path, const(char)* pg_command_line, int with_header, int device,
                      sbx_view_stats* stats, char* err, size_t errlen);
+    // one entry point for the three sinks; the request starts with its own size and grows at its end.  valid_only: `view -v`
+    enum SBX_VIEW_SINK_COUNT = 0;
+    enum SBX_VIEW_SINK_BAM = 1;
+    enum SBX_VIEW_SINK_SAM = 2;
+    alias sbx_cstr = const(char)*;
+    alias sbx_cstr_list = const(char*)*;
+    alias sbx_filter_ptr = const(sbx_filter)*;
+    alias sbx_view_opts_ptr = const(sbx_view_opts)*;
+    struct sbx_view_request {
+        uint struct_size; int sink;
+        sbx_cstr in_path; sbx_cstr out_path; sbx_filter_ptr filter; sbx_view_opts_ptr opts; sbx_cstr_list regions; size_t n_regions;
+        sbx_cstr bed_path; sbx_cstr pg_command_line;
+        int level; int with_index; int with_header; int device;
+        int valid_only; int reserved;
+    }
+    int sbx_view_run(const(sbx_view_request)* request, ulong* count, sbx_view_stats* stats, char* err, size_t errlen);
+    // which records are valid (alignment.d's isValid), and why not: class k of the report is bit k of a record's mask
+    enum SBX_VALIDATE_CLASSES = 10;
+    struct sbx_validate_report {
+        ulong n_records; ulong n_invalid;
+        ulong[SBX_VALIDATE_CLASSES] class_count;
+        ulong first_ordinal;
+        uint first_mask; uint first_name_len;
+        char[256] first_name;
+    }
+    struct sbx_validate_stats {
+        double ms_inflate; double ms_index; double ms_valid; double ms_total_wall;
+        ulong inflated_bytes;
+        uint n_batches; uint reserved;
+    }
+    int sbx_validate_bam(const(char)* in_path, int device, sbx_validate_report* report, sbx_validate_stats* stats, char* err, size_t errlen);
+    int sbx_format_validate_report(const(char)* path, const(sbx_validate_report)* report, char* buf, size_t cap, size_t* len);
     /* `sambamba slice`: R1 and [a, b) per region, whole BGZF blocks copied from the file (see sbx_depth.h).  Divergences from slice.d's
        code, following its header comment: a is the first record with pos >= beg; b is the end of the contig's records when none starts
        at or behind end; FASTA input is not provided. */

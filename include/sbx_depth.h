@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -350,6 +350,70 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
 int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
                  size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device,
                  sbx_view_stats* stats, char* err, size_t errlen);
+/* One entry point for the three sinks, and the way in for options sbx_view_opts (whose size is fixed) cannot take.  The request
+ * begins with its own size as the caller compiled it: fields the caller's struct does not have are 0 here, so the struct grows at its
+ * end without new functions; a struct_size that ends in front of `device`'s end is SBX_EINVAL.  sink selects sbx_view_count (*count
+ * receives the entries; out_path, pg_command_line, level, with_index, with_header unused), sbx_view_bam (with_header unused) or
+ * sbx_view_sam (level, with_index unused); those three are this call with valid_only = 0, and every field means what their
+ * argument of the same name means.  count may be NULL for the other sinks.
+ * valid_only != 0 (`view -v`): K19 (sbx_validate_bam's kernel) runs on every batch in front of the selection and a record whose
+ * mask is not 0 is not selected, whatever else it passes -- also a record with a malformed fixed part or malformed tags, which
+ * without the option fails the call with SBX_EFORMAT when it is selected.  stats.ms_select includes the time of K19. */
+#define SBX_VIEW_SINK_COUNT 0
+#define SBX_VIEW_SINK_BAM 1
+#define SBX_VIEW_SINK_SAM 2
+typedef const char* sbx_cstr;
+typedef const char* const* sbx_cstr_list;
+typedef const sbx_filter* sbx_filter_ptr;
+typedef const sbx_view_opts* sbx_view_opts_ptr;
+typedef struct {
+    uint32_t struct_size;                      /* sizeof(sbx_view_request) */
+    int32_t sink;                              /* SBX_VIEW_SINK_* */
+    sbx_cstr in_path;
+    sbx_cstr out_path;
+    sbx_filter_ptr filter;
+    sbx_view_opts_ptr opts;
+    sbx_cstr_list regions;
+    size_t n_regions;
+    sbx_cstr bed_path;
+    sbx_cstr pg_command_line;
+    int32_t level, with_index, with_header, device;
+    int32_t valid_only, reserved;
+} sbx_view_request;
+int sbx_view_run(const sbx_view_request* request, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen);
+
+/* ---- validate: which records of a BAM are valid, and why not (`sambamba view -v`; `sambamba validate` is an empty stub) ----
+ * A record is valid when isValid of BioD bio/std/hts/bam/validation/alignment.d says so.  K19 evaluates every class of error on its
+ * own, so a record can be counted in several; class k, in this order: name-empty, name-chars (a byte < '!', > '~' or '@'), position
+ * (outside [-1, 2^29 - 2]), qualities (neither all 0xFF nor all <= 93), cigar-hard (H strictly inside), cigar-soft (S strictly inside
+ * once one H is taken off either end), cigar-length (l_seq > 0 differs from the M I S = X lengths), tag-value (a tag breaks a rule of
+ * its type or of its predefined key), tag-duplicate (two tags share a key), malformed.  Deliberate divergence: `malformed` -- a
+ * block_size below 32, l_read_name 0, name + CIGAR + sequence + qualities past block_size, a tag of unknown type, a B array of
+ * unknown element type, a tag value past the record, a Z / H without NUL -- makes the reference read past the record or throw; here
+ * the record is invalid.  A malformed fixed part is counted in `malformed` alone; with malformed tags the other classes cover what
+ * lies in front of the break.
+ * sbx_validate_bam streams the file in batches like sbx_flagstat (any BAM, sorted or not, indexed or not; nothing is resident;
+ * SBX_INDEX_BATCH_BYTES applies); what breaks the record chain is SBX_EFORMAT as there.  first_*: the first invalid record in file
+ * order, meaningful when n_invalid > 0 -- its 0-based ordinal, its mask (bit k = class k) and its name without the NUL (at most 254
+ * bytes, not terminated; length 0 when l_read_name is 0 or 32 + l_read_name exceeds block_size).  Milliseconds are device time (valid = K19). */
+#define SBX_VALIDATE_CLASSES 10
+typedef struct {
+    uint64_t n_records, n_invalid;
+    uint64_t class_count[SBX_VALIDATE_CLASSES];
+    uint64_t first_ordinal;
+    uint32_t first_mask, first_name_len;
+    char first_name[256];
+} sbx_validate_report;
+typedef struct {
+    double ms_inflate, ms_index, ms_valid, ms_total_wall;
+    uint64_t inflated_bytes;
+    uint32_t n_batches, reserved;
+} sbx_validate_stats;
+int sbx_validate_bam(const char* in_path, int device, sbx_validate_report* report, sbx_validate_stats* stats, char* err, size_t errlen);
+/* The report of `sbx-validate` for one file (host only), tab-separated lines: "file" path, "records" n, "invalid" m, the ten classes
+ * by name with their counts, and when m > 0 "first-invalid" with the ordinal, the name (bytes outside [!-~] and '\\' as \xHH) and the
+ * comma-joined names of its classes.  buf / cap / len as sbx_format_flagstat. */
+int sbx_format_validate_report(const char* path, const sbx_validate_report* report, char* buf, size_t cap, size_t* len);
 /* ---- `sambamba slice` (sambamba/slice.d): regions of an indexed BAM copied with their BGZF blocks reused ----
  * The records of in_path in file order are i = 0 .. n-1; record i occupies [u_i, u_{i+1}) of the inflated stream.  For a region
  * (r, beg, end): R1 = the records with ref == r, pos < beg and pos + basesCovered > beg; first_ge(x) = the first record with ref < 0,

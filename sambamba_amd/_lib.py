@@ -18,6 +18,7 @@ _NSORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-nsort")
 _IMPORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-import")
 _INDEX_CLI_PATH = os.path.join(HERE, "csrc", "sbx-index")
 _FIXBINS_CLI_PATH = os.path.join(HERE, "csrc", "sbx-fixbins")
+_VALIDATE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-validate")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -117,6 +118,29 @@ class ViewStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_regions", "n_sort_passes", "n_batches", "reserved")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_select", "ms_emit", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
 
+VIEW_SINKS = {"count": 0, "bam": 1, "sam": 2}
+
+
+class ViewRequest(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("sink", C.c_int32), ("in_path", C.c_char_p), ("out_path", C.c_char_p),
+                ("filter", C.POINTER(Filter)), ("opts", C.POINTER(ViewOpts)), ("regions", C.POINTER(C.c_char_p)), ("n_regions", C.c_size_t),
+                ("bed_path", C.c_char_p), ("pg_command_line", C.c_char_p), ("level", C.c_int32), ("with_index", C.c_int32),
+                ("with_header", C.c_int32), ("device", C.c_int32), ("valid_only", C.c_int32), ("reserved", C.c_int32)]
+
+
+VALIDATE_CLASSES = ("name-empty", "name-chars", "position", "qualities", "cigar-hard", "cigar-soft", "cigar-length", "tag-value",
+                    "tag-duplicate", "malformed")
+
+
+class ValidateReport(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_invalid", C.c_uint64), ("class_count", C.c_uint64 * len(VALIDATE_CLASSES)),
+                ("first_ordinal", C.c_uint64), ("first_mask", C.c_uint32), ("first_name_len", C.c_uint32), ("first_name", C.c_char * 256)]
+
+
+class ValidateStats(C.Structure):
+    _fields_ = ([(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_valid", "ms_total_wall")] + [("inflated_bytes", C.c_uint64)] +
+                [(k, C.c_uint32) for k in ("n_batches", "reserved")])
+
 class SliceStats(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("n_regions", "records_r1", "blocks_inflated", "blocks_copied", "bytes_copied", "stream_bytes",
                                            "compressed_bytes")] +
@@ -148,7 +172,8 @@ EXPORTS = [
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
     "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
-    "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_num_filter", "sbx_view_reference_info",
+    "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_run", "sbx_view_num_filter", "sbx_view_reference_info",
+    "sbx_validate_bam", "sbx_format_validate_report",
     "sbx_slice_bam",
     "sbx_import_sam",
     "sbx_index_bam", "sbx_fixbins", "sbx_index_fasta",
@@ -207,6 +232,10 @@ def index_cli_path():
 
 def fixbins_cli_path():
     return _FIXBINS_CLI_PATH
+
+
+def validate_cli_path():
+    return _VALIDATE_CLI_PATH
 
 
 def lib():
@@ -280,6 +309,9 @@ def lib():
                                C.c_int, C.c_int, C.c_int, C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
     L.sbx_view_sam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.POINTER(ViewOpts), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_char_p,
                                C.c_int, C.c_int, C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
+    L.sbx_view_run.argtypes = [C.POINTER(ViewRequest), C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
+    L.sbx_validate_bam.argtypes = [C.c_char_p, C.c_int, C.POINTER(ValidateReport), C.POINTER(ValidateStats), C.c_char_p, C.c_size_t]
+    L.sbx_format_validate_report.argtypes = [C.c_char_p, C.POINTER(ValidateReport), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_view_num_filter.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
     L.sbx_view_reference_info.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_slice_bam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_int, C.POINTER(SliceStats), C.c_char_p,
@@ -305,7 +337,8 @@ def lib():
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
                      ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats),
                      ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats),
-                     ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats), ("sbx_slice_stats", SliceStats)):
+                     ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats), ("sbx_slice_stats", SliceStats),
+                     ("sbx_view_request", ViewRequest), ("sbx_validate_report", ValidateReport), ("sbx_validate_stats", ValidateStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -755,14 +788,15 @@ def view_num_filter(text):
 
 
 def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, regions=(), bed=None, subsample=None, seed=None, level=-1,
-         index=False, command_line=None, device=-1, format="bam", with_header=False):
-    """sbx_view_count / sbx_view_bam / sbx_view_sam (`sambamba view -c` / `-f bam` / `-f sam`): the records of in_path that pass the -F query string `filter`,
+         index=False, command_line=None, device=-1, format="bam", with_header=False, valid=False):
+    """sbx_view_run (`sambamba view -c` / `-f bam` / `-f sam`): the records of in_path that pass the -F query string `filter`,
     `num_filter` ("i1/i2"), the subsampling (`subsample` = fraction, `seed` = 64-bit seed, drawn at random when None) and overlap
     `regions` ("chr", "chr:beg-end", "*": once per listed region, in listed order) or the BED file `bed` (once, in file order).
     count=True returns their number; otherwise they are written to out_path ("-": stdout) as a BAM -- index=True also writes
     out_path + ".bai", command_line is the CL field of the @PG line that is added (None: no @PG) -- and the fields of sbx_view_stats
     come back as a dict.  format="sam" writes SAM text instead, formatted on the device: one line per record, after the header text
-    when with_header (`view -h`); level and index do not apply to it (ValueError)."""
+    when with_header (`view -h`); level and index do not apply to it (ValueError).  valid=True (`view -v`): only the records validate() calls
+    valid are selected."""
     if format not in ("bam", "sam"):
         raise ValueError("view: format must be 'bam' or 'sam'")
     if format == "sam" and (level != -1 or index):
@@ -781,24 +815,67 @@ def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, r
     err = C.create_string_buffer(512)
     fp = C.byref(f) if f is not None else None
     bedp = bed.encode() if bed else None
-    if count:
-        n = C.c_uint64(0)
-        rc = L.sbx_view_count(in_path.encode(), fp, C.byref(o), arr, len(regions), bedp, device, C.byref(n), C.byref(st), err, 512)
-        if rc != 0:
-            raise SbxError(rc, err.value.decode())
-        return int(n.value)
-    if out_path is None:
+    if not count and out_path is None:
         raise ValueError("view: out_path is required unless count=True ('-' writes to stdout)")
-    cl = command_line.encode() if command_line is not None else None
-    if format == "sam":
-        rc = L.sbx_view_sam(in_path.encode(), out_path.encode(), fp, C.byref(o), arr, len(regions), bedp, cl, int(bool(with_header)), device,
-                            C.byref(st), err, 512)
-    else:
-        rc = L.sbx_view_bam(in_path.encode(), out_path.encode(), fp, C.byref(o), arr, len(regions), bedp, cl, int(level), int(index), device,
-                            C.byref(st), err, 512)
+    q = ViewRequest()
+    q.struct_size = C.sizeof(ViewRequest)
+    q.sink = VIEW_SINKS["count" if count else format]
+    q.in_path = in_path.encode()
+    q.out_path = None if count else out_path.encode()
+    q.filter = C.pointer(f) if f is not None else None
+    q.opts = C.pointer(o)
+    q.regions, q.n_regions = arr, len(regions)
+    q.bed_path = bed.encode() if bed else None
+    q.pg_command_line = command_line.encode() if command_line is not None else None
+    q.level, q.with_index, q.with_header, q.device = int(level), int(index), int(bool(with_header)), device
+    q.valid_only = int(bool(valid))
+    n = C.c_uint64(0)
+    rc = L.sbx_view_run(C.byref(q), C.byref(n), C.byref(st), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
+    if count:
+        return int(n.value)
     return {k: getattr(st, k) for k, _ in ViewStats._fields_ if k != "reserved"}
+
+
+def validate(path, device=-1):
+    """sbx_validate_bam (`sambamba view -v` as a report): every record of the BAM judged on the device by the reference's isValid.
+    Returns n_records, n_invalid, class_count ({class name: records}; a record can be in several) and, when n_invalid > 0,
+    first_invalid = {ordinal, mask, classes, name (bytes)} for the first invalid record in file order (else None), plus the fields of
+    sbx_validate_stats under "stats"."""
+    L = lib()
+    r, st = ValidateReport(), ValidateStats()
+    err = C.create_string_buffer(512)
+    rc = L.sbx_validate_bam(path.encode(), device, C.byref(r), C.byref(st), err, 512)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    first = None
+    if r.n_invalid:
+        first = {"ordinal": int(r.first_ordinal), "mask": int(r.first_mask),
+                 "classes": [c for k, c in enumerate(VALIDATE_CLASSES) if r.first_mask >> k & 1],
+                 "name": C.string_at(C.addressof(r) + ValidateReport.first_name.offset, r.first_name_len)}
+    return {"n_records": int(r.n_records), "n_invalid": int(r.n_invalid),
+            "class_count": {c: int(r.class_count[k]) for k, c in enumerate(VALIDATE_CLASSES)}, "first_invalid": first,
+            "stats": {k: getattr(st, k) for k, _ in ValidateStats._fields_ if k != "reserved"}}
+
+
+def format_validate_report(path, n_records, n_invalid, class_count, first_invalid=None):
+    """sbx_format_validate_report: the text `sbx-validate` prints for one file (host only); the arguments as validate() returns them."""
+    L = lib()
+    r = ValidateReport()
+    r.n_records, r.n_invalid = n_records, n_invalid
+    for k, c in enumerate(VALIDATE_CLASSES):
+        r.class_count[k] = class_count.get(c, 0)
+    if first_invalid is not None:
+        r.first_ordinal, r.first_mask, r.first_name_len = first_invalid["ordinal"], first_invalid["mask"], len(first_invalid["name"])
+        C.memmove(C.addressof(r) + ValidateReport.first_name.offset, first_invalid["name"], len(first_invalid["name"]))
+    n = C.c_size_t(0)
+    L.sbx_format_validate_report(path.encode(), C.byref(r), None, 0, C.byref(n))
+    buf = C.create_string_buffer(n.value + 1)
+    rc = L.sbx_format_validate_report(path.encode(), C.byref(r), buf, n.value + 1, C.byref(n))
+    if rc != 0:
+        raise SbxError(rc, "sbx_format_validate_report failed")
+    return buf.raw[:n.value]
 
 
 def slice_bam(in_path, out_path=None, regions=(), bed=None, device=-1):

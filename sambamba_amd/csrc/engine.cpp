@@ -64,6 +64,9 @@ size_t sbx_abi_sizeof(const char* name) {
     if (n == "sbx_import_stats") return sizeof(sbx_import_stats);
     if (n == "sbx_fixbins_stats") return sizeof(sbx_fixbins_stats);
     if (n == "sbx_fasta_stats") return sizeof(sbx_fasta_stats);
+    if (n == "sbx_view_request") return sizeof(sbx_view_request);
+    if (n == "sbx_validate_report") return sizeof(sbx_validate_report);
+    if (n == "sbx_validate_stats") return sizeof(sbx_validate_stats);
     return 0;
 }
 

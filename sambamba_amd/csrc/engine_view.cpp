@@ -1,4 +1,6 @@
-// engine_view.cpp -- sbx_view_count / sbx_view_bam / sbx_view_sam: the record selection of `sambamba view` (sambamba/view.d) on the device.
+// engine_view.cpp -- sbx_view_run, and sbx_view_count / sbx_view_bam / sbx_view_sam as that call with valid_only = 0: the record
+// selection of `sambamba view` (sambamba/view.d) on the device.  With valid_only (`view -v`) K19 (valid.hip) runs on every batch in
+// front of K12a, which then selects no record whose mask is not 0; its time is part of ms_select.
 //
 // One index-mode pass over the input (for_each_record_batch: K1 + K2 per batch, K2 leaving the verdict of -F in RecDesc::pad); per
 // batch K12a (view.hip) decides, for every record, how many times it is selected.  -c adds that up and stores nothing, so it streams
@@ -16,6 +18,7 @@
 #include "engine_store.hpp"
 #include "markdup_core.hpp"
 #include "sam.hpp"
+#include "valid.hpp"
 #include "view.hpp"
 #include "view_core.hpp"
 
@@ -70,7 +73,7 @@ void check_opts(const sbx_filter* filter, const sbx_view_opts* opts, uint64_t* t
 }
 
 ViewSelectArgs select_args(sbx_ctx* c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& regions, const sbx_region* d_regions,
-                           uint64_t nrec, uint64_t u_end, unsigned long long* d_acc) {
+                           uint64_t nrec, uint64_t u_end, unsigned long long* d_acc, const uint16_t* d_invalid) {
     ViewSelectArgs a{};
     a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = u_end;
     if (opts) {
@@ -79,8 +82,33 @@ ViewSelectArgs select_args(sbx_ctx* c, const sbx_view_opts* opts, uint64_t thres
     }
     a.regions = d_regions; a.n_regions = (uint32_t)regions.list.size(); a.regions_merged = regions.merged ? 1u : 0u;
     a.acc = d_acc;
+    a.invalid = d_invalid;
     return a;
 }
+
+// view -v: K19 in front of K12a.  run() leaves the masks of the batch's records and returns them; null when the option is off.
+struct ValidPass {
+    bool on = false;
+    DevBuf<uint16_t> mask;
+    DevBuf<unsigned long long> acc;
+    uint64_t rec_base = 0;
+    void init(bool valid_only, hipStream_t s) {
+        on = valid_only;
+        if (!on) return;
+        unsigned long long zero[kValidAccWords] = {0};
+        zero[kValidAccFirst] = kValidNone;
+        acc.alloc(kValidAccWords);
+        SBX_HIP(hipMemcpyAsync(acc.p, zero, sizeof zero, hipMemcpyHostToDevice, s));
+        SBX_HIP(hipStreamSynchronize(s));
+    }
+    const uint16_t* run(sbx_ctx* c, uint64_t nrec, uint64_t u_end, hipStream_t s) {
+        if (!on) return nullptr;
+        mask.ensure((size_t)nrec + 2);
+        launch_valid_masks(ValidArgs{c->U(), c->d_desc.p, nrec, u_end, rec_base, mask.p, acc.p}, s);
+        rec_base += nrec;
+        return mask.p;
+    }
+};
 
 void upload_regions(const ViewRegions& regions, DevBuf<sbx_region>* d, hipStream_t s) {
     d->ensure(regions.list.size() + 1);
@@ -113,8 +141,8 @@ struct SelectedRecords {
 // Reads the file (K1, K2, K12a, K12b per batch; the records go to the store), closes the context and orders the entries (K9b over
 // the region index for listed regions).  hlen / per_record: bytes of the sink's header and of the per-record arrays it will add,
 // for the refusal of a file that does not fit.  Fills the counts and the times of the passes into *st.
-void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& sel, uint64_t hlen, uint64_t per_record,
-                     SelectedRecords* out, sbx_view_stats* st_out) {
+void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& sel, bool valid_only, uint64_t hlen,
+                     uint64_t per_record, SelectedRecords* out, sbx_view_stats* st_out) {
     sbx_view_stats& st = *st_out;
     const bool listed = !sel.merged && !sel.list.empty();
     DevBuf<uint8_t>& d_store = out->store;
@@ -133,6 +161,8 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
     DevBuf<unsigned long long> d_acc(kViewAccWords);
     SBX_HIP(hipMemsetAsync(d_acc.p, 0, kViewAccWords * sizeof(unsigned long long), s));
     SBX_HIP(hipStreamSynchronize(s));
+    ValidPass valid;
+    valid.init(valid_only, s);
 
     // ---- the read pass ----
     EventTimer t_a, t_b;
@@ -147,7 +177,8 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
         d_group_entry_base.ensure(groups + 4); d_group_record_base.ensure(groups + 4);
         t_a.start(s);
         copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
-        ViewSelectArgs a = select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p);
+        const uint16_t* d_invalid = valid.run(c.get(), nrec, next - base, s);
+        ViewSelectArgs a = select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p, d_invalid);
         a.with_lengths = 1;
         a.count = d_count.p; a.group_entries = d_group_entries.p; a.group_records = d_group_records.p;
         launch_view_select(a, s);
@@ -256,8 +287,13 @@ int sbx_view_reference_info(sbx_ctx* c, char* out, size_t cap, size_t* out_len) 
     return copy_to_caller(viewc::reference_info_json(names, lengths), out, cap, out_len);
 }
 
-int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions, size_t n_regions,
-                   const char* bed_path, int device, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
+}  // extern "C"
+
+namespace {
+
+// ---- the three sinks: the bodies behind sbx_view_run ----
+int view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions, size_t n_regions,
+               const char* bed_path, int device, int valid_only, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
     return run_entry(err, errlen, [&] {
         if (!in_path || !count) throw Error(SBX_EINVAL, "null argument");
         uint64_t threshold = 0;
@@ -271,12 +307,15 @@ int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view
         DevBuf<unsigned long long> d_acc(kViewAccWords);
         SBX_HIP(hipMemsetAsync(d_acc.p, 0, kViewAccWords * sizeof(unsigned long long), s));
         sbx_view_stats st{};
+        ValidPass valid;
+        valid.init(valid_only != 0, s);
         EventTimer t_k;
         uint64_t n_in = 0;
         uint32_t n_batches = 0;
         for_each_record_batch(c.get(), index_batch_bytes(), &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
             t_k.start(s);
-            launch_view_select(select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p), s);
+            const uint16_t* d_invalid = valid.run(c.get(), nrec, next - base, s);
+            launch_view_select(select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p, d_invalid), s);
             t_k.stop(s);
             // (the next batch's K2 overwrites these descriptors, and may reallocate them, from the host side: K12a ends first)
             SBX_HIP(hipStreamSynchronize(s));
@@ -299,9 +338,9 @@ int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view
     });
 }
 
-int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
-                 size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device,
-                 sbx_view_stats* stats, char* err, size_t errlen) {
+int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
+             size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device, int valid_only,
+             sbx_view_stats* stats, char* err, size_t errlen) {
     const bool to_stdout = !out_path || !strcmp(out_path, "-");
     const char* const path = to_stdout ? "/dev/stdout" : out_path;
     const int rc = run_entry(err, errlen, [&] {
@@ -322,7 +361,7 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
 
         sbx_view_stats st{};
         SelectedRecords r;
-        select_resident(c, opts, threshold, sel, hlen, 48, &r, &st);
+        select_resident(c, opts, threshold, sel, valid_only != 0, hlen, 48, &r, &st);
         const uint64_t n = r.n;
         hipStream_t s = r.stream.get();
         DevBuf<uint64_t> d_out_off((size_t)n + 2);
@@ -339,9 +378,9 @@ int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* fi
     return rc != SBX_OK ? rc : index_written_bam(path, with_index, device, err, errlen);
 }
 
-int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
-                 size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device, sbx_view_stats* stats,
-                 char* err, size_t errlen) {
+int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
+             size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device, int valid_only,
+             sbx_view_stats* stats, char* err, size_t errlen) {
     const bool to_stdout = !out_path || !strcmp(out_path, "-");
     const char* const path = to_stdout ? "/dev/stdout" : out_path;
     return run_entry(err, errlen, [&] {
@@ -359,7 +398,7 @@ int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* fi
         const std::vector<RefSeq> refs = c->hdr.refs;       // (select_resident lets go of the context)
         sbx_view_stats st{};
         SelectedRecords r;
-        select_resident(c, opts, threshold, sel, text.size(), 48 + 12, &r, &st);       // (+ length and offset of every line)
+        select_resident(c, opts, threshold, sel, valid_only != 0, text.size(), 48 + 12, &r, &st);       // (+ length and offset of every line)
         const uint64_t n = r.n;
         hipStream_t s = r.stream.get();
         DeviceRefNames names;
@@ -453,6 +492,64 @@ int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* fi
                     (unsigned long long)budget);
         if (stats) *stats = st;
     });
+}
+
+sbx_view_request request_of(int sink, const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts,
+                            const char* const* regions, size_t n_regions, const char* bed_path, const char* pg_command_line, int device) {
+    sbx_view_request q{};
+    q.struct_size = (uint32_t)sizeof q;
+    q.sink = sink;
+    q.in_path = in_path; q.out_path = out_path; q.filter = filter; q.opts = opts;
+    q.regions = regions; q.n_regions = n_regions; q.bed_path = bed_path; q.pg_command_line = pg_command_line;
+    q.level = -1; q.device = device;
+    return q;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sbx_view_run(const sbx_view_request* request, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
+    sbx_view_request q{};
+    const int rc = run_entry(err, errlen, [&] {
+        if (!request) throw Error(SBX_EINVAL, "null argument");
+        if (request->struct_size < offsetof(sbx_view_request, valid_only))
+            throw Error(SBX_EINVAL, "sbx_view_request: struct_size " + std::to_string(request->struct_size) + " is smaller than the first version of the struct");
+        memcpy(&q, request, std::min<size_t>(request->struct_size, sizeof q));      // (what the caller's struct lacks stays 0)
+        if (q.sink != SBX_VIEW_SINK_COUNT && q.sink != SBX_VIEW_SINK_BAM && q.sink != SBX_VIEW_SINK_SAM)
+            throw Error(SBX_EINVAL, "sbx_view_request: unknown sink " + std::to_string(q.sink));
+    });
+    if (rc != SBX_OK) return rc;
+    if (q.sink == SBX_VIEW_SINK_COUNT)
+        return view_count(q.in_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.device, q.valid_only, count, stats, err, errlen);
+    if (q.sink == SBX_VIEW_SINK_BAM)
+        return view_bam(q.in_path, q.out_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.pg_command_line, q.level, q.with_index,
+                        q.device, q.valid_only, stats, err, errlen);
+    return view_sam(q.in_path, q.out_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.pg_command_line, q.with_header, q.device,
+                    q.valid_only, stats, err, errlen);
+}
+
+// the three entry points of before sbx_view_run: the same call with valid_only = 0
+int sbx_view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions, size_t n_regions,
+                   const char* bed_path, int device, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
+    const sbx_view_request q = request_of(SBX_VIEW_SINK_COUNT, in_path, nullptr, filter, opts, regions, n_regions, bed_path, nullptr, device);
+    return sbx_view_run(&q, count, stats, err, errlen);
+}
+
+int sbx_view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
+                 size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device,
+                 sbx_view_stats* stats, char* err, size_t errlen) {
+    sbx_view_request q = request_of(SBX_VIEW_SINK_BAM, in_path, out_path, filter, opts, regions, n_regions, bed_path, pg_command_line, device);
+    q.level = level; q.with_index = with_index;
+    return sbx_view_run(&q, nullptr, stats, err, errlen);
+}
+
+int sbx_view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
+                 size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device, sbx_view_stats* stats,
+                 char* err, size_t errlen) {
+    sbx_view_request q = request_of(SBX_VIEW_SINK_SAM, in_path, out_path, filter, opts, regions, n_regions, bed_path, pg_command_line, device);
+    q.with_header = with_header;
+    return sbx_view_run(&q, nullptr, stats, err, errlen);
 }
 
 }  // extern "C"

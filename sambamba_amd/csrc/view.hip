@@ -8,7 +8,8 @@
 //                        number of entries (0, 1, or one per overlapped region) is stored; the entries and the selected records of a
 //                        workgroup are summed (block_sum, block_rank_of_kept: wave_prims.hpp) so that two exclusive scans
 //                        (launch_count_scan) give every workgroup its first output slots -- the file-order-preserving compaction
-//                        of K9a.  For -c nothing is stored: one atomicAdd per wave into the file's counter.
+//                        of K9a.  For -c nothing is stored: one atomicAdd per wave into the file's counter.  With -v the lane first
+//                        reads the mask K19 left for its record (ViewSelectArgs::invalid): not 0, and nothing else is asked.
 //   K12b k_view_emit     the same lanes again: a selected record's ordinal is the workgroup's base + the selected threads in front
 //                        of it (block_rank_of_kept), its first entry the base + an exclusive prefix of the counts (block_exclusive).
 //                        Store offset and length are written once per record; for listed regions the list is walked again and
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(kViewThreads) void k_view_select(ViewSelectArgs a) 
         pos = d.pos;
         covered = (uint32_t)(d.end - d.pos);
         rec_off = d.rec_off;
-        pass = passes_filters(a, d, &bad);
+        pass = !(a.invalid && a.invalid[i]) && passes_filters(a, d, &bad);
     }
     if (a.n_regions == 0) cnt = pass ? 1u : 0u;
     else if (a.regions_merged) cnt = pass && in_merged(a.regions, a.n_regions, ref, pos, covered) ? 1u : 0u;

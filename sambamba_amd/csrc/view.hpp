@@ -25,6 +25,8 @@ struct ViewSelectArgs {
     uint32_t* group_entries;        // [view_groups(n)] out: entries per workgroup; null for -c
     uint32_t* group_records;        // [view_groups(n)] out: selected records per workgroup; null for -c
     unsigned long long* acc;        // [kViewAccWords]
+    const uint16_t* invalid;        // [n] the masks of K19 (valid.hip), or null: a record whose mask is not 0 is not selected and is not
+                                    // counted as malformed either, whatever RecDesc::pad says (view -v)
 };
 constexpr uint32_t kViewThreads = 256;
 inline uint32_t view_groups(uint64_t n) { return (uint32_t)((n + kViewThreads - 1) / kViewThreads); }

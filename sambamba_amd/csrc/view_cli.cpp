@@ -1,6 +1,6 @@
 // view_cli.cpp -- `sbx-view`: the command line of `sambamba-view` (view_main / sambambaMain, sambamba/view.d:149-403) on top of the
-// C ABI of libsbx_depth.so.  Reading, selecting and compressing happen on the device (sbx_view_count / sbx_view_bam); this file
-// parses the options and prints the host-only outputs (-H, -I).
+// C ABI of libsbx_depth.so.  Reading, selecting and compressing happen on the device (sbx_view_run); this file parses the options
+// and prints the host-only outputs (-H, -I).
 //
 //   sbx-view [options] <input.bam> [region1 [...]]
 //
@@ -12,9 +12,10 @@
 // "view" followed by the arguments as given.  Errors: "sbx-view: <message>" on stderr and exit status 1.
 //
 // Compiled a second time with -DSBX_VIEW_SAM=1 this file is `sbx-sam`: the same options under the same policy, with the third sink
-// (sbx_view_sam).  There `sam` is the default format as in the reference, -f sam and -f bam are both taken, -h writes the header in
-// front of the SAM records, and -l together with SAM output is refused.  (sbx-view keeps refusing sam: folding the two into one
-// executable is the removal of this switch.)
+// (SBX_VIEW_SINK_SAM).  There `sam` is the default format as in the reference, -f sam and -f bam are both taken, -h writes the header in
+// front of the SAM records, -l together with SAM output is refused, and -v / --valid is taken for all three sinks: only the records
+// the reference's isValid accepts are selected (sbx_view_request::valid_only, K19).  (sbx-view keeps refusing sam and -v: folding the
+// two into one executable is the removal of this switch.)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -66,9 +67,11 @@ void usage() {
           "                    subsample reads (read pairs)\n"
           "         --subsampling-seed=SEED\n"
           "                    set seed for subsampling\n"
+          "         -v, --valid\n"
+          "                    output only valid alignments\n"
           "         -t, --nthreads=NTHREADS, -p, --show-progress, -T, --ref-filename=FASTA\n"
           "                    accepted for compatibility\n"
-          "         -v, --valid, -S, --sam-input\n"
+          "         -S, --sam-input\n"
           "                    not supported\n"
           "\n"
           "Regions are 'chr', 'chr:beg-end' or '*' (reads without a reference); at most 1024 may be listed, a BED file has no limit.\n"
@@ -158,13 +161,13 @@ int print_text(const std::string& in, bool reference_info) {
 
 int main(int argc, char** argv) {
     std::string filter_str, num_filter, format = "sam", bed, level_str, out, frac_str, seed_str;
-    bool have_num_filter = false, have_frac = false, have_seed = false, header_only = false, reference_info = false, count_only = false, with_header = false;
+    bool have_num_filter = false, have_frac = false, have_seed = false, header_only = false, reference_info = false, count_only = false, with_header = false, valid_only = false;
     std::vector<std::string> files;
     // long name, short name, takes a value, what it does: 0 ignored, 1 filter, 2 num-filter, 3 format, 4 -H, 5 -I, 6 -L, 7 -c, 8 level, 9 out,
-    // 10 fraction, 11 seed, 12 refused, 13 -h
+    // 10 fraction, 11 seed, 12 refused, 13 -h, 14 -v
     static const sbx::OptSpec opts[] = {
         {"filter", 'F', true, 1}, {"num-filter", 0, true, 2}, {"format", 'f', true, 3}, {"with-header", 'h', false, 13}, {"header", 'H', false, 4},
-        {"reference-info", 'I', false, 5}, {"regions", 'L', true, 6}, {"count", 'c', false, 7}, {"valid", 'v', false, 12},
+        {"reference-info", 'I', false, 5}, {"regions", 'L', true, 6}, {"count", 'c', false, 7}, {"valid", 'v', false, SBX_VIEW_SAM ? 14 : 12},
         {"sam-input", 'S', false, 12}, {"show-progress", 'p', false, 0}, {"compression-level", 'l', true, 8}, {"output-filename", 'o', true, 9},
         {"nthreads", 't', true, 0}, {"subsample", 's', true, 10}, {"subsampling-seed", 0, true, 11}, {"ref-filename", 'T', true, 0},
     };
@@ -193,6 +196,7 @@ int main(int argc, char** argv) {
             case 10: frac_str = t.value; have_frac = true; break;
             case 11: seed_str = t.value; have_seed = true; break;
             case 13: with_header = true; break;
+            case 14: valid_only = true; break;
             default: break;
         }
     }
@@ -247,27 +251,31 @@ int main(int argc, char** argv) {
     if (have_filter && sbx_compile_filter(filter_str.c_str(), &filter, err, sizeof err) != SBX_OK) return die(err);
     std::vector<const char*> regions;
     for (size_t k = 1; k < files.size(); ++k) regions.push_back(files[k].c_str());
+    sbx_view_request q;
+    memset(&q, 0, sizeof q);
+    q.struct_size = (uint32_t)sizeof q;
+    q.in_path = in.c_str();
+    q.filter = have_filter ? &filter : nullptr;
+    q.opts = &vo;
+    q.regions = regions.data();
+    q.n_regions = regions.size();
+    q.bed_path = bed.c_str();
+    q.level = level;
+    q.device = -1;
+    q.valid_only = valid_only ? 1 : 0;
     if (count_only) {
         uint64_t count = 0;
-        const int rc = sbx_view_count(in.c_str(), have_filter ? &filter : nullptr, &vo, regions.data(), regions.size(), bed.c_str(), -1, &count, nullptr,
-                                      err, sizeof err);
-        if (rc != SBX_OK) return die(err);
+        q.sink = SBX_VIEW_SINK_COUNT;
+        if (sbx_view_run(&q, &count, nullptr, err, sizeof err) != SBX_OK) return die(err);
         printf("%llu\n", (unsigned long long)count);
         return 0;
     }
     std::string cl = "view";
     for (int i = 1; i < argc; ++i) { cl += ' '; cl += argv[i]; }
-#if SBX_VIEW_SAM
-    if (sam_out) {
-        const int rc = sbx_view_sam(in.c_str(), out.empty() ? "-" : out.c_str(), have_filter ? &filter : nullptr, &vo, regions.data(), regions.size(),
-                                    bed.c_str(), cl.c_str(), with_header ? 1 : 0, -1, nullptr, err, sizeof err);
-        if (rc != SBX_OK) return die(err);
-        return 0;
-    }
-#endif
-    (void)with_header;
-    const int rc = sbx_view_bam(in.c_str(), out.empty() ? "-" : out.c_str(), have_filter ? &filter : nullptr, &vo, regions.data(), regions.size(),
-                                bed.c_str(), cl.c_str(), level, 0, -1, nullptr, err, sizeof err);
-    if (rc != SBX_OK) return die(err);
+    q.sink = sam_out ? SBX_VIEW_SINK_SAM : SBX_VIEW_SINK_BAM;
+    q.out_path = out.empty() ? "-" : out.c_str();
+    q.pg_command_line = cl.c_str();
+    q.with_header = with_header ? 1 : 0;
+    if (sbx_view_run(&q, nullptr, nullptr, err, sizeof err) != SBX_OK) return die(err);
     return 0;
 }
