@@ -69,7 +69,8 @@ struct HostResults {
 //   kFlagTicket         cleared and copied back with the three before it; no kernel takes it (the tickets of the scans live in d_scan_part).
 //   kFlagRewalked       launch_rewalk_mismatched / launch_chain_repair add the blocks they walked again; repair_chain clears it before
 //                       every launch and reads it after.
-//   kFlagMaxPartners    launch_max_u32 over n_partners (-m); accumulate_pass reads it and chooses between pairs and partner lists.
+//   kFlagMaxPartners    launch_max_u32 over n_partners (-m); accumulate_pass reads it and chooses between pairs and partner lists;
+//                       bit 31: one name in two samples next to a same-sample partner, which accumulate_pass refuses.
 //   kFlagMatesOverflow  launch_accumulate_mates (-m, `base`): != 0, more overlapping same-name records on a position than K7 pairs;
 //                       accumulate_pass reads it and refuses.
 //   kFlagCrossFile      launch_cross_file_mates (-m, several BAMs): != 0, a same-name pair lies in two files; run_files clears and reads it.

@@ -409,9 +409,16 @@ static CounterLayout accumulate_pass(sbx_ctx* c, PassGeometry g, const IndexResu
         launch_max_u32(c->d_n_partners.p, n_records, c->d_flag.p + kFlagMaxPartners, s);
         SBX_HIP(hipMemcpyAsync(&R.max_partners, c->d_flag.p + kFlagMaxPartners, 4, hipMemcpyDeviceToHost, s));
         SBX_HIP(hipStreamSynchronize(s));
-        const char* many_msg = "--fix-mate-overlaps: four or more overlapping records with the same name cover one position (or, in region / "
-                               "window mode, a record overlaps two or more such records); the reference's result then depends on the hash "
-                               "order of unrelated reads (depth.d:343-377) and is not on the device path";
+        const char* many_msg = "--fix-mate-overlaps: four or more overlapping records with the same name cover one position, or one record "
+                               "overlaps four or more records with the same name wherever they lie (or, in region / window mode, a record "
+                               "overlaps two or more such records); the reference's result then depends on the hash order of unrelated "
+                               "reads (depth.d:343-377) and is not on the device path";
+        // bit 31: some record has a partner AND overlaps a same-name record of another sample.  In the reference's column that record
+        // can sort between the partners, which then are no neighbours and do not pair (depth.d:343-377)
+        if (R.max_partners & 0x80000000u)
+            throw Error(SBX_EUNSUPPORTED, "--fix-mate-overlaps: overlapping records with the same name belong to different samples and two "
+                                          "of them to the same one; whether the reference pairs those two depends on the order of the "
+                                          "column (depth.d:343-377) and is not on the device path");
         if (R.max_partners > 1 && c->mode != SBX_MODE_BASE) throw Error(SBX_EUNSUPPORTED, many_msg);
         if (c->mode == SBX_MODE_BASE) {
             const bool multi = R.max_partners > 1;

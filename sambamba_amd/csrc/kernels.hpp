@@ -191,7 +191,7 @@ void launch_accumulate(const uint8_t* d_U, const RecDesc* d_desc, const uint32_t
 
 // ---- K7: --fix-mate-overlaps, base mode (mates.hip) ---------------------------------------
 // d_mate[i] = index of the single overlapping same-name record of i (0xFFFFFFFF: none),
-// d_n_partners[i] = how many were found (> 1 is outside the supported scope)
+// d_n_partners[i] = how many were found (> 1: partner lists), bit 31: i overlaps a same-name record of ANOTHER sample
 void launch_find_mates(const uint8_t* d_U, const RecDesc* d_desc, const uint64_t* d_hash, const int32_t* d_rec_ref, uint64_t n_records,
                        uint32_t* d_mate, uint32_t* d_n_partners, hipStream_t stream);
 // second pass when some record has more than one partner: up to three partners per record in d_ext[3 i ..] (d_n_partners is
@@ -208,7 +208,8 @@ void launch_accumulate_mates(const uint8_t* d_U, const RecDesc* d_desc, const ui
                              const uint32_t* d_tile_hi, const uint32_t* d_active, uint32_t n_active, const uint32_t* d_tile_base,
                              int32_t n_ref, uint32_t tile_pos, uint32_t n_samples, uint32_t min_bq, const uint32_t* d_ext,
                              const uint32_t* d_n_partners, uint32_t* d_too_many, uint32_t* d_counters, uint32_t* d_span, hipStream_t stream);
-// max over records of n_partners (single block reduction into *d_out)
+// max over records of n_partners as launch_find_mates leaves it, into *d_out; bit 31 of a record counts only where its count is
+// not zero, so bit 31 of the result says: some record has a partner AND a same-name neighbour of another sample (refused)
 void launch_max_u32(const uint32_t* d_in, uint64_t n, uint32_t* d_out, hipStream_t stream);
 
 // ---- K5: region / window statistics (reduce.hip) --------------------------------------------

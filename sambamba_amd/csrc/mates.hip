@@ -63,15 +63,24 @@ __device__ bool same_name(const uint8_t* U, const RecDesc& a, const RecDesc& b) 
 // A workgroup of find_mates / find_partners looks at the 1024 records from its first one on (a window staged in LDS); a lane whose
 // span reaches beyond the window (coverage in the thousands) finishes in global memory.
 constexpr uint32_t kFindWin = 1024;
+// bit 31 of n_partners[] after find_mates: the record overlaps a same-name record of another sample (the count is below it)
+constexpr uint32_t kOtherSample = 0x80000000u;
 
 __device__ __forceinline__ void link_if_mates(const uint8_t* U, const RecDesc* desc, const uint64_t* hash, const RecDesc& a, uint64_t h,
                                               uint64_t i, uint64_t j, uint32_t* mate, uint32_t* n_partners) {
     const RecDesc b = desc[j];
-    if (b.kind != 0 && hash[j] == h && b.sample == a.sample && b.end > a.pos && same_name(U, a, b)) {
-        mate[i] = (uint32_t)j;
-        mate[j] = (uint32_t)i;
-        atomicAdd(&n_partners[i], 1u);
-        atomicAdd(&n_partners[j], 1u);
+    if (b.kind != 0 && hash[j] == h && b.end > a.pos && same_name(U, a, b)) {
+        if (b.sample == a.sample) {
+            mate[i] = (uint32_t)j;
+            mate[j] = (uint32_t)i;
+            atomicAdd(&n_partners[i], 1u);
+            atomicAdd(&n_partners[j], 1u);
+        } else {
+            // an overlapping same-name record of ANOTHER sample is nobody's partner, but in the reference's column it sorts
+            // between same-sample partners and keeps them from being neighbours (depth.d:343-377): marked, see k_max_u32
+            atomicOr(&n_partners[i], kOtherSample);
+            atomicOr(&n_partners[j], kOtherSample);
+        }
     }
 }
 
@@ -642,10 +651,15 @@ __global__ __launch_bounds__(kMateThreads) void k_mates_columns(
     for (uint32_t i = threadIdx.x; i < T; i += kMateThreads) span_out[(size_t)blockIdx.x * T + i] = spn[i];
 }
 
-// the largest n_partners[] of the run: it decides between pairs and partner lists (engine_run.cpp, kFlagMaxPartners)
+// the largest n_partners[] of the run: it decides between pairs and partner lists (engine_run.cpp, kFlagMaxPartners).  The
+// kOtherSample mark of a record survives into the result only where the record has a partner as well: that is the case the
+// engine refuses; a record with such a neighbour and no partner (two samples that share read names) counts as it always did.
 __global__ __launch_bounds__(1024) void k_max_u32(const uint32_t* __restrict__ in, uint64_t n, uint32_t* out) {
     uint32_t m = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 1024) m = in[i] > m ? in[i] : m;
+    for (uint64_t i = (uint64_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 1024) {
+        const uint32_t v = in[i], v1 = (v & ~kOtherSample) ? v : 0u;
+        m = v1 > m ? v1 : m;
+    }
     for (int d = 32; d >= 1; d >>= 1) { uint32_t o = __shfl_down(m, d, 64); m = o > m ? o : m; }
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
