@@ -10,7 +10,9 @@
 //                                 byte is zero, no key has more than kMaxKeyWords words.
 //   namesort_host hi              stdin: one hex-encoded aux area per line ("-": empty).  Per line "ok hi": find_hi over an
 //                                 allocation of exactly that size, so a sanitizer build sees every read behind it.
-// Every mode prints "checked C bad B" last and exits with 1 when B != 0.
+//   namesort_host words ORDER     stdin: one name per line.  Per line the words of its key (decimal), as key_words and key_emit give
+//                                 them for ORDER (1 lexicographic, 2 natural).
+// The first three modes print "checked C bad B" last and exits with 1 when B != 0.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -199,6 +201,19 @@ int main(int argc, char** argv) {
         }
         check_all_pairs(names);
         return finish();
+    }
+    if (mode == "words" && argc == 3) {
+        const uint32_t order = (uint32_t)atoi(argv[2]);
+        std::string line;
+        while (std::getline(std::cin, line)) {
+            const uint32_t words = key_words(u8(line), (uint32_t)line.size(), order);
+            std::vector<uint64_t> key(words + 1);
+            uint32_t got = 0;
+            if (!key_emit(u8(line), (uint32_t)line.size(), order, key.data(), words, &got) || got != words) return 1;
+            for (uint32_t k = 0; k < words; ++k) printf("%s%llu", k ? " " : "", (unsigned long long)key[k]);
+            printf("\n");
+        }
+        return 0;
     }
     if (mode == "hi" && argc == 2) {
         std::string line;
