@@ -81,9 +81,11 @@ extern (C) nothrow @nogc {
     }
     int sbx_flagstat(const(char)* bam_path, int device, sbx_flagstat_counts* out_, char* err, size_t errlen);
     int sbx_format_flagstat(const(sbx_flagstat_counts)* f, int tabular, char* buf, size_t cap, size_t* len);
+    // n_windows: 0 when the records stayed on the device; otherwise the windows the sorted stream was written in (a file larger
+    // than the device, or SBX_SORT_WINDOW_BYTES): sbx_sort_bam then passes the file through the device once per window
     struct sbx_sort_stats {
         ulong n_records_in; ulong n_records_out; ulong inflated_bytes; ulong sorted_stream_bytes; ulong compressed_bytes;
-        uint key_bits; uint n_sort_passes; uint n_batches; uint reserved;
+        uint key_bits; uint n_sort_passes; uint n_batches; uint n_windows;
         double ms_inflate; double ms_index; double ms_keys; double ms_sort; double ms_gather; double ms_deflate; double ms_total_wall;
     }
     int sbx_sort_bam(const(char)* in_path, const(char)* out_path, const(sbx_filter)* filter, int level, int with_index, int device,

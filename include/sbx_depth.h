@@ -195,13 +195,29 @@ int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, si
 /* `sambamba sort` in coordinate order (sambamba/sort.d, default mode): compareCoordinatesAndStrand applied by a stable sort -- ref_id -1
  * last, ascending ref_id, ascending position (signed), forward strand first, ties in file order.  The input needs no sort order and no
  * index.  Records are copied byte for byte; the header text is re-serialised with SO:coordinate (sbx_sort_header_text).  The whole
- * file is sorted on the device: one whose inflated records do not fit next to one batch of the read pass is refused with SBX_ENOMEM.
+ * file is sorted on the device, on one of two paths that write the same file byte for byte:
+ *   resident  the inflated records fit the device next to one batch of the read pass: they stay there (the record store), the keys
+ *             are sorted and the records gathered in order.  n_windows == 0.
+ *   windowed  they do not fit (or SBX_SORT_WINDOW_BYTES=<n> is set: tests and measurements, windows of n bytes rounded up to whole
+ *             pieces of the output stream): only the keys are sorted -- 36 bytes per record during the sort, 12 afterwards -- the
+ *             order becomes one destination per record, and the sorted stream is written window by window, n_windows of them: for
+ *             every window the batches of the read pass whose records have a byte in it are inflated and described again (K1 + K2)
+ *             and K9d puts each record at its place.  No temporary file, no merge; -m and --tmpdir of sbx-sort stay without
+ *             effect.  A file already in order is inflated about twice in all, a shuffled one once per window and once more.  If
+ *             the input is not the same in every pass -- the record bytes a window receives do not add up, or a record's length is
+ *             not the one its key was taken with -- the call fails with SBX_EIO ("the input changed while it was being sorted") and
+ *             the output file is removed.  SBX_ENOMEM only when not even the keys, one minimal read batch and a window of one piece
+ *             fit.
+ * sbx_sort_bam_by_name, sbx_markdup, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins have the resident path only and
+ * refuse what does not fit with SBX_ENOMEM (a name order needs the names next to the keys: not built).
  * Milliseconds are device time of the kernels (inflate = K1, index = K2, keys = K9a + the copy into the record store, sort = K9b,
- * gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index. */
+ * gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index.
+ * On the windowed path inflate and index are those of the key pass alone (SBX_TIMING=1 reports the replays in a `[sbx] sort-windows:`
+ * line), keys = K9a alone, gather = output offsets + K9d. */
 typedef struct {
     uint64_t n_records_in, n_records_out;      /* out < in only with a filter */
     uint64_t inflated_bytes, sorted_stream_bytes, compressed_bytes;
-    uint32_t key_bits, n_sort_passes, n_batches, reserved;    /* key_bits: width of the stretch of key bits in which records differ */
+    uint32_t key_bits, n_sort_passes, n_batches, n_windows;   /* key_bits: width of the stretch of key bits in which records differ; n_windows: 0 on the resident path */
     double ms_inflate, ms_index, ms_keys, ms_sort, ms_gather, ms_deflate, ms_total_wall;
 } sbx_sort_stats;
 /* filter == NULL: every record (not depth's default filter); otherwise only the records the filter admits are written.

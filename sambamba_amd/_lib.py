@@ -95,7 +95,7 @@ class Flagstat(C.Structure):
 
 class SortStats(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("n_records_in", "n_records_out", "inflated_bytes", "sorted_stream_bytes", "compressed_bytes")] +
-                [(k, C.c_uint32) for k in ("key_bits", "n_sort_passes", "n_batches", "reserved")] +
+                [(k, C.c_uint32) for k in ("key_bits", "n_sort_passes", "n_batches", "n_windows")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_keys", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
 
 class MarkdupStats(C.Structure):

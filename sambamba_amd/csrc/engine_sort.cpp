@@ -9,7 +9,15 @@
 //
 // The scaffold of the entry point, the plan of the store, the copy into it and the output tail are engine_store.hpp, shared with
 // sbx_markdup, sbx_merge_bam and sbx_view_bam.
-// What does not fit the device next to one batch of the read pass is refused with SBX_ENOMEM (an out-of-core merge is not built).
+//
+// A file whose records do not fit the device next to one batch of the read pass takes the WINDOWED path (sort_file_windowed; also
+// forced by SBX_SORT_WINDOW_BYTES): no record store.  The key pass runs K9a alone and saves its batches (for_each_record_batch with
+// `saved`); K9b sorts the keys; the offsets of the sorted stream become one destination per record (K9d-1) and one span of
+// destinations per batch (K9d-2); then, for every window of whole pieces of the stream that fits the device, the batches whose span
+// meets the window are run again (run_record_batch: the same K1 + K2, the same U and descriptors) and K9d-3 scatters their records
+// into the window, which goes through the same encoder to the file.  No temporary file and no merge; the file is the resident
+// path's byte for byte.  The name orders, sbx_markdup, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins stay resident
+// and refuse with SBX_ENOMEM what does not fit.
 //
 // sbx_sort_bam_by_name (`sambamba sort -n / -N`, with or without -M) is the same call with another order: next to K9a, K14a
 // (namesort.hip) builds the key of every kept record's name in a key store of 64-bit words, and the order is an LSD sort over those
@@ -114,6 +122,228 @@ struct NameKeys {
     void release() { store.release(); off.release(); mate.release(); words.release(); word_base.release(); }
 };
 
+// the `[sbx] sort:` line of SBX_TIMING; by: what a name order puts in front ("" otherwise); the four wall-clock phases in ms
+void print_sort_line(const sbx_sort_stats& st, const char* by, double open_ms, double read_ms, double sort_ms, double write_ms) {
+    fprintf(stderr, "[sbx] sort: %sn_records_in=%llu n_records_out=%llu inflated_bytes=%llu sorted_stream_bytes=%llu compressed_bytes=%llu "
+                    "key_bits=%u n_sort_passes=%u n_batches=%u ms_inflate=%.2f ms_index=%.2f ms_keys=%.2f ms_sort=%.2f ms_gather=%.2f "
+                    "ms_deflate=%.2f ms_total_wall=%.1f (open %.1f, read pass %.1f, sort %.1f, write %.1f)\n", by,
+            (unsigned long long)st.n_records_in, (unsigned long long)st.n_records_out, (unsigned long long)st.inflated_bytes,
+            (unsigned long long)st.sorted_stream_bytes, (unsigned long long)st.compressed_bytes, st.key_bits, st.n_sort_passes, st.n_batches,
+            st.ms_inflate, st.ms_index, st.ms_keys, st.ms_sort, st.ms_gather, st.ms_deflate, st.ms_total_wall, open_ms, read_ms, sort_ms, write_ms);
+}
+
+// SBX_SORT_WINDOW_BYTES (tests, measurements): forces the windowed path with windows of this many bytes, rounded up to whole pieces.
+// 0: unset (or not a positive decimal number).
+uint64_t window_bytes_hook() {
+    const char* e = getenv("SBX_SORT_WINDOW_BYTES");
+    if (!e || *e < '0' || *e > '9') return 0;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    return *end ? 0 : (uint64_t)v;
+}
+
+// Inflated bytes per batch of the windowed sort.  The batch buffers (~5 x this) stay allocated from the key pass to the last window
+// and are taken from what the windows could have: a batch is kept small against a window, and a short batch has a narrow span of
+// destinations, which is what lets a window skip it.  K1 + K2 run at ~300 GB/s of inflated bytes (README), so 2 GiB is ~7 ms of
+// kernels per batch -- far above the cost of launching them.
+constexpr uint64_t kWindowedBatchBytes = 2ull << 30;
+constexpr uint64_t kWindowedPerRecord = 36;     // bytes per record while the keys are sorted: key, key2, len, val, val2, dest / out_off
+
+// The coordinate sort of a file whose records do not stay on the device (or SBX_SORT_WINDOW_BYTES): the keys of the whole file are
+// sorted as in sort_file, the order becomes one destination per record (K9d-1), and the sorted stream is written window by window:
+// the batches of the key pass whose destinations meet the window (K9d-2) are run again and K9d-3 puts their records in place.  The
+// stream is cut into BGZF blocks exactly as write_permuted_bam cuts it, so the file is the resident path's byte for byte.
+void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<uint8_t>& header, bool use_filter, int level, uint64_t hook,
+                        double w0, sbx_sort_stats* stats) {
+    const uint64_t hlen = header.size();
+    const int32_t n_ref = (int32_t)c->hdr.refs.size();
+    const uint64_t u_total = c->blocks.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
+    const uint64_t piece_blocks = bgzf_piece_blocks(), piece_bytes = piece_blocks * (uint64_t)kBgzfPayload;
+    // the encoder's buffers, as plan_store_bytes reserves them, and the smallest window: one piece, or the whole stream when it is shorter
+    const uint64_t stream_est = u_total - u_first + hlen;
+    const uint64_t cap_bytes = std::min<uint64_t>(piece_bytes, stream_est + kBgzfPayload);
+    const uint64_t out_reserve = cap_bytes * 3 + (8ull << 20);
+    const uint64_t est_records = (u_total - u_first) / 160 + 4096;
+    auto refuse = [&](uint64_t need, uint64_t free_b, const char* what) {
+        throw Error(SBX_ENOMEM, std::string("the file does not fit the device: sorting it in windows needs ") + std::to_string(need) +
+                                    " bytes of device memory (" + what + "), " + std::to_string(free_b) + " are free");
+    };
+    {
+        size_t free_b = 0, total_b = 0;
+        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t need = est_records * kWindowedPerRecord + 5ull * (64ull << 20) + out_reserve + cap_bytes;
+        if (need > free_b) refuse(need, free_b, "the keys of its records, one read batch, the encoder and a window of one piece");
+    }
+    const uint64_t batch_u = std::min<uint64_t>(index_batch_bytes(est_records * kWindowedPerRecord + out_reserve + cap_bytes), kWindowedBatchBytes);
+    hipStream_t s = c->stream.get();
+    DevBuf<uint64_t> d_key;
+    DevBuf<uint32_t> d_len, d_group_count, d_rank;
+    DevBuf<uint64_t> d_group_base;
+    DevBuf<unsigned long long> d_acc(kSortAccWords);
+    unsigned long long acc[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
+    SBX_HIP(hipMemcpyAsync(d_acc.p, acc, sizeof acc, hipMemcpyHostToDevice, s));
+    SBX_HIP(hipStreamSynchronize(s));
+    const double w1 = wall_now();
+
+    // ---- the key pass: K9a, nothing copied; the batches are saved ----
+    sbx_sort_stats st{};
+    EventTimer t_k;
+    std::vector<SavedBatch> saved;
+    uint64_t n_in = 0, n_kept = 0;
+    uint32_t n_batches = 0;
+    for_each_record_batch(c.get(), batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        const size_t want = (size_t)(n_kept + nrec + 2);
+        grow_keeping(d_key, (size_t)n_kept, want, s);
+        grow_keeping(d_len, (size_t)n_kept, want, s);
+        if (use_filter) { d_group_count.ensure(sort_keys_groups(nrec) + 4); d_group_base.ensure(sort_keys_groups(nrec) + 4); }
+        SortKeysArgs a{};
+        a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
+        a.n_ref = n_ref; a.key_n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
+        a.out_base = n_kept;
+        a.key = d_key.p; a.off = nullptr; a.len = d_len.p; a.acc = d_acc.p;
+        t_k.start(s);
+        launch_sort_keys(a, d_group_count.p, d_group_base.p, s);
+        t_k.stop(s);
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_keys += t_k.ms();
+        n_in += nrec;
+        saved.back().first_kept = n_kept;
+        saved.back().n_kept = acc[kSortAccKept] - n_kept;
+        n_kept = acc[kSortAccKept];
+        return !acc[kSortAccBad];
+    }, &saved);
+    if (acc[kSortAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSortAccBad]));
+    if (!use_filter && n_kept != n_in)
+        throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(n_in) + " records received a key");
+    if (n_kept > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
+    const uint64_t n = n_kept;
+    const double w2 = wall_now();
+
+    // ---- K9b, the offsets, K9d-1 and K9d-2 ----
+    double ms_dest = 0;
+    DevBuf<uint64_t> d_dest((size_t)n + 2);
+    std::vector<uint64_t> span_lo(saved.size(), ~0ull), span_hi(saved.size(), 0);
+    uint64_t total = hlen;
+    {
+        ResidentOrder order;
+        sort_resident(d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
+        st.ms_sort = order.ms_sort;
+        st.key_bits = order.key_bits; st.n_sort_passes = order.n_passes;
+        const OutputPlan plan = plan_output(d_len.p, order.perm, n, hlen, order.key2.p, s, &st.ms_gather);
+        total = plan.total;
+        if (total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the sorted records do not add up");
+        std::vector<uint64_t> first(saved.size() + 1, n);
+        for (size_t b = 0; b < saved.size(); ++b) first[b] = saved[b].first_kept;
+        DevBuf<uint64_t> d_first(first.size()), d_lo(saved.size() + 1), d_hi(saved.size() + 1);
+        SBX_HIP(hipMemcpyAsync(d_first.p, first.data(), first.size() * 8, hipMemcpyHostToDevice, s));
+        EventTimer t;
+        t.start(s);
+        launch_window_dest(order.perm, order.key2.p, n, d_dest.p, s);
+        launch_batch_spans(d_dest.p, d_len.p, d_first.p, (uint32_t)saved.size(), d_lo.p, d_hi.p, s);
+        t.stop(s);
+        if (!saved.empty()) {
+            SBX_HIP(hipMemcpyAsync(span_lo.data(), d_lo.p, saved.size() * 8, hipMemcpyDeviceToHost, s));
+            SBX_HIP(hipMemcpyAsync(span_hi.data(), d_hi.p, saved.size() * 8, hipMemcpyDeviceToHost, s));
+        }
+        SBX_HIP(hipStreamSynchronize(s));
+        ms_dest = t.ms();
+        // keys, key2, val / val2 and the offsets go before the first window comes (order and the small tables: end of this scope)
+        d_key.release();
+    }
+
+    // ---- the window: what is free next to the batch buffers (they stay) less the encoder's ----
+    const uint32_t cap_blocks = (uint32_t)std::min<uint64_t>(piece_blocks, std::max<uint64_t>(1, (total + kBgzfPayload - 1) / kBgzfPayload));
+    uint64_t window_bytes = hook;
+    if (!window_bytes) {
+        size_t free_b = 0, total_b = 0;
+        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t reserve = out_reserve + (64ull << 20);
+        const uint64_t avail = free_b > reserve ? free_b - reserve : 0;
+        const uint64_t smallest = std::min<uint64_t>(piece_bytes, total);
+        if (avail < smallest) refuse(smallest + reserve, free_b, "one window of one piece and the encoder, next to the read batch and 12 bytes per record");
+        window_bytes = std::max<uint64_t>(avail / piece_bytes, 1) * piece_bytes;
+    }
+    const std::vector<sortc::Window> windows = sortc::plan_windows(total, piece_bytes, window_bytes);
+    const uint64_t span = sortc::window_span(piece_bytes, window_bytes);
+    DevBuf<uint8_t> d_win((size_t)std::min<uint64_t>(span, total) + 64);
+    DevBuf<unsigned long long> d_wacc(kWindowAccWords);
+    BgzfPieceCompressor comp(cap_blocks, level, true);
+    BgzfPieceTimes bt_times;
+    const double w3 = wall_now();
+
+    FILE* f = fopen(out_file.c_str(), "wb");
+    if (!f) throw Error(SBX_EIO, "cannot write " + out_file.path);
+    out_file.arm();
+    bool ok = true;
+    uint64_t n_batch_runs = 0, n_batches_skipped = 0;
+    double ms_scatter = 0, ms_inflate_replay = 0, ms_index_replay = 0;
+    EventTimer t_s;
+    try {
+        for (const sortc::Window& w : windows) {
+            SBX_HIP(hipMemsetAsync(d_wacc.p, 0, kWindowAccWords * sizeof(unsigned long long), s));
+            if (w.w0 < hlen) SBX_HIP(hipMemcpyAsync(d_win.p, header.data() + w.w0, std::min<uint64_t>(hlen, w.w1) - w.w0, hipMemcpyHostToDevice, s));
+            for (size_t b = 0; b < saved.size(); ++b) {
+                const SavedBatch& sb = saved[b];
+                if (!sortc::span_meets_window(span_lo[b], span_hi[b], w.w0, w.w1)) { ++n_batches_skipped; continue; }
+                ++n_batch_runs;
+                run_record_batch(c.get(), sb, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+                    if (nrec != sb.nrec || base != sb.base || next != sb.next)
+                        throw Error(SBX_EIO, "the input changed while it was being sorted (a batch of the read pass holds other records than before)");
+                    if (use_filter) {
+                        d_group_count.ensure(sort_keys_groups(nrec) + 4);
+                        d_group_base.ensure(sort_keys_groups(nrec) + 4);
+                        d_rank.ensure((size_t)nrec + 2);
+                    }
+                    WindowScatterArgs a{};
+                    a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base; a.use_filter = use_filter ? 1u : 0u;
+                    a.first_kept = sb.first_kept; a.n_kept = sb.n_kept;
+                    a.dest = d_dest.p; a.len = d_len.p; a.w0 = w.w0; a.w1 = w.w1; a.window = d_win.p; a.acc = d_wacc.p;
+                    t_s.start(s);
+                    launch_window_scatter(a, d_group_count.p, d_group_base.p, d_rank.p, s);
+                    t_s.stop(s);
+                    // (the next batch's K1 / K2 overwrite U and the descriptors: K9d-3 ends first)
+                    SBX_HIP(hipStreamSynchronize(s));
+                    ms_scatter += t_s.ms();
+                    ms_inflate_replay += c->stats.ms_inflate;
+                    ms_index_replay += c->stats.ms_index;
+                    return true;
+                });
+            }
+            unsigned long long wacc[kWindowAccWords] = {0, 0};
+            SBX_HIP(hipMemcpyAsync(wacc, d_wacc.p, sizeof wacc, hipMemcpyDeviceToHost, s));
+            SBX_HIP(hipStreamSynchronize(s));
+            const std::string why = sortc::window_refusal(w.w0, w.w1, hlen, wacc[kWindowAccBytes], wacc[kWindowAccMismatch]);
+            if (!why.empty()) throw Error(SBX_EIO, why);
+            comp.run((size_t)(w.w1 - w.w0), false, &bt_times,
+                     [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
+                         SBX_HIP(hipMemcpyAsync(d_in, d_win.p + done, bytes, hipMemcpyDeviceToDevice, ps));
+                     },
+                     [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
+        }
+    } catch (...) { fclose(f); throw; }
+    ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
+    if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out_file.path);
+    out_file.disarm();
+    const double w4 = wall_now();
+
+    st.ms_gather += ms_dest + ms_scatter;
+    st.n_records_in = n_in; st.n_records_out = n;
+    st.inflated_bytes = u_total; st.sorted_stream_bytes = total; st.compressed_bytes = bt_times.out_bytes + 28;
+    st.n_batches = n_batches; st.n_windows = (uint32_t)windows.size();
+    st.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+    st.ms_total_wall = (w4 - w0) * 1e3;
+    if (getenv("SBX_TIMING")) {
+        fprintf(stderr, "[sbx] output: stream_bytes=%llu compressed_bytes=%llu n_pieces=%u piece_blocks=%llu\n", (unsigned long long)total,
+                (unsigned long long)st.compressed_bytes, bt_times.n_pieces, (unsigned long long)piece_blocks);
+        fprintf(stderr, "[sbx] sort-windows: n_windows=%u window_bytes=%llu n_batch_runs=%llu n_batches_skipped=%llu ms_dest=%.2f ms_scatter=%.2f "
+                        "ms_inflate_replay=%.2f ms_index_replay=%.2f\n", st.n_windows, (unsigned long long)span, (unsigned long long)n_batch_runs,
+                (unsigned long long)n_batches_skipped, ms_dest, ms_scatter, ms_inflate_replay, ms_index_replay);
+        print_sort_line(st, "", (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
+    }
+    if (stats) *stats = st;
+}
+
 // order: 0 coordinate (sbx_sort_bam), nsc::kOrderLex, nsc::kOrderNatural (sbx_sort_bam_by_name)
 void sort_file(const char* in_path, const char* out_path, const sbx_filter* filter, int level, uint32_t name_order, bool match_mates,
                int device, sbx_sort_stats* stats) {
@@ -133,7 +363,22 @@ void sort_file(const char* in_path, const char* out_path, const sbx_filter* filt
 
     // per record: key, offset, length and K9b's second key and two values; a name order adds the key's offset, the -M word and
     // -- an estimate, the key store grows with the batches -- four key words
-    const StorePlan plan = plan_record_store(c.get(), hlen, name_order ? 48 + 16 + 32 : 48, "sorting");
+    // The coordinate order goes through windows when the records do not fit (or the hook says so); the name orders stay resident.
+    const uint64_t hook = name_order ? 0 : window_bytes_hook();
+    StorePlan plan{};
+    bool windowed = hook != 0;
+    if (!windowed) {
+        try {
+            plan = plan_record_store(c.get(), hlen, name_order ? 48 + 16 + 32 : 48, "sorting");
+        } catch (const Error& e) {
+            if (name_order || e.code != SBX_ENOMEM) throw;
+            windowed = true;
+        }
+    }
+    if (windowed) {
+        sort_file_windowed(c, out_file, header, use_filter, level, hook, w0, stats);
+        return;
+    }
     const uint64_t u_total = plan.u_total, u_first = plan.u_first, store_bytes = plan.store_bytes, batch_u = plan.batch_u;
     hipStream_t s = c->stream.get();
     DevBuf<uint8_t> d_store((size_t)store_bytes + 64);
@@ -228,13 +473,7 @@ void sort_file(const char* in_path, const char* out_path, const sbx_filter* filt
         if (name_order)
             snprintf(by, sizeof by, "order=%s%s words_sorted=%u ", name_order == nsc::kOrderNatural ? "natural" : "queryname",
                      match_mates ? "+mates" : "", names.words_sorted);
-        fprintf(stderr, "[sbx] sort: %sn_records_in=%llu n_records_out=%llu inflated_bytes=%llu sorted_stream_bytes=%llu compressed_bytes=%llu "
-                        "key_bits=%u n_sort_passes=%u n_batches=%u ms_inflate=%.2f ms_index=%.2f ms_keys=%.2f ms_sort=%.2f ms_gather=%.2f "
-                        "ms_deflate=%.2f ms_total_wall=%.1f (open %.1f, read pass %.1f, sort %.1f, write %.1f)\n", by,
-                (unsigned long long)st.n_records_in, (unsigned long long)st.n_records_out, (unsigned long long)st.inflated_bytes,
-                (unsigned long long)st.sorted_stream_bytes, (unsigned long long)st.compressed_bytes, st.key_bits, st.n_sort_passes, st.n_batches,
-                st.ms_inflate, st.ms_index, st.ms_keys, st.ms_sort, st.ms_gather, st.ms_deflate, st.ms_total_wall, (w1 - w0) * 1e3,
-                (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
+        print_sort_line(st, by, (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
     }
     if (stats) *stats = st;
 }

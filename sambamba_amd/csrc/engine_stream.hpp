@@ -1,7 +1,8 @@
 // engine_stream.hpp -- the two streaming loops engine_writer.cpp and engine_sort.cpp share: BGZF compression of a byte stream piece by
 // piece on the device (bgzf_compress_pieces: the source of a piece is a callback -- a copy from host memory for sbx_bgzf_compress /
 // sbx_write_bam, a gather on the device for sbx_sort_bam) and the index-mode pass over the records of a file in batches
-// (for_each_record_batch: sbx_build_index, sbx_flagstat, sbx_sort_bam).
+// (for_each_record_batch: sbx_build_index, sbx_flagstat, sbx_sort_bam; run_record_batch: one saved batch of such a pass once more,
+// for the windowed sort).
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -138,8 +139,30 @@ inline uint64_t index_batch_bytes(uint64_t reserved = 0) {
 // batch.  consume(nrec, base, next) is called once per batch: records [0, nrec) of c->d_desc / c->d_rec_ref are the batch's, their
 // rec_off count from U[0] = inflated offset `base` of the file, and `next` is the inflated offset behind the batch's last record.
 // It returns false to stop the pass (then so does this function); *n_batches receives the number of batches handed over.
+//
+// A batch is decided by (cur, bu) alone, so a pass can be repeated batch by batch: with `saved`, every batch handed over is also
+// appended to it -- its run, what consume() received, and (cur, bu) -- and run_record_batch() below runs exactly that batch again.
+// first_kept / n_kept are the caller's: the ordinal of the batch's first record that takes part and the number of those records.
+struct SavedBatch {
+    FileRun run;
+    uint64_t cur, bu;               // the batch started at inflated offset cur with a batch size of bu bytes
+    uint64_t nrec, base, next;      // what consume() received
+    uint64_t first_kept = 0, n_kept = 0;
+};
+struct RecordBatch { uint64_t nrec, base, next; };
+// K1 + K2 over one run of an index-mode context: the shared body of the pass and of its replay
+inline RecordBatch describe_record_run(sbx_ctx* c, const FileRun& run) {
+    const std::vector<FileRun> runs{run};
+    run_impl(c, {}, false, &runs);
+    RecordBatch b;
+    b.nrec = c->primary_records;
+    b.base = c->blocks.out_off[run.blk0];                // work-list offsets count from the batch's first block
+    // an open-ended run stops in front of the record that straddles its last block boundary
+    b.next = run.open_end && c->index_straddler != kOffUnknown ? b.base + c->index_straddler : run.ue;
+    return b;
+}
 template <class Consume>
-bool for_each_record_batch(sbx_ctx* c, uint64_t batch_u, uint32_t* n_batches, Consume&& consume) {
+bool for_each_record_batch(sbx_ctx* c, uint64_t batch_u, uint32_t* n_batches, Consume&& consume, std::vector<SavedBatch>* saved = nullptr) {
     const BlockTable& bt = c->blocks;
     const size_t nbk = bt.size();
     const uint64_t total = bt.out_off.back(), first = c->hdr.first_record_off;
@@ -151,20 +174,26 @@ bool for_each_record_batch(sbx_ctx* c, uint64_t batch_u, uint32_t* n_batches, Co
         b1 = std::min<uint32_t>(std::max(b1, b0 + 1), (uint32_t)nbk);
         if (bt.out_off[b1] >= total) b1 = (uint32_t)nbk;          // (whatever follows holds no bytes: EOF blocks)
         const bool last = b1 == nbk;
-        const std::vector<FileRun> runs{FileRun{b0, b1, cur, last ? total : bt.out_off[b1], !last}};
-        run_impl(c, {}, false, &runs);
-        const uint64_t nrec = c->primary_records;
-        const uint64_t base = bt.out_off[b0];            // work-list offsets count from the batch's first block
-        const uint64_t next = last ? total : c->index_straddler != kOffUnknown ? base + c->index_straddler : bt.out_off[b1];
-        if (!last && next == cur) {                      // not one whole record in the batch: a longer batch
+        const FileRun run{b0, b1, cur, last ? total : bt.out_off[b1], !last};
+        const RecordBatch b = describe_record_run(c, run);
+        if (!last && b.next == cur) {                    // not one whole record in the batch: a longer batch
             bu *= 2;
             continue;
         }
         ++*n_batches;
-        if (!consume(nrec, base, next)) return false;
-        cur = next;
+        if (saved) saved->push_back(SavedBatch{run, cur, bu, b.nrec, b.base, b.next});
+        if (!consume(b.nrec, b.base, b.next)) return false;
+        cur = b.next;
     }
     return true;
+}
+// One batch of an earlier pass over the same context once more: the same run, hence the same U and the same descriptors at the same
+// places.  consume(nrec, base, next) as above; what it returns is returned.  Whether the batch came out as it did the first time
+// (b.nrec, b.base, b.next against the saved ones) is the consumer's to judge.
+template <class Consume>
+bool run_record_batch(sbx_ctx* c, const SavedBatch& saved, Consume&& consume) {
+    const RecordBatch b = describe_record_run(c, saved.run);
+    return consume(b.nrec, b.base, b.next);
 }
 
 }  // namespace sbx

@@ -19,7 +19,7 @@ struct SortKeysArgs {
     int64_t store_delta;            // a record's offset in the record store = rec_off + store_delta
     uint64_t out_base;              // records kept of the batches before
     uint64_t* key;                  // [out_base + ...) of the kept records, in file order
-    uint64_t* off;
+    uint64_t* off;                  // (null: no record store, the windowed sort)
     uint32_t* len;
     unsigned long long* acc;        // [kSortAccWords]
 };
@@ -42,5 +42,31 @@ void launch_piece_bounds(const uint64_t* d_out_off, uint64_t n, uint64_t piece_b
 // K9c: the bytes of sorted records [r0, r1) that lie in [p0, p1) of the sorted stream go to d_dst[0, p1 - p0)
 void launch_gather_records(const uint8_t* d_store, const uint64_t* d_off, const uint32_t* d_perm, const uint64_t* d_out_off, uint64_t r0,
                            uint64_t r1, uint64_t p0, uint64_t p1, uint8_t* d_dst, hipStream_t stream);
+
+// ---- K9d: the windowed sort (no record store; the file passes through the read pass once per window of the output stream) ----
+// K9d-1: d_dest[d_perm[r]] = d_out_off[r], r in [0, n): where in the sorted stream the kept record with file-order ordinal i starts
+void launch_window_dest(const uint32_t* d_perm, const uint64_t* d_out_off, uint64_t n, uint64_t* d_dest, hipStream_t stream);
+// K9d-2: batch b holds the kept records [d_first[b], d_first[b + 1]); d_lo[b] = min dest, d_hi[b] = max (dest + len) over them
+// (~0 and 0 for a batch without records)
+void launch_batch_spans(const uint64_t* d_dest, const uint32_t* d_len, const uint64_t* d_first, uint32_t n_batches, uint64_t* d_lo,
+                        uint64_t* d_hi, hipStream_t stream);
+// words of K9d-3's accumulator: bytes written into the window; records that are not what the key pass saw
+enum WindowAcc : uint32_t { kWindowAccBytes = 0, kWindowAccMismatch = 1, kWindowAccWords = 2 };
+struct WindowScatterArgs {
+    const uint8_t* U;               // inflated bytes of the replayed batch
+    const RecDesc* desc;            // its records
+    uint64_t n;                     // records of the batch
+    uint64_t u_end;                 // no record of the batch ends behind this offset of U
+    uint32_t use_filter;            // != 0: only records with RecDesc::pad == kFilterPass take part, numbered as K9a numbered them
+    uint64_t first_kept, n_kept;    // ordinals the key pass gave the batch's kept records: [first_kept, first_kept + n_kept)
+    const uint64_t* dest;           // [ordinal] offset in the sorted stream (K9d-1)
+    const uint32_t* len;            // [ordinal] block_size + 4 as the key pass read it
+    uint64_t w0, w1;                // the window of the sorted stream
+    uint8_t* window;                // [w1 - w0]
+    unsigned long long* acc;        // [kWindowAccWords]
+};
+// K9d-3.  With a filter: d_group_count / d_group_base as for launch_sort_keys, d_rank has n + 2 words (a kept record's rank among
+// the kept records of the batch); without, all three may be null.
+void launch_window_scatter(const WindowScatterArgs& a, uint32_t* d_group_count, uint64_t* d_group_base, uint32_t* d_rank, hipStream_t stream);
 
 }  // namespace sbx

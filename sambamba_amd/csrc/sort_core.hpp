@@ -1,7 +1,8 @@
 // sort_core.hpp -- what `sambamba sort` (coordinate order) needs besides the kernels: the 64-bit sort key of a record, the digits a
-// radix sort has to look at, the arithmetic of the pieces the output stream is produced in, and the header text of the output.  The
-// key and piece functions are `__host__ __device__` (K9a, k_piece_bounds and K9c of sort.hip run the very statements the CPU test
-// checks: tests/native/sort_host.cpp); the header text is host code.
+// radix sort has to look at, the arithmetic of the pieces the output stream is produced in and of the windows a file larger than the
+// device is written in, and the header text of the output.  The key, piece and window functions are `__host__ __device__` (K9a,
+// k_piece_bounds, K9c and K9d of sort.hip run the very statements the CPU tests check: tests/native/sort_host.cpp and
+// tests/native/sortwin_host.cpp); the header text, plan_windows and window_refusal are host code.
 //
 // Order (compareCoordinatesAndStrand, BioD bio/std/hts/bam/read.d:1632-1642, applied by a stable merge sort): ref_id -1 last, ascending
 // ref_id, ascending position as a signed number, forward strand in front of reverse strand, ties in file order.  Records with ref_id -1
@@ -96,6 +97,31 @@ SBX_SORT_HD bool clip_to_piece(uint64_t o, uint64_t e, uint64_t p0, uint64_t p1,
     return true;
 }
 
+// ---- the windows of the output stream (the windowed sort: engine_sort.cpp; K9d, sort.hip) ----
+// A file whose records do not fit the device is written window by window: a window is a run of whole pieces [w0, w1) of the stream
+// that fits the device, filled by passing the file through the read pass again and putting every record that has bytes in it at
+// dest - w0 (the clip of a record to a window is clip_to_piece).  window_bytes is rounded UP to whole pieces, at least one; the last
+// window ends at total; no window is empty.
+SBX_SORT_HD uint64_t window_span(uint64_t piece_bytes, uint64_t window_bytes) {
+    const uint64_t pieces = window_bytes ? (window_bytes - 1) / piece_bytes + 1 : 1;
+    return pieces * piece_bytes;
+}
+SBX_SORT_HD uint64_t window_count(uint64_t total, uint64_t piece_bytes, uint64_t window_bytes) {
+    const uint64_t span = window_span(piece_bytes, window_bytes);
+    return total ? (total - 1) / span + 1 : 0;
+}
+// window k of window_count(): [*w0, *w1)
+SBX_SORT_HD void window_at(uint64_t k, uint64_t total, uint64_t piece_bytes, uint64_t window_bytes, uint64_t* w0, uint64_t* w1) {
+    const uint64_t span = window_span(piece_bytes, window_bytes);
+    *w0 = k * span;
+    *w1 = total - *w0 > span ? *w0 + span : total;
+}
+// Does a batch of the read pass whose records go to [lo, hi) of the stream (K9d-2: the minimum of dest, the maximum of dest + len;
+// a batch without records has lo >= hi) hold a byte of the window [w0, w1)?
+SBX_SORT_HD bool span_meets_window(uint64_t lo, uint64_t hi, uint64_t w0, uint64_t w1) {
+    return lo < hi && lo < w1 && hi > w0;
+}
+
 }  // namespace sortc
 }  // namespace sbx
 
@@ -106,6 +132,26 @@ SBX_SORT_HD bool clip_to_piece(uint64_t o, uint64_t e, uint64_t p0, uint64_t p1,
 
 namespace sbx {
 namespace sortc {
+
+// the windows [w0, w1) of a stream of total_stream_bytes, in order (window_count / window_at)
+struct Window { uint64_t w0, w1; };
+inline std::vector<Window> plan_windows(uint64_t total_stream_bytes, uint64_t piece_bytes, uint64_t window_bytes) {
+    std::vector<Window> w((size_t)window_count(total_stream_bytes, piece_bytes, window_bytes));
+    for (size_t k = 0; k < w.size(); ++k) window_at(k, total_stream_bytes, piece_bytes, window_bytes, &w[k].w0, &w[k].w1);
+    return w;
+}
+
+// The two checks on a window before it is compressed (K9d-3's accumulator): the record bytes written must be the window less the
+// header bytes that lie in it (header: [0, hlen) of the stream), and no record may have had another length than the key pass saw.
+// Empty: the window is whole; otherwise the text of the SBX_EIO refusal.
+inline std::string window_refusal(uint64_t w0, uint64_t w1, uint64_t hlen, uint64_t bytes_written, uint64_t mismatches) {
+    PieceClip h;
+    const uint64_t header_bytes = clip_to_piece(0, hlen, w0, w1, &h) ? h.len : 0;
+    if (!mismatches && bytes_written == w1 - w0 - header_bytes) return std::string();
+    return "the input changed while it was being sorted (bytes [" + std::to_string(w0) + ", " + std::to_string(w1) + ") of the sorted stream: " +
+           std::to_string(bytes_written) + " record bytes arrived where " + std::to_string(w1 - w0 - header_bytes) + " belong, " +
+           std::to_string(mismatches) + " record(s) are not the ones the keys were taken from)";
+}
 
 // A SAM header text as SamHeader's constructor reads it (BioD bio/std/hts/sam/header.d:473-545) and SamHeader.toSam prints it back
 // (header.d:626-656): the version and sorting order of an @HD line that is the first line of the input (1.3 and none otherwise);
