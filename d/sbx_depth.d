@@ -146,6 +146,16 @@ extern (C) nothrow @nogc {
         int valid_only; int reserved;
     }
     int sbx_view_run(const(sbx_view_request)* request, ulong* count, sbx_view_stats* stats, char* err, size_t errlen);
+    // the same call reading only the blocks the .bai names for the regions; OFF is sbx_view_run, AUTO falls back to it without a .bai
+    struct sbx_view_index_stats {
+        ulong blocks_in_file; ulong blocks_read; ulong runs; ulong compressed_bytes_read; ulong inflated_bytes_read;
+        double ms_plan;
+    }
+    enum SBX_VIEW_INDEX_OFF = 0;
+    enum SBX_VIEW_INDEX_REQUIRED = 1;
+    enum SBX_VIEW_INDEX_AUTO = 2;
+    int sbx_view_run_indexed(const(sbx_view_request)* request, int index_mode, ulong* count, sbx_view_stats* stats,
+                             sbx_view_index_stats* index, char* err, size_t errlen);
     // which records are valid (alignment.d's isValid), and why not: class k of the report is bit k of a record's mask
     enum SBX_VALIDATE_CLASSES = 10;
     struct sbx_validate_report {

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -324,7 +324,7 @@ int sbx_merge_header_text(const char* const* texts, const size_t* lens, int n, c
  * them and every record that overlaps any of them is output once, in file order.  Both at once are SBX_EINVAL.
  * Deliberate divergences: no .bai is needed and the input need not be sorted -- the result is defined by the predicate over all
  * records in file order, which is what the reference yields for a sorted, indexed file -- and -L uses the same predicate whatever
- * the header's SO says.  The whole file is read even for a small region.
+ * the header's SO says.  These calls read the whole file even for a small region; sbx_view_run_indexed reads what the .bai names.
  * Milliseconds are device time (inflate = K1, index = K2, select = K12a [+ the copy into the record store and the scans of its
  * counts for BAM output], emit = K12b, sort = K9b over the region indices + the composition, gather = output offsets + K9c,
  * deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index. */
@@ -397,6 +397,34 @@ typedef struct {
     int32_t valid_only, reserved;
 } sbx_view_request;
 int sbx_view_run(const sbx_view_request* request, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen);
+/* sbx_view_run that reads only the blocks the .bai names for the regions of the request.  The calls above keep reading the whole
+ * file: they need no .bai and promise n_records_in = the records of the file; this one is the way to a cost that follows the region.
+ * index_mode: SBX_VIEW_INDEX_OFF is sbx_view_run; SBX_VIEW_INDEX_REQUIRED fails with SBX_ENOINDEX when the request has a region or a
+ * BED file and the input has no .bai; SBX_VIEW_INDEX_AUTO then reads the whole file.  Without region and BED file there is nothing to
+ * restrict: every mode is OFF, and blocks_read == blocks_in_file.
+ * On the indexed path the merged BAI chunks of all regions of the call (getGroupChunks, randomaccessmanager.d:247-294; for `*` the
+ * stretch from the first record without a reference to the end of the stream) are joined where they share a block or lie at most
+ * one block apart, and the union is read once, in batches of SBX_INDEX_BATCH_BYTES as for the other passes; the selection over the
+ * described records is the one of sbx_view_run, so counts, BAM and SAM bytes are those of the whole-file pass.  stats.n_records_in
+ * is then the number of records described and stats.inflated_bytes the bytes inflated (a block at the cut between two batches of one
+ * run is inflated twice); every other field means what it means there.  The record store of the BAM and SAM sinks holds the inflated
+ * bytes of the runs' blocks (index.inflated_bytes_read), and SBX_ENOMEM names that figure.
+ * The result equals the predicate over all records only when the file is in coordinate order, so every batch read is checked: a
+ * record with a reference whose (ref_id, pos) lies in front of the record read before it is SBX_ENOTSORTED.  A .bai whose number of
+ * references differs from the header's is SBX_EFORMAT, and so is a chunk offset that lands on no record (K2's chain check).  On
+ * failure no output file is left.
+ * index (may be NULL): blocks_in_file = BGZF blocks of the input in front of the first empty one (the EOF block); blocks_read, runs, compressed_bytes_read,
+ * inflated_bytes_read = the distinct blocks of the joined runs, their number, the file bytes from the first to the last block of
+ * every run, and what they inflate to; ms_plan = host time from the regions to the run list. */
+typedef struct {
+    uint64_t blocks_in_file, blocks_read, runs, compressed_bytes_read, inflated_bytes_read;
+    double ms_plan;
+} sbx_view_index_stats;
+#define SBX_VIEW_INDEX_OFF 0
+#define SBX_VIEW_INDEX_REQUIRED 1
+#define SBX_VIEW_INDEX_AUTO 2
+int sbx_view_run_indexed(const sbx_view_request* request, int index_mode, uint64_t* count, sbx_view_stats* stats,
+                         sbx_view_index_stats* index, char* err, size_t errlen);
 
 /* ---- validate: which records of a BAM are valid, and why not (`sambamba view -v`; `sambamba validate` is an empty stub) ----
  * A record is valid when isValid of BioD bio/std/hts/bam/validation/alignment.d says so.  K19 evaluates every class of error on its

@@ -10,7 +10,7 @@ from ._lib import (SbxError, Depth, lib, lib_path, inflate_blocks, compile_filte
                    bgzf_compress, write_bam, build_index, flagstat, format_flagstat, flagstat_cli_path,
                    sort_bam, sort_header_text, sort_cli_path, nsort_cli_path, markdup, markdup_header_text, markdup_cli_path,
                    merge, merge_header_text, merge_cli_path,
-                   view, view_num_filter, view_reference_info, view_cli_path, sam_cli_path,
+                   view, view_num_filter, view_reference_info, view_cli_path, sam_cli_path, iview_cli_path,
                    slice_bam, slice_cli_path,
                    import_sam, import_cli_path,
                    fixbins, index_fasta, index_cli_path, fixbins_cli_path,

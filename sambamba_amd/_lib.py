@@ -15,6 +15,7 @@ _VIEW_CLI_PATH = os.path.join(HERE, "csrc", "sbx-view")
 _SLICE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-slice")
 _SAM_CLI_PATH = os.path.join(HERE, "csrc", "sbx-sam")
 _NSORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-nsort")
+_IVIEW_CLI_PATH = os.path.join(HERE, "csrc", "sbx-iview")
 _IMPORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-import")
 _INDEX_CLI_PATH = os.path.join(HERE, "csrc", "sbx-index")
 _FIXBINS_CLI_PATH = os.path.join(HERE, "csrc", "sbx-fixbins")
@@ -161,6 +162,12 @@ class FastaStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_chunks", "reserved")] +
                 [(k, C.c_double) for k in ("ms_lines", "ms_segments", "ms_total_wall")])
 
+class ViewIndexStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("blocks_in_file", "blocks_read", "runs", "compressed_bytes_read", "inflated_bytes_read")] +
+                [("ms_plan", C.c_double)])
+
+VIEW_INDEX_MODES = {False: 0, True: 1, "auto": 2}       # SBX_VIEW_INDEX_OFF / _REQUIRED / _AUTO
+
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
 
 EXPORTS = [
@@ -172,7 +179,7 @@ EXPORTS = [
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
     "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
-    "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_run", "sbx_view_num_filter", "sbx_view_reference_info",
+    "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_run", "sbx_view_run_indexed", "sbx_view_num_filter", "sbx_view_reference_info",
     "sbx_validate_bam", "sbx_format_validate_report",
     "sbx_slice_bam",
     "sbx_import_sam",
@@ -220,6 +227,10 @@ def sam_cli_path():
 
 def nsort_cli_path():
     return _NSORT_CLI_PATH
+
+
+def iview_cli_path():
+    return _IVIEW_CLI_PATH
 
 
 def import_cli_path():
@@ -310,6 +321,8 @@ def lib():
     L.sbx_view_sam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Filter), C.POINTER(ViewOpts), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_char_p,
                                C.c_int, C.c_int, C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
     L.sbx_view_run.argtypes = [C.POINTER(ViewRequest), C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
+    L.sbx_view_run_indexed.argtypes = [C.POINTER(ViewRequest), C.c_int, C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.POINTER(ViewIndexStats),
+                                       C.c_char_p, C.c_size_t]
     L.sbx_validate_bam.argtypes = [C.c_char_p, C.c_int, C.POINTER(ValidateReport), C.POINTER(ValidateStats), C.c_char_p, C.c_size_t]
     L.sbx_format_validate_report.argtypes = [C.c_char_p, C.POINTER(ValidateReport), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_view_num_filter.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
@@ -338,7 +351,8 @@ def lib():
                      ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats),
                      ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats),
                      ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats), ("sbx_slice_stats", SliceStats),
-                     ("sbx_view_request", ViewRequest), ("sbx_validate_report", ValidateReport), ("sbx_validate_stats", ValidateStats)):
+                     ("sbx_view_request", ViewRequest), ("sbx_validate_report", ValidateReport), ("sbx_validate_stats", ValidateStats),
+                     ("sbx_view_index_stats", ViewIndexStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -788,7 +802,7 @@ def view_num_filter(text):
 
 
 def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, regions=(), bed=None, subsample=None, seed=None, level=-1,
-         index=False, command_line=None, device=-1, format="bam", with_header=False, valid=False):
+         index=False, command_line=None, device=-1, format="bam", with_header=False, valid=False, use_index=False, with_stats=False):
     """sbx_view_run (`sambamba view -c` / `-f bam` / `-f sam`): the records of in_path that pass the -F query string `filter`,
     `num_filter` ("i1/i2"), the subsampling (`subsample` = fraction, `seed` = 64-bit seed, drawn at random when None) and overlap
     `regions` ("chr", "chr:beg-end", "*": once per listed region, in listed order) or the BED file `bed` (once, in file order).
@@ -796,7 +810,13 @@ def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, r
     out_path + ".bai", command_line is the CL field of the @PG line that is added (None: no @PG) -- and the fields of sbx_view_stats
     come back as a dict.  format="sam" writes SAM text instead, formatted on the device: one line per record, after the header text
     when with_header (`view -h`); level and index do not apply to it (ValueError).  valid=True (`view -v`): only the records validate() calls
-    valid are selected."""
+    valid are selected.
+    use_index (sbx_view_run_indexed): False reads the whole file, as ever; True reads only the blocks the .bai of in_path names for
+    the regions or the BED file and fails with SBX_ENOINDEX (-7) without one; "auto" falls back to the whole file then.  The stats
+    dict then also carries the fields of sbx_view_index_stats (blocks_in_file, blocks_read, runs, ...), and n_records_in counts the
+    records that were described.  with_stats=True makes count=True return (count, stats dict)."""
+    if use_index not in (False, True, "auto"):
+        raise ValueError("view: use_index must be False, True or 'auto'")
     if format not in ("bam", "sam"):
         raise ValueError("view: format must be 'bam' or 'sam'")
     if format == "sam" and (level != -1 or index):
@@ -830,12 +850,19 @@ def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, r
     q.level, q.with_index, q.with_header, q.device = int(level), int(index), int(bool(with_header)), device
     q.valid_only = int(bool(valid))
     n = C.c_uint64(0)
-    rc = L.sbx_view_run(C.byref(q), C.byref(n), C.byref(st), err, 512)
+    ix = ViewIndexStats()
+    if use_index is False:
+        rc = L.sbx_view_run(C.byref(q), C.byref(n), C.byref(st), err, 512)
+    else:
+        rc = L.sbx_view_run_indexed(C.byref(q), VIEW_INDEX_MODES[use_index], C.byref(n), C.byref(st), C.byref(ix), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
+    stats = {k: getattr(st, k) for k, _ in ViewStats._fields_ if k != "reserved"}
+    if use_index is not False:
+        stats.update({k: getattr(ix, k) for k, _ in ViewIndexStats._fields_})
     if count:
-        return int(n.value)
-    return {k: getattr(st, k) for k, _ in ViewStats._fields_ if k != "reserved"}
+        return (int(n.value), stats) if with_stats else int(n.value)
+    return stats
 
 
 def validate(path, device=-1):

@@ -1,4 +1,4 @@
-"""Build libsbx_depth.so (HIP kernels + C ABI) and the sbx-depth / sbx-flagstat / sbx-sort / sbx-markdup / sbx-merge / sbx-view / sbx-sam / sbx-nsort / sbx-import / sbx-index / sbx-fixbins / sbx-slice / sbx-validate CLIs for gfx950 with hipcc.
+"""Build libsbx_depth.so (HIP kernels + C ABI) and the sbx-depth / sbx-flagstat / sbx-sort / sbx-markdup / sbx-merge / sbx-view / sbx-sam / sbx-iview / sbx-nsort / sbx-import / sbx-index / sbx-fixbins / sbx-slice / sbx-validate CLIs for gfx950 with hipcc.
 
 Usage: python -m sambamba_amd.build   (or sambamba_amd.build.build())
 Outputs are written in-tree (sambamba_amd/csrc/) so they travel with gpurun snapshots.
@@ -17,6 +17,7 @@ MARKDUP_CLI = os.path.join(CSRC, "sbx-markdup")
 MERGE_CLI = os.path.join(CSRC, "sbx-merge")
 VIEW_CLI = os.path.join(CSRC, "sbx-view")
 SAM_CLI = os.path.join(CSRC, "sbx-sam")        # view_cli.cpp once more, with SAM output (-DSBX_VIEW_SAM=1)
+IVIEW_CLI = os.path.join(CSRC, "sbx-iview")    # view_cli.cpp a third time, reading through the .bai (-DSBX_VIEW_INDEXED=1)
 NSORT_CLI = os.path.join(CSRC, "sbx-nsort")    # sort_cli.cpp once more, with the name orders (-DSBX_SORT_BY_NAME=1)
 IMPORT_CLI = os.path.join(CSRC, "sbx-import")
 INDEX_CLI = os.path.join(CSRC, "sbx-index")
@@ -69,7 +70,7 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd)
     for cli, src, defs in ((CLI, "cli.cpp", []), (FLAGSTAT_CLI, "flagstat_cli.cpp", []), (SORT_CLI, "sort_cli.cpp", []),
                            (MARKDUP_CLI, "markdup_cli.cpp", []), (MERGE_CLI, "merge_cli.cpp", []), (VIEW_CLI, "view_cli.cpp", []),
-                           (SAM_CLI, "view_cli.cpp", ["-DSBX_VIEW_SAM=1"]), (NSORT_CLI, "sort_cli.cpp", ["-DSBX_SORT_BY_NAME=1"]),
+                           (SAM_CLI, "view_cli.cpp", ["-DSBX_VIEW_SAM=1"]), (IVIEW_CLI, "view_cli.cpp", ["-DSBX_VIEW_INDEXED=1"]), (NSORT_CLI, "sort_cli.cpp", ["-DSBX_SORT_BY_NAME=1"]),
                            (IMPORT_CLI, "import_cli.cpp", []), (INDEX_CLI, "index_cli.cpp", []), (FIXBINS_CLI, "fixbins_cli.cpp", []), (SLICE_CLI, "slice_cli.cpp", []),
                            (VALIDATE_CLI, "validate_cli.cpp", [])):
         cli_src = os.path.join(CSRC, src)

@@ -67,6 +67,7 @@ size_t sbx_abi_sizeof(const char* name) {
     if (n == "sbx_view_request") return sizeof(sbx_view_request);
     if (n == "sbx_validate_report") return sizeof(sbx_validate_report);
     if (n == "sbx_validate_stats") return sizeof(sbx_validate_stats);
+    if (n == "sbx_view_index_stats") return sizeof(sbx_view_index_stats);
     return 0;
 }
 

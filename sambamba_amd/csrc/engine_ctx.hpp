@@ -12,6 +12,7 @@
 
 #include "common.hpp"
 #include "entry_util.hpp"
+#include "file_run.hpp"
 #include "host_io.hpp"
 #include "host_res.hpp"
 #include "kernels.hpp"
@@ -25,14 +26,6 @@ namespace sbx {
 // ~128 KiB beyond its own block -- into the following blocks, or, for the last blocks of a batch, into this padding.  (The general
 // kernel, which re-decodes every block the fast one flags, tests its input per symbol.)
 constexpr size_t kCompPad = 192 * 1024;
-
-// One run of the work list in FILE coordinates: BGZF blocks [blk0, blk1), inflated-stream offsets [ub, ue).
-struct FileRun {
-    uint32_t blk0, blk1;
-    uint64_t ub, ue;
-    bool open_end = false;        // ue is a block boundary in the middle of the record stream (ChainRun::open_end)
-    bool operator==(const FileRun& o) const { return blk0 == o.blk0 && blk1 == o.blk1 && ub == o.ub && ue == o.ue && open_end == o.open_end; }
-};
 
 // The work list of a launch: file runs, and the per-block tables of the launch in compacted coordinates
 // (block i of the launch is file block file_blk[i]; its payload sits at comp_off[i] of d_comp, its inflated

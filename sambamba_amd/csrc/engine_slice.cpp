@@ -17,9 +17,8 @@
 // every compressed segment of the call (SBX_BGZF_PIECE_BLOCKS honoured); each segment is a launch sequence of its own, and the host
 // copies a file range only after the segment in front of it has arrived: neither batching the segments of many regions into one
 // deflate launch nor overlapping the copy with the device is built.
-#include <map>
-
 #include "engine_store.hpp"
+#include "index_starts.hpp"
 #include "slice.hpp"
 #include "slice_core.hpp"
 
@@ -67,91 +66,6 @@ SliceRegions resolve_regions(const sbx_ctx* c, const char* const* regions, size_
     return out;
 }
 
-// ---- what the index says about the first record behind a window -------------------------------------------------------------------
-// first position of a bin of the UCSC scheme (levels of 2^29 .. 2^14 positions)
-uint64_t bin_first_pos(uint32_t id) {
-    static const uint32_t first[6] = {0, 1, 9, 73, 585, 4681}, shift[6] = {29, 26, 23, 20, 17, 14};
-    for (int l = 5; l >= 0; --l)
-        if (id >= first[l]) return (uint64_t)(id - first[l]) << shift[l];
-    return 0;
-}
-
-struct IndexStarts {
-    // per contig: (first position of a bin, lowest chunk start of the bins that begin there or behind), ascending by position
-    std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins_behind;
-    std::vector<uint64_t> contigs_behind;       // [r]: lowest chunk start of the contigs behind r, or where the records without reference start
-    uint64_t v_unmapped = 0;                    // the highest chunk end of the index: the first record without a reference, or the end
-    bool any_chunk = false;
-};
-
-IndexStarts index_starts(const sbx_ctx* c) {
-    IndexStarts s;
-    const size_t n = c->bai.refs.size();
-    std::vector<uint64_t> first(n, ~0ull);
-    for (size_t r = 0; r < n; ++r)
-        for (const BaiBin& b : c->bai.refs[r].bins) {
-            if (b.id > 37448) continue;
-            for (const BaiChunk& ch : b.chunks) {
-                if (ch.beg >= ch.end) continue;
-                first[r] = std::min(first[r], ch.beg);
-                s.v_unmapped = std::max(s.v_unmapped, ch.end);
-                s.any_chunk = true;
-            }
-        }
-    s.contigs_behind.assign(n + 1, ~0ull);
-    for (size_t r = n; r-- > 0;) s.contigs_behind[r] = r + 1 < n ? std::min(s.contigs_behind[r + 1], first[r + 1]) : ~0ull;
-    return s;
-}
-
-const std::vector<std::pair<uint64_t, uint64_t>>& bins_of(const sbx_ctx* c, IndexStarts* s, uint32_t own) {
-    auto it = s->bins_behind.find(own);
-    if (it != s->bins_behind.end()) return it->second;
-    std::vector<std::pair<uint64_t, uint64_t>> v;
-    if (own < c->bai.refs.size())
-        for (const BaiBin& b : c->bai.refs[own].bins) {
-            if (b.id > 37448) continue;
-            uint64_t lo = ~0ull;
-            for (const BaiChunk& ch : b.chunks) if (ch.beg < ch.end) lo = std::min(lo, ch.beg);
-            if (lo != ~0ull) v.push_back({bin_first_pos(b.id), lo});
-        }
-    std::sort(v.begin(), v.end());
-    for (size_t k = v.size(); k-- > 1;) v[k - 1].second = std::min(v[k - 1].second, v[k].second);
-    return s->bins_behind[own] = std::move(v);
-}
-
-// Stream offset of the first record behind the 16 KiB window of x that lies in no bin containing the window: the first record of a
-// bin that begins behind the window, else of a later contig, else the first record without a reference (the end of the stream when
-// there is none).
-uint64_t first_behind_window(const sbx_ctx* c, IndexStarts* s, uint32_t ref_id, uint32_t x, uint64_t u_unmapped) {
-    const uint64_t window_end = (((uint64_t)x >> 14) + 1) << 14;
-    uint64_t v = ~0ull;
-    if (ref_id < c->bai.refs.size()) {
-        const auto& bins = bins_of(c, s, ref_id);
-        auto it = std::lower_bound(bins.begin(), bins.end(), std::make_pair(window_end, (uint64_t)0));
-        if (it != bins.end()) v = it->second;
-        v = std::min(v, s->contigs_behind[ref_id]);
-    }
-    if (v == ~0ull) return u_unmapped;
-    uint32_t blk = 0;
-    return std::min(voffset_to_stream(c, v, &blk), u_unmapped);
-}
-
-// sorted runs joined where they share or touch a block (as build_runs joins chunks); the end of the joined run is the one that
-// reaches furthest, open when that one is
-std::vector<FileRun> join_runs(std::vector<FileRun> runs) {
-    std::sort(runs.begin(), runs.end(), [](const FileRun& a, const FileRun& b) { return a.ub != b.ub ? a.ub < b.ub : a.ue < b.ue; });
-    std::vector<FileRun> merged;
-    for (const FileRun& r : runs) {
-        if (!merged.empty() && r.blk0 <= merged.back().blk1) {
-            FileRun& m = merged.back();
-            if (r.ue > m.ue) { m.ue = r.ue; m.open_end = r.open_end; }
-            else if (r.ue == m.ue) m.open_end = m.open_end && r.open_end;
-            m.blk1 = std::max(m.blk1, r.blk1);
-        } else merged.push_back(r);
-    }
-    return merged;
-}
-
 void print_timing(const sbx_slice_stats& st) {
     if (!getenv("SBX_TIMING")) return;
     fprintf(stderr, "[sbx] slice: n_regions=%llu records_r1=%llu blocks_inflated=%llu blocks_copied=%llu bytes_copied=%llu stream_bytes=%llu "
@@ -186,8 +100,7 @@ int sbx_slice_bam(const char* in_path, const char* out_path, const char* const* 
 
         // ---- the index: where the records without a reference start; per edge the first record behind its window ----
         IndexStarts starts = index_starts(c.get());
-        uint64_t u_unmapped = first_rec;
-        if (starts.any_chunk) { uint32_t blk = 0; u_unmapped = std::max(first_rec, voffset_to_stream(c.get(), starts.v_unmapped, &blk)); }
+        const uint64_t u_unmapped = unmapped_start(c.get(), starts);
         const size_t n = sel.list.size();
         auto own_ref = [&](uint32_t r) { return r; };       // (one file: the index speaks the ids of the header)
         std::vector<SliceEdge> edges;

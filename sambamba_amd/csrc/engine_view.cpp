@@ -14,13 +14,20 @@
 // 64-bit offsets, and K13b writes the text piece by piece -- two device and two pinned buffers, so that the copy and the write of
 // a piece overlap the kernel of the next.
 //
-// The whole file is read whatever the regions say: restricting the read pass through the BAI work list is not built.
+// sbx_view_run and the three calls of before it read the whole file whatever the regions say (their stats promise n_records_in =
+// the records of the file, and they need no .bai).  sbx_view_run_indexed reads only the blocks the .bai names for the regions: the
+// runs of build_runs over all regions of the call, the stretch of `*` (index_starts.hpp), joined and cut into batches by the planner
+// of view_index_core.hpp.  Both paths feed the same consumers (read_batches); K12a / K12b select over whatever was described, so the
+// result is the one of the whole-file pass as long as the file is in coordinate order -- which K12c checks on every batch that was
+// read (SBX_ENOTSORTED).  The record store of the BAM and SAM sinks is then sized by the inflated bytes of the runs' blocks.
 #include "engine_store.hpp"
+#include "index_starts.hpp"
 #include "markdup_core.hpp"
 #include "sam.hpp"
 #include "valid.hpp"
 #include "view.hpp"
 #include "view_core.hpp"
+#include "view_index_core.hpp"
 
 namespace {
 
@@ -126,6 +133,125 @@ void print_timing(const sbx_view_stats& st, const char* sink) {
             st.ms_total_wall);
 }
 
+// ---- the read pass: the whole file, or the runs the index names for the regions ----
+void print_index_timing(const sbx_view_index_stats& ix) {
+    if (!getenv("SBX_TIMING")) return;
+    fprintf(stderr, "[sbx] view-index: blocks_in_file=%llu blocks_read=%llu runs=%llu compressed_bytes_read=%llu inflated_bytes_read=%llu ms_plan=%.3f\n",
+            (unsigned long long)ix.blocks_in_file, (unsigned long long)ix.blocks_read, (unsigned long long)ix.runs,
+            (unsigned long long)ix.compressed_bytes_read, (unsigned long long)ix.inflated_bytes_read, ix.ms_plan);
+}
+
+struct IndexedRead {
+    bool on = false;                // false: the whole-file pass
+    std::vector<FileRun> runs;      // joined, ascending
+    uint64_t store_bytes = 0;       // inflated bytes of their blocks: what the record store has to hold at most
+};
+
+// From the regions to the run list.  index_mode OFF, no region and no BED file, or AUTO without a .bai: the whole-file pass.
+IndexedRead plan_indexed_read(const sbx_ctx* c, const char* in_path, const ViewRegions& sel, int index_mode, sbx_view_index_stats* ix_out) {
+    const double w0 = wall_now();
+    const BlockTable& bt = c->blocks;
+    const uint32_t nbk = (uint32_t)bt.size();
+    IndexedRead rd;
+    sbx_view_index_stats ix{};
+    ix.blocks_in_file = nbk;
+    if (index_mode != SBX_VIEW_INDEX_OFF && index_mode != SBX_VIEW_INDEX_REQUIRED && index_mode != SBX_VIEW_INDEX_AUTO)
+        throw Error(SBX_EINVAL, "unknown index mode " + std::to_string(index_mode));
+    if (index_mode != SBX_VIEW_INDEX_OFF && !sel.list.empty()) {
+        if (c->has_index) rd.on = true;
+        else if (index_mode == SBX_VIEW_INDEX_REQUIRED) throw Error(SBX_ENOINDEX, std::string("the input has no index: ") + in_path + ".bai is needed");
+    }
+    if (!rd.on) {
+        ix.blocks_read = nbk; ix.runs = nbk ? 1 : 0; ix.compressed_bytes_read = c->file.size; ix.inflated_bytes_read = bt.out_off.back();
+        ix.ms_plan = (wall_now() - w0) * 1e3;
+        if (index_mode != SBX_VIEW_INDEX_OFF) print_index_timing(ix);
+        if (ix_out) *ix_out = ix;
+        return rd;
+    }
+    if (c->bai.refs.size() != c->hdr.refs.size())
+        throw Error(SBX_EFORMAT, "the index names " + std::to_string(c->bai.refs.size()) + " references, the header of the BAM " +
+                                     std::to_string(c->hdr.refs.size()) + ": the .bai does not belong to this file");
+    std::vector<sbx_region> placed;
+    bool star = false;
+    for (const sbx_region& g : sel.list) {
+        if (g.ref_id == viewc::kUnmappedRegion) star = true;
+        else if (g.ref_id != kNoRegion) placed.push_back(g);
+    }
+    if (!placed.empty()) rd.runs = build_runs(c, placed, true);
+    if (star) viewidx::unmapped_tail(bt.out_off.data(), nbk, unmapped_start(c, index_starts(c)), &rd.runs);
+    rd.runs = join_runs(std::move(rd.runs), 1);
+    viewidx::runs_cost(rd.runs, bt.out_off.data(), &ix.blocks_read, &rd.store_bytes);
+    ix.runs = rd.runs.size();
+    ix.inflated_bytes_read = rd.store_bytes;
+    for (const FileRun& r : rd.runs) ix.compressed_bytes_read += bt.comp_off[r.blk1 - 1] + bt.comp_len[r.blk1 - 1] + 8 - bt.coffset[r.blk0];
+    ix.ms_plan = (wall_now() - w0) * 1e3;
+    print_index_timing(ix);
+    if (ix_out) *ix_out = ix;
+    return rd;
+}
+
+// One batch of the read pass as its consumer sees it: records [0, nrec) of c->d_desc / c->d_rec_ref, their rec_off offsets of U.
+struct ViewBatch {
+    uint64_t nrec;
+    uint64_t u_end;                 // no record of the batch ends behind this offset of U
+    uint64_t keep_lo, keep_hi;      // the bytes of U from the batch's first record to behind its last: what a record store keeps
+};
+
+// K12c over the batch that was just described; the key of its last record is carried to the next one
+struct OrderCheck {
+    DevBuf<uint32_t> unsorted;
+    DevBuf<unsigned long long> last;
+    uint64_t prev_key = 0;
+    void run(sbx_ctx* c, uint64_t nrec, hipStream_t s) {
+        if (!nrec) return;
+        unsorted.ensure(1); last.ensure(1);
+        uint32_t flag = 0;
+        unsigned long long key = 0;
+        SBX_HIP(hipMemsetAsync(unsorted.p, 0, 4, s));
+        launch_view_order(c->d_desc.p, c->d_rec_ref.p, nrec, prev_key, unsorted.p, last.p, s);
+        SBX_HIP(hipMemcpyAsync(&flag, unsorted.p, 4, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipMemcpyAsync(&key, last.p, 8, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        if (flag) throw Error(SBX_ENOTSORTED, "the records the index names for the regions are not in coordinate order: the .bai does not describe this file");
+        prev_key = key;
+    }
+};
+
+// consume(ViewBatch) once per batch, in file order; it returns false to stop the pass.  *inflated receives the bytes K1 wrote.
+template <class Consume>
+void read_batches(sbx_ctx* c, const IndexedRead& rd, uint64_t batch_u, uint32_t* n_batches, uint64_t* inflated, Consume&& consume) {
+    const BlockTable& bt = c->blocks;
+    *n_batches = 0;
+    if (!rd.on) {
+        uint64_t cur = c->hdr.first_record_off;
+        for_each_record_batch(c, batch_u, n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+            const ViewBatch b{nrec, next - base, cur - base, next - base};
+            cur = next;
+            return consume(b);
+        });
+        *inflated = bt.out_off.back();
+        return;
+    }
+    *inflated = 0;
+    viewidx::Planner planner(rd.runs, bt.out_off.data(), batch_u);
+    std::vector<FileRun> batch;
+    OrderCheck order;
+    while (planner.next(&batch)) {
+        run_impl(c, {}, false, &batch);
+        const WorkList& wl = c->wl;
+        *inflated += wl.u_bytes;
+        // an open-ended piece stops in front of the record that straddles its last block boundary (describe_record_run)
+        const bool stopped = batch.size() == 1 && batch[0].open_end && c->index_straddler != kOffUnknown;
+        const uint64_t keep_hi = stopped ? c->index_straddler : wl.chain.back().u_end;
+        const uint64_t stop = stopped ? bt.out_off[batch[0].blk0] + c->index_straddler : batch.back().ue;
+        if (!planner.advance(stop)) continue;           // not one whole record in the piece: again, longer
+        ++*n_batches;
+        const uint64_t nrec = c->primary_records;
+        order.run(c, nrec, c->stream.get());
+        if (!consume(ViewBatch{nrec, keep_hi, wl.chain.front().u_beg, keep_hi})) return;
+    }
+}
+
 // ---- what the BAM and the SAM sink share: the read pass and the order of the entries ----
 // The records of the file in the resident store and the selected entries in output order: entry i is record perm[i], len[perm[i]]
 // bytes at store + off[perm[i]].
@@ -141,8 +267,8 @@ struct SelectedRecords {
 // Reads the file (K1, K2, K12a, K12b per batch; the records go to the store), closes the context and orders the entries (K9b over
 // the region index for listed regions).  hlen / per_record: bytes of the sink's header and of the per-record arrays it will add,
 // for the refusal of a file that does not fit.  Fills the counts and the times of the passes into *st.
-void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& sel, bool valid_only, uint64_t hlen,
-                     uint64_t per_record, SelectedRecords* out, sbx_view_stats* st_out) {
+void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& sel, const IndexedRead& rd, bool valid_only,
+                     uint64_t hlen, uint64_t per_record, SelectedRecords* out, sbx_view_stats* st_out) {
     sbx_view_stats& st = *st_out;
     const bool listed = !sel.merged && !sel.list.empty();
     DevBuf<uint8_t>& d_store = out->store;
@@ -150,8 +276,9 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
     DevBuf<uint32_t>& d_len = out->len;
     DevBuf<uint32_t>& d_perm = out->perm;
     Stream& stream = out->stream;
-    const StorePlan plan = plan_record_store(c.get(), hlen, per_record, "selecting records of");
-    const uint64_t u_first = plan.u_first;
+    // the store holds the records of the file, or -- indexed -- the bytes of the runs
+    const StorePlan plan = rd.on ? plan_store_bytes(rd.store_bytes, hlen, per_record, "selecting records of", "the blocks the index names for the regions do")
+                                 : plan_record_store(c.get(), hlen, per_record, "selecting records of");
     hipStream_t s = c->stream.get();
     d_store = DevBuf<uint8_t>((size_t)plan.store_bytes + 64);
     DevBuf<sbx_region> d_regions;
@@ -166,19 +293,22 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
 
     // ---- the read pass ----
     EventTimer t_a, t_b;
-    uint64_t n_in = 0, n_rec = 0, n_ent = 0, cur = u_first;
+    uint64_t n_in = 0, n_rec = 0, n_ent = 0, store_at = 0, inflated = 0;
     uint32_t n_batches = 0;
     bool too_many = false;
     unsigned long long acc[kViewAccWords] = {0};
-    for_each_record_batch(c.get(), plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+    read_batches(c.get(), rd, plan.batch_u, &n_batches, &inflated, [&](const ViewBatch& vb) -> bool {
+        const uint64_t nrec = vb.nrec, kept = vb.keep_hi - vb.keep_lo;
         const uint32_t groups = view_groups(nrec);
+        if (store_at + kept > plan.store_bytes) throw Error(SBX_EFORMAT, "internal error: the batches hold more bytes than the record store was planned for");
         d_count.ensure((size_t)nrec + 2);
         d_group_entries.ensure(groups + 4); d_group_records.ensure(groups + 4);
         d_group_entry_base.ensure(groups + 4); d_group_record_base.ensure(groups + 4);
         t_a.start(s);
-        copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
-        const uint16_t* d_invalid = valid.run(c.get(), nrec, next - base, s);
-        ViewSelectArgs a = select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p, d_invalid);
+        // the batch's records go behind those of the batches before
+        if (kept) SBX_HIP(hipMemcpyAsync(d_store.p + store_at, c->U() + vb.keep_lo, kept, hipMemcpyDeviceToDevice, s));
+        const uint16_t* d_invalid = valid.run(c.get(), nrec, vb.u_end, s);
+        ViewSelectArgs a = select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, vb.u_end, d_acc.p, d_invalid);
         a.with_lengths = 1;
         a.count = d_count.p; a.group_entries = d_group_entries.p; a.group_records = d_group_records.p;
         launch_view_select(a, s);
@@ -191,7 +321,8 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
         SBX_HIP(hipStreamSynchronize(s));
         st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_select += t_a.ms();
         n_in += nrec;
-        cur = next;
+        const int64_t store_delta = (int64_t)store_at - (int64_t)vb.keep_lo;
+        store_at += kept;
         if (acc[kViewAccBad]) return false;
         if (acc[kViewAccEntries] > 0xFFFFFFF0ull) { too_many = true; return false; }
         // the arrays grow to what the batch selected, then K12b fills them
@@ -204,7 +335,7 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
         ViewEmitArgs b{};
         b.s = a;
         b.group_entry_base = d_group_entry_base.p; b.group_record_base = d_group_record_base.p;
-        b.store_delta = (int64_t)base - (int64_t)u_first;
+        b.store_delta = store_delta;
         b.record_base = n_rec; b.entry_base = n_ent;
         b.off = d_off.p; b.len = d_len.p;
         b.entry_key = listed ? d_entry_key.p : nullptr; b.entry_rec = listed ? d_entry_rec.p : nullptr;
@@ -221,7 +352,6 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
     if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
     if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 output records");
     if (!listed && n_ent != n_rec) throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_ent) + " entries for " + std::to_string(n_rec) + " records");
-    const uint64_t u_total = plan.u_total;
     c.reset();                                       // the batch buffers make room for the sort and the output pieces
     d_count.release(); d_group_entries.release(); d_group_records.release(); d_group_entry_base.release(); d_group_record_base.release();
 
@@ -255,7 +385,7 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
     out->n = n;
     out->record_bytes = acc[kViewAccBytes];
     st.n_records_in = n_in; st.n_records_selected = n_rec; st.n_entries_out = n;
-    st.inflated_bytes = u_total;
+    st.inflated_bytes = inflated;
     st.n_regions = sel.given(); st.n_batches = n_batches;
 }
 
@@ -293,7 +423,8 @@ namespace {
 
 // ---- the three sinks: the bodies behind sbx_view_run ----
 int view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions, size_t n_regions,
-               const char* bed_path, int device, int valid_only, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
+               const char* bed_path, int device, int valid_only, int index_mode, sbx_view_index_stats* ix, uint64_t* count, sbx_view_stats* stats,
+               char* err, size_t errlen) {
     return run_entry(err, errlen, [&] {
         if (!in_path || !count) throw Error(SBX_EINVAL, "null argument");
         uint64_t threshold = 0;
@@ -301,6 +432,7 @@ int view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opt
         const double w0 = wall_now();
         Standalone c = open_record_pass(in_path, device, filter, true);
         const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
+        const IndexedRead rd = plan_indexed_read(c.get(), in_path, sel, index_mode, ix);
         hipStream_t s = c->stream.get();
         DevBuf<sbx_region> d_regions;
         upload_regions(sel, &d_regions, s);
@@ -310,12 +442,13 @@ int view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opt
         ValidPass valid;
         valid.init(valid_only != 0, s);
         EventTimer t_k;
-        uint64_t n_in = 0;
+        uint64_t n_in = 0, inflated = 0;
         uint32_t n_batches = 0;
-        for_each_record_batch(c.get(), index_batch_bytes(), &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        read_batches(c.get(), rd, index_batch_bytes(), &n_batches, &inflated, [&](const ViewBatch& vb) -> bool {
+            const uint64_t nrec = vb.nrec;
             t_k.start(s);
-            const uint16_t* d_invalid = valid.run(c.get(), nrec, next - base, s);
-            launch_view_select(select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, next - base, d_acc.p, d_invalid), s);
+            const uint16_t* d_invalid = valid.run(c.get(), nrec, vb.u_end, s);
+            launch_view_select(select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, vb.u_end, d_acc.p, d_invalid), s);
             t_k.stop(s);
             // (the next batch's K2 overwrites these descriptors, and may reallocate them, from the host side: K12a ends first)
             SBX_HIP(hipStreamSynchronize(s));
@@ -329,7 +462,7 @@ int view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opt
         SBX_HIP(hipStreamSynchronize(s));
         if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
         st.n_records_in = n_in; st.n_records_selected = acc[kViewAccRecords]; st.n_entries_out = acc[kViewAccEntries];
-        st.inflated_bytes = c->blocks.out_off.back();
+        st.inflated_bytes = inflated;
         st.n_regions = sel.given(); st.n_batches = n_batches;
         st.ms_total_wall = (wall_now() - w0) * 1e3;
         print_timing(st, "count");
@@ -340,7 +473,7 @@ int view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opt
 
 int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
              size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device, int valid_only,
-             sbx_view_stats* stats, char* err, size_t errlen) {
+             int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, char* err, size_t errlen) {
     const bool to_stdout = !out_path || !strcmp(out_path, "-");
     const char* const path = to_stdout ? "/dev/stdout" : out_path;
     const int rc = run_entry(err, errlen, [&] {
@@ -354,6 +487,7 @@ int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter
         Standalone c = open_record_pass(in_path, device, filter, true);
         OutputGuard out_file(path, to_stdout);
         const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
+        const IndexedRead rd = plan_indexed_read(c.get(), in_path, sel, index_mode, ix);
         std::string text, why;
         if (!mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why)) throw Error(SBX_EFORMAT, "SAM header: " + why);
         const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
@@ -361,7 +495,7 @@ int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter
 
         sbx_view_stats st{};
         SelectedRecords r;
-        select_resident(c, opts, threshold, sel, valid_only != 0, hlen, 48, &r, &st);
+        select_resident(c, opts, threshold, sel, rd, valid_only != 0, hlen, 48, &r, &st);
         const uint64_t n = r.n;
         hipStream_t s = r.stream.get();
         DevBuf<uint64_t> d_out_off((size_t)n + 2);
@@ -380,7 +514,7 @@ int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter
 
 int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
              size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device, int valid_only,
-             sbx_view_stats* stats, char* err, size_t errlen) {
+             int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, char* err, size_t errlen) {
     const bool to_stdout = !out_path || !strcmp(out_path, "-");
     const char* const path = to_stdout ? "/dev/stdout" : out_path;
     return run_entry(err, errlen, [&] {
@@ -392,13 +526,14 @@ int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter
         Standalone c = open_record_pass(in_path, device, filter, true);
         OutputGuard out_file(path, to_stdout);
         const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
+        const IndexedRead rd = plan_indexed_read(c.get(), in_path, sel, index_mode, ix);
         std::string text, why;
         if (with_header && !mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why))
             throw Error(SBX_EFORMAT, "SAM header: " + why);
         const std::vector<RefSeq> refs = c->hdr.refs;       // (select_resident lets go of the context)
         sbx_view_stats st{};
         SelectedRecords r;
-        select_resident(c, opts, threshold, sel, valid_only != 0, text.size(), 48 + 12, &r, &st);       // (+ length and offset of every line)
+        select_resident(c, opts, threshold, sel, rd, valid_only != 0, text.size(), 48 + 12, &r, &st);       // (+ length and offset of every line)
         const uint64_t n = r.n;
         hipStream_t s = r.stream.get();
         DeviceRefNames names;
@@ -509,7 +644,8 @@ sbx_view_request request_of(int sink, const char* in_path, const char* out_path,
 
 extern "C" {
 
-int sbx_view_run(const sbx_view_request* request, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
+int sbx_view_run_indexed(const sbx_view_request* request, int index_mode, uint64_t* count, sbx_view_stats* stats, sbx_view_index_stats* ix,
+                         char* err, size_t errlen) {
     sbx_view_request q{};
     const int rc = run_entry(err, errlen, [&] {
         if (!request) throw Error(SBX_EINVAL, "null argument");
@@ -521,12 +657,17 @@ int sbx_view_run(const sbx_view_request* request, uint64_t* count, sbx_view_stat
     });
     if (rc != SBX_OK) return rc;
     if (q.sink == SBX_VIEW_SINK_COUNT)
-        return view_count(q.in_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.device, q.valid_only, count, stats, err, errlen);
+        return view_count(q.in_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.device, q.valid_only, index_mode, ix, count, stats, err,
+                          errlen);
     if (q.sink == SBX_VIEW_SINK_BAM)
         return view_bam(q.in_path, q.out_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.pg_command_line, q.level, q.with_index,
-                        q.device, q.valid_only, stats, err, errlen);
+                        q.device, q.valid_only, index_mode, ix, stats, err, errlen);
     return view_sam(q.in_path, q.out_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.pg_command_line, q.with_header, q.device,
-                    q.valid_only, stats, err, errlen);
+                    q.valid_only, index_mode, ix, stats, err, errlen);
+}
+
+int sbx_view_run(const sbx_view_request* request, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
+    return sbx_view_run_indexed(request, SBX_VIEW_INDEX_OFF, count, stats, nullptr, err, errlen);
 }
 
 // the three entry points of before sbx_view_run: the same call with valid_only = 0

@@ -16,6 +16,9 @@
 //                        (region index, record ordinal) written per overlapped region, in listed order.
 //   k_view_compose       perm[i] = entry_rec[order[i]]: the sorted entries (K9b over the region index) as record ordinals, the form
 //                        plan_output / K9c read.
+//   K12c k_view_order    the indexed view only: one lane per described record, its (ref_id, pos) against the record in front of it
+//                        (the batch before for lane 0: a key the host carries over); one coalesced read of RecDesc and rec_ref
+//                        per record and of the neighbour's, which the cache holds; a wave that saw a decrease ORs 1 into the flag.
 //
 // Bytes moved (n records of a batch, s of them selected, e entries, r listed regions): K12a reads 36 n (descriptor, rec_ref), with -s
 // the name bytes (scattered, <= 254 each), with BAM output 4 s scattered words of U, and 12 r per wave through the scalar cache;
@@ -147,7 +150,32 @@ __global__ __launch_bounds__(256) void k_view_compose(const uint32_t* __restrict
     if (i < n) perm[i] = entry_rec[order[i]];
 }
 
+__device__ __forceinline__ uint64_t order_key(int32_t ref, int32_t pos) {
+    return ref < 0 ? 0ull : ((uint64_t)((uint32_t)ref + 1u) << 32) | (uint32_t)(pos + 1);
+}
+
+__global__ __launch_bounds__(kViewThreads) void k_view_order(const RecDesc* __restrict__ desc, const int32_t* __restrict__ rec_ref, uint64_t n,
+                                                            uint64_t prev_key, uint32_t* __restrict__ unsorted,
+                                                            unsigned long long* __restrict__ last_key) {
+    const uint64_t i = (uint64_t)blockIdx.x * kViewThreads + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        const uint64_t key = order_key(rec_ref[i], desc[i].pos);
+        const uint64_t before = i ? order_key(rec_ref[i - 1], desc[i - 1].pos) : prev_key;
+        bad = key != 0 && before != 0 && key < before;
+        if (i + 1 == n) *last_key = key;
+    }
+    if (__ballot(bad) && (threadIdx.x & 63u) == 0) atomicOr(unsorted, 1u);
+}
+
 }  // namespace
+
+void launch_view_order(const RecDesc* d_desc, const int32_t* d_rec_ref, uint64_t n, uint64_t prev_key, uint32_t* d_unsorted,
+                       unsigned long long* d_last_key, hipStream_t stream) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_view_order, dim3(view_groups(n)), dim3(kViewThreads), 0, stream, d_desc, d_rec_ref, n, prev_key, d_unsorted, d_last_key);
+    SBX_HIP(hipGetLastError());
+}
 
 void launch_view_select(const ViewSelectArgs& a, hipStream_t stream) {
     if (!a.n) return;

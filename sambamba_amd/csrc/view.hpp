@@ -49,4 +49,15 @@ void launch_view_emit(const ViewEmitArgs& a, hipStream_t stream);
 // d_perm[i] = d_entry_rec[d_order[i]], i < n
 void launch_view_compose(const uint32_t* d_entry_rec, const uint32_t* d_order, uint64_t n, uint32_t* d_perm, hipStream_t stream);
 
+
+// K12c, the order check of the indexed view: one lane per described record of a batch, in file order.  A record with a reference
+// whose (ref_id, pos) lies in front of that of the record before it -- of `prev_key` for the batch's first record: order_key of the
+// last record of the batch before, 0 for none -- sets *unsorted to 1.  Records without a reference take no part, as in the
+// reference's index builder.  *last_key receives the key of the batch's last record (0 when it has no reference).
+inline uint64_t view_order_key(int32_t ref, int32_t pos) {
+    return ref < 0 ? 0ull : ((uint64_t)((uint32_t)ref + 1u) << 32) | (uint32_t)(pos + 1);
+}
+void launch_view_order(const RecDesc* d_desc, const int32_t* d_rec_ref, uint64_t n, uint64_t prev_key, uint32_t* d_unsorted,
+                       unsigned long long* d_last_key, hipStream_t stream);
+
 }  // namespace sbx

@@ -16,6 +16,10 @@
 // front of the SAM records, -l together with SAM output is refused, and -v / --valid is taken for all three sinks: only the records
 // the reference's isValid accepts are selected (sbx_view_request::valid_only, K19).  (sbx-view keeps refusing sam and -v: folding the
 // two into one executable is the removal of this switch.)
+//
+// Compiled a third time with -DSBX_VIEW_INDEXED=1 it is `sbx-iview`: sbx-sam's options and sinks, and a region or -L reads only the
+// blocks the .bai names (sbx_view_run_indexed in REQUIRED mode, as the reference needs the index for a region); --no-index selects the
+// whole-file pass of the other two.  --no-index is not part of the @PG line's CL: the two passes write the same bytes.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -27,13 +31,68 @@
 #include "../../include/sbx_depth.h"
 #include "cli_opts.hpp"
 
+#ifndef SBX_VIEW_INDEXED
+#define SBX_VIEW_INDEXED 0
+#endif
+#if SBX_VIEW_INDEXED
+#undef SBX_VIEW_SAM
+#define SBX_VIEW_SAM 1
+#endif
 #ifndef SBX_VIEW_SAM
 #define SBX_VIEW_SAM 0
 #endif
 
 namespace {
 
-#if SBX_VIEW_SAM
+#if SBX_VIEW_INDEXED
+const char* const kProgram = "sbx-iview";
+
+void usage() {
+    fputs("Usage: sbx-iview [options] <input.bam> [region1 [...]]\n"
+          "\n"
+          "Selects records of a BAM file, as `sambamba view` does, on the GPU; writes them as SAM (the default), as a BAM (-f bam)\n"
+          "or their number (-c).  The SAM text is formatted on the GPU.\n"
+          "\n"
+          "Options: -F, --filter=FILTER\n"
+          "                    set custom filter for alignments\n"
+          "         --num-filter=NUMFILTER\n"
+          "                    filter flag bits; 'i1/i2' corresponds to -f i1 -F i2 samtools arguments;\n"
+          "                    either of the numbers can be omitted\n"
+          "         -f, --format=sam|bam\n"
+          "                    output format (default: sam); json, unpack, msgpack and cram are not supported\n"
+          "         -h, --with-header\n"
+          "                    print header before reads (always done for BAM output)\n"
+          "         -H, --header\n"
+          "                    output only header to stdout, as SAM\n"
+          "         -I, --reference-info\n"
+          "                    output to stdout only reference names and lengths in JSON\n"
+          "         -L, --regions=FILENAME\n"
+          "                    output only reads overlapping one of regions from the BED file\n"
+          "         -c, --count\n"
+          "                    output to stdout only count of matching records, hHI are ignored\n"
+          "         -l, --compression-level\n"
+          "                    specify compression level (from 0 to 9, works only for BAM output)\n"
+          "         -o, --output-filename\n"
+          "                    specify output filename (default, and '-': stdout)\n"
+          "         -s, --subsample=FRACTION\n"
+          "                    subsample reads (read pairs)\n"
+          "         --subsampling-seed=SEED\n"
+          "                    set seed for subsampling\n"
+          "         -v, --valid\n"
+          "                    output only valid alignments\n"
+          "         -t, --nthreads=NTHREADS, -p, --show-progress, -T, --ref-filename=FASTA\n"
+          "                    accepted for compatibility\n"
+          "         --no-index\n"
+          "                    read the whole file even for a region or -L (no .bai needed)\n"
+          "         -S, --sam-input\n"
+          "                    not supported\n"
+          "\n"
+          "Regions are 'chr', 'chr:beg-end' or '*' (reads without a reference); at most 1024 may be listed, a BED file has no limit.\n"
+          "A read that overlaps several listed regions is written once per region.  With a region or -L only the blocks the .bai names\n"
+          "are read, and the .bai is required; without either, or with --no-index, the whole file is read.\n",
+          stderr);
+}
+#elif SBX_VIEW_SAM
 const char* const kProgram = "sbx-sam";
 
 void usage() {
@@ -161,15 +220,18 @@ int print_text(const std::string& in, bool reference_info) {
 
 int main(int argc, char** argv) {
     std::string filter_str, num_filter, format = "sam", bed, level_str, out, frac_str, seed_str;
-    bool have_num_filter = false, have_frac = false, have_seed = false, header_only = false, reference_info = false, count_only = false, with_header = false, valid_only = false;
+    bool have_num_filter = false, have_frac = false, have_seed = false, header_only = false, reference_info = false, count_only = false, with_header = false, valid_only = false, no_index = false;
     std::vector<std::string> files;
     // long name, short name, takes a value, what it does: 0 ignored, 1 filter, 2 num-filter, 3 format, 4 -H, 5 -I, 6 -L, 7 -c, 8 level, 9 out,
-    // 10 fraction, 11 seed, 12 refused, 13 -h, 14 -v
+    // 10 fraction, 11 seed, 12 refused, 13 -h, 14 -v, 15 --no-index
     static const sbx::OptSpec opts[] = {
         {"filter", 'F', true, 1}, {"num-filter", 0, true, 2}, {"format", 'f', true, 3}, {"with-header", 'h', false, 13}, {"header", 'H', false, 4},
         {"reference-info", 'I', false, 5}, {"regions", 'L', true, 6}, {"count", 'c', false, 7}, {"valid", 'v', false, SBX_VIEW_SAM ? 14 : 12},
         {"sam-input", 'S', false, 12}, {"show-progress", 'p', false, 0}, {"compression-level", 'l', true, 8}, {"output-filename", 'o', true, 9},
         {"nthreads", 't', true, 0}, {"subsample", 's', true, 10}, {"subsampling-seed", 0, true, 11}, {"ref-filename", 'T', true, 0},
+#if SBX_VIEW_INDEXED
+        {"no-index", 0, false, 15},
+#endif
     };
     for (int i = 1; i < argc; ++i) {
         const sbx::OptToken t = sbx::next_opt(argc, argv, &i, opts);
@@ -197,6 +259,7 @@ int main(int argc, char** argv) {
             case 11: seed_str = t.value; have_seed = true; break;
             case 13: with_header = true; break;
             case 14: valid_only = true; break;
+            case 15: no_index = true; break;
             default: break;
         }
     }
@@ -263,19 +326,32 @@ int main(int argc, char** argv) {
     q.level = level;
     q.device = -1;
     q.valid_only = valid_only ? 1 : 0;
+    // sbx-iview: the read pass follows the index unless --no-index
+    auto run = [&](const sbx_view_request* request, uint64_t* count, char* e, size_t n) {
+#if SBX_VIEW_INDEXED
+        return sbx_view_run_indexed(request, no_index ? SBX_VIEW_INDEX_OFF : SBX_VIEW_INDEX_REQUIRED, count, nullptr, nullptr, e, n);
+#else
+        (void)no_index;
+        return sbx_view_run(request, count, nullptr, e, n);
+#endif
+    };
     if (count_only) {
         uint64_t count = 0;
         q.sink = SBX_VIEW_SINK_COUNT;
-        if (sbx_view_run(&q, &count, nullptr, err, sizeof err) != SBX_OK) return die(err);
+        if (run(&q, &count, err, sizeof err) != SBX_OK) return die(err);
         printf("%llu\n", (unsigned long long)count);
         return 0;
     }
     std::string cl = "view";
-    for (int i = 1; i < argc; ++i) { cl += ' '; cl += argv[i]; }
+    for (int i = 1; i < argc; ++i) {
+        if (SBX_VIEW_INDEXED && !strcmp(argv[i], "--no-index")) continue;
+        cl += ' ';
+        cl += argv[i];
+    }
     q.sink = sam_out ? SBX_VIEW_SINK_SAM : SBX_VIEW_SINK_BAM;
     q.out_path = out.empty() ? "-" : out.c_str();
     q.pg_command_line = cl.c_str();
     q.with_header = with_header ? 1 : 0;
-    if (sbx_view_run(&q, nullptr, nullptr, err, sizeof err) != SBX_OK) return die(err);
+    if (run(&q, nullptr, err, sizeof err) != SBX_OK) return die(err);
     return 0;
 }
