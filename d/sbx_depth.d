@@ -103,6 +103,15 @@ extern (C) nothrow @nogc {
     }
     int sbx_markdup(const(char)* in_path, const(char)* out_path, int remove_duplicates, int level, const(char)* pg_command_line, int device,
                     sbx_markdup_stats* stats, char* err, size_t errlen);
+    // the streamed path of sbx_markdup (a file larger than the device, or SBX_MARKDUP_WINDOW_BYTES); n_windows == 0: the resident path.
+    // struct_size: sbx_markdup_stream_stats.sizeof, set by the caller
+    struct sbx_markdup_stream_stats {
+        uint struct_size; uint n_windows; uint n_batch_runs; uint n_batches_skipped;
+        ulong window_bytes; ulong key_store_bytes; ulong n_key_records;
+        double ms_keys; double ms_plan; double ms_scatter; double ms_inflate_replay; double ms_index_replay;
+    }
+    int sbx_markdup_run(const(char)* in_path, const(char)* out_path, int remove_duplicates, int level, const(char)* pg_command_line, int device,
+                        sbx_markdup_stats* stats, sbx_markdup_stream_stats* stream_stats, char* err, size_t errlen);
     int sbx_markdup_header_text(const(char)* text, size_t n, const(char)* pg_command_line, char* out_, size_t cap, size_t* out_len);
     struct sbx_merge_stats {
         ulong n_records_in; ulong n_records_out; ulong n_records_rewritten; long bytes_grown;

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_markdup_stream_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -208,7 +208,7 @@ int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, si
  *             not the one its key was taken with -- the call fails with SBX_EIO ("the input changed while it was being sorted") and
  *             the output file is removed.  SBX_ENOMEM only when not even the keys, one minimal read batch and a window of one piece
  *             fit.
- * sbx_sort_bam_by_name, sbx_markdup, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins have the resident path only and
+ * sbx_sort_bam_by_name, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins have the resident path only and
  * refuse what does not fit with SBX_ENOMEM (a name order needs the names next to the keys: not built).
  * Milliseconds are device time of the kernels (inflate = K1, index = K2, keys = K9a + the copy into the record store, sort = K9b,
  * gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index.
@@ -253,10 +253,25 @@ int sbx_sort_bam_by_name(const char* in_path, const char* out_path, const sbx_fi
  * pairs (both mates mapped; matched by read name and RG string, 1st with 2nd, 3rd with 4th occurrence in file order) are compared by
  * library, the unclipped 5' coordinates and the strands of both ends, fragments by those of their one end; the best of a group (sum of
  * base qualities >= 15; ties: first in the file) stays unmarked, and a fragment where a paired read lies is always marked.  The header
- * text is re-serialised (sbx_markdup_header_text).  The whole file is resident on the device: one whose inflated records do not fit
- * next to one batch of the read pass is refused with SBX_ENOMEM, more than 2^32 records with SBX_EUNSUPPORTED.  Milliseconds are
- * device time (inflate = K1, index = K2, ends = K10a + the copy into the record store, pairing = hash sort + K10b, groups = K10c +
- * K10d, gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call. */
+ * text is re-serialised (sbx_markdup_header_text).  More than 2^32 records are refused with SBX_EUNSUPPORTED.  The duplicates are
+ * found on the device, on one of two paths that write the same file byte for byte:
+ *   resident  the inflated records fit the device next to one batch of the read pass: they stay there (the record store), the flags
+ *             are patched in place and the records gathered into the output.  n_windows == 0.
+ *   streamed  they do not fit (or SBX_MARKDUP_WINDOW_BYTES=<n> is set: tests and measurements, windows of n bytes rounded up to whole
+ *             pieces of the output stream): no record is kept.  Per record the key pass keeps the figures the decision needs and the
+ *             flag, and -- for the records that can pair -- name and RG bytes in a compact key store (K10e), over which the pairing
+ *             runs.  The output is the input in input order, so the stream is written window by window, n_windows of them: the
+ *             batches of the read pass whose records have a byte in the window are inflated and described again (K1 + K2) and K10f
+ *             puts each record at its place with its flag byte patched.  Batches and windows are both consecutive stretches of one
+ *             stream: a batch is run again at most once per window it touches, n_batch_runs <= n_batches + n_windows - 1, the file
+ *             is inflated about twice in all.  No temporary file.  If the input is not the same in both passes the call fails
+ *             with SBX_EIO ("the input changed while its duplicates were being marked") and the output file is removed.  SBX_ENOMEM
+ *             only when the per-record arrays (98 bytes per record at the peak), the key store (estimated), one minimal read batch,
+ *             the encoder and a window of one piece do not fit together; the message states the bytes needed and free.
+ * Milliseconds are device time (inflate = K1, index = K2, ends = K10a + the copy into the record store, pairing = hash sort + K10b,
+ * groups = K10c + K10d, gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the
+ * call.  On the streamed path inflate and index are those of the key pass alone (the replays: sbx_markdup_stream_stats), ends =
+ * K10a + K10e, groups = K10c, gather = the output plan + K10f. */
 typedef struct {
     uint64_t n_records_in, n_records_out;
     uint64_t n_end_pairs, n_single_ends, n_unmatched_pairs, n_duplicates;   /* the reference's stderr figures */
@@ -268,6 +283,22 @@ typedef struct {
  * SBX_EINVAL when out_path is the input.  On failure no output file is left behind. */
 int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates, int level,
                 const char* pg_command_line, int device, sbx_markdup_stats* stats, char* err, size_t errlen);
+/* What the streamed path of sbx_markdup did.  n_windows == 0: the resident path, and every other figure is 0.  struct_size: set by
+ * the caller to sizeof(sbx_markdup_stream_stats) and left as it is (a smaller value is SBX_EINVAL).  window_bytes: bytes of the
+ * output stream per window; n_batch_runs / n_batches_skipped: batches run again / not run, summed over the windows;
+ * key_store_bytes / n_key_records: the key store at its end and the records with an entry in it.  Milliseconds are device time:
+ * keys = K10e, plan = output lengths, destinations and the batches' spans, scatter = K10f, inflate_replay / index_replay = K1 / K2
+ * of the batches run again.  With SBX_TIMING=1 the same figures are printed in a `[sbx] markdup-stream:` line. */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t n_windows, n_batch_runs, n_batches_skipped;
+    uint64_t window_bytes, key_store_bytes, n_key_records;
+    double ms_keys, ms_plan, ms_scatter, ms_inflate_replay, ms_index_replay;
+} sbx_markdup_stream_stats;
+/* sbx_markdup with the figures of the streamed path: stream_stats may be NULL, and sbx_markdup is this call with NULL. */
+int sbx_markdup_run(const char* in_path, const char* out_path, int remove_duplicates, int level,
+                    const char* pg_command_line, int device, sbx_markdup_stats* stats, sbx_markdup_stream_stats* stream_stats,
+                    char* err, size_t errlen);
 /* The output header text for an input header text (host only): SamHeader.toSam of the input -- SO kept when it is unsorted, coordinate
  * or queryname -- with "@PG ID:sambamba CL:<pg_command_line> PP:<last @PG> VN:1.0" added unless pg_command_line is NULL or an @PG
  * with ID:sambamba exists.  Lengths and errors as sbx_sort_header_text. */

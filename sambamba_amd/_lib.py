@@ -105,6 +105,11 @@ class MarkdupStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_sort_passes", "n_batches")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_ends", "ms_pairing", "ms_groups", "ms_gather", "ms_deflate", "ms_total_wall")])
 
+class MarkdupStreamStats(C.Structure):
+    _fields_ = ([(k, C.c_uint32) for k in ("struct_size", "n_windows", "n_batch_runs", "n_batches_skipped")] +
+                [(k, C.c_uint64) for k in ("window_bytes", "key_store_bytes", "n_key_records")] +
+                [(k, C.c_double) for k in ("ms_keys", "ms_plan", "ms_scatter", "ms_inflate_replay", "ms_index_replay")])
+
 class MergeStats(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("n_records_in", "n_records_out", "n_records_rewritten")] + [("bytes_grown", C.c_int64)] +
                 [(k, C.c_uint64) for k in ("inflated_bytes", "merged_stream_bytes", "compressed_bytes")] +
@@ -177,7 +182,7 @@ EXPORTS = [
     "sbx_depth_window_stats",
     "sbx_format_base_rows", "sbx_stream_base_rows", "sbx_plan_batches", "sbx_run_batch", "sbx_last_run_stats", "sbx_tile_info", "sbx_next_active_range", "sbx_preload",
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
-    "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_header_text",
+    "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_run", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
     "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_run", "sbx_view_run_indexed", "sbx_view_num_filter", "sbx_view_reference_info",
     "sbx_validate_bam", "sbx_format_validate_report",
@@ -310,6 +315,8 @@ def lib():
                                        C.c_size_t]
     L.sbx_sort_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_markdup.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(MarkdupStats), C.c_char_p, C.c_size_t]
+    L.sbx_markdup_run.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(MarkdupStats),
+                                  C.POINTER(MarkdupStreamStats), C.c_char_p, C.c_size_t]
     L.sbx_markdup_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_merge_bam.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.POINTER(MergeStats),
                                 C.c_char_p, C.c_size_t]
@@ -348,7 +355,8 @@ def lib():
     for name, ty in (("sbx_region", Region), ("sbx_header_info", HeaderInfo), ("sbx_region_stats", RegionStats),
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
-                     ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_merge_stats", MergeStats),
+                     ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_markdup_stream_stats", MarkdupStreamStats),
+                     ("sbx_merge_stats", MergeStats),
                      ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats),
                      ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats), ("sbx_slice_stats", SliceStats),
                      ("sbx_view_request", ViewRequest), ("sbx_validate_report", ValidateReport), ("sbx_validate_stats", ValidateStats),
@@ -513,15 +521,21 @@ def sort_header_text(text):
 
 def markdup(in_path, out_path, remove_duplicates=False, level=-1, command_line=None, device=-1):
     """sbx_markdup (`sambamba markdup`): marks (remove_duplicates: removes) the duplicates of in_path into out_path on the device;
-    command_line is the CL field of the @PG line that is added (None: no @PG).  Returns the fields of sbx_markdup_stats as a dict."""
+    command_line is the CL field of the @PG line that is added (None: no @PG).  Returns the fields of sbx_markdup_stats as a dict,
+    plus n_windows, n_batch_runs, window_bytes and key_store_bytes of sbx_markdup_stream_stats: zeros when the records stayed on the
+    device, the figures of the streamed path when they did not fit (or SBX_MARKDUP_WINDOW_BYTES is set)."""
     L = lib()
     st = MarkdupStats()
+    ss = MarkdupStreamStats()
+    ss.struct_size = C.sizeof(MarkdupStreamStats)
     err = C.create_string_buffer(512)
-    rc = L.sbx_markdup(in_path.encode(), out_path.encode(), int(bool(remove_duplicates)), int(level),
-                       command_line.encode() if command_line is not None else None, device, C.byref(st), err, 512)
+    rc = L.sbx_markdup_run(in_path.encode(), out_path.encode(), int(bool(remove_duplicates)), int(level),
+                           command_line.encode() if command_line is not None else None, device, C.byref(st), C.byref(ss), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
-    return {k: getattr(st, k) for k, _ in MarkdupStats._fields_}
+    out = {k: getattr(st, k) for k, _ in MarkdupStats._fields_}
+    out.update({k: getattr(ss, k) for k in ("n_windows", "n_batch_runs", "window_bytes", "key_store_bytes")})
+    return out
 
 
 def markdup_header_text(text, command_line=None):

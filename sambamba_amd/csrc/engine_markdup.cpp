@@ -6,6 +6,16 @@
 // ends and one marker per pair end by their two (K10c: LSD over the words with K9b's passes, a key gather between the words, digits
 // that do not vary skipped); "not the first of its group" marks the duplicates; K10d patches the flags in the store; the file is
 // written in input order -- with -r without the marked records -- by the writer sort uses.
+//
+// A file whose records do not fit the device next to one batch of the read pass takes the STREAMED path (markdup_streamed; also
+// forced by SBX_MARKDUP_WINDOW_BYTES): no record store.  The key pass runs K10a and, next to it, K10e, which keeps the flag of every
+// record and -- for the pairable ones -- the bytes K10b compares in a compact key store; the batches are saved.  K10b runs over the
+// key store, K10c as ever.  The output stream is the input stream with some flag bytes changed and, with -r, some records left out:
+// one kernel turns flag + duplicate bit into the length every record has in the output, a scan into its destination, and the stream
+// is written window by window -- the saved batches whose records have a byte in the window are run again (run_record_batch) and K10f
+// puts their records in place with byte 19 patched.  Batches and windows are both consecutive stretches of one ordered stream, so a
+// batch is run again for at most the windows its stretch touches: the file goes through K1 + K2 about twice in all.  The file
+// written is the resident path's byte for byte.
 #include "engine_store.hpp"
 #include "markdup.hpp"
 #include "markdup_core.hpp"
@@ -54,6 +64,380 @@ uint64_t compact(MdPred pred, const uint8_t* d_c, const uint32_t* d_mate, uint64
     return total;
 }
 
+// the buffers of K10c that live to its end; the caller frees them when its timer has stopped (a free waits for the device)
+struct GroupBuffers {
+    DevBuf<uint32_t> d_first;
+    DevBuf<uint64_t> d_w0, d_end2;
+};
+
+// K10c, shared by both paths: the pairs K10b made and the single ends, each sorted by their key words; d_dup[record] = 1 for every
+// record that is not the first of its group.  Ends with the stream idle.
+void mark_groups(const MdRecords& r, uint64_t n, uint64_t n_pairable, const uint32_t* d_mate, uint32_t ref_bits, WordSorter& sorter,
+                 DevBuf<uint32_t>& d_cnt, DevBuf<uint64_t>& d_base, unsigned long long* d_acc, uint8_t* d_dup, hipStream_t s, GroupBuffers& g,
+                 uint64_t* n_pairs_out, uint64_t* n_single_out) {
+    DevBuf<uint32_t>& d_first = g.d_first;
+    DevBuf<uint64_t>&d_w0 = g.d_w0, &d_end2 = g.d_end2;
+    d_first.alloc((size_t)n_pairable / 2 + 2);
+    const uint64_t n_pairs = compact(kMdPredPairFirst, r.cls, d_mate, n, d_cnt, d_base, d_first.p, s);
+    d_w0.alloc((size_t)n_pairs + 2);
+    DevBuf<uint64_t> d_w1((size_t)n_pairs + 2), d_w2((size_t)n_pairs + 2);
+    d_end2.alloc((size_t)n_pairs + 2);
+    launch_md_pair_keys(d_first.p, d_mate, n_pairs, r, ref_bits, d_w0.p, d_w1.p, d_w2.p, d_end2.p, s);
+    launch_iota(sorter.idx(), n_pairs, s);
+    sorter.sort_by(d_w2.p, n_pairs, d_acc, s);
+    sorter.sort_by(d_w1.p, n_pairs, d_acc, s);
+    sorter.sort_by(d_w0.p, n_pairs, d_acc, s);
+    launch_md_pair_dups(sorter.idx(), d_w0.p, d_w1.p, n_pairs, d_first.p, d_mate, d_dup, s);
+    d_w1.release(); d_w2.release();
+    DevBuf<uint32_t> d_single((size_t)(n - 2 * n_pairs) + 2);
+    const uint64_t n_single = compact(kMdPredSingle, r.cls, d_mate, n, d_cnt, d_base, d_single.p, s);
+    const uint64_t m = 2 * n_pairs + n_single;
+    DevBuf<uint64_t> d_v0((size_t)m + 2), d_v1((size_t)m + 2);
+    DevBuf<uint32_t> d_rec((size_t)m + 2);
+    launch_md_single_entries(d_w0.p, d_end2.p, n_pairs, d_single.p, n_single, r, d_v0.p, d_v1.p, d_rec.p, d_acc, s);
+    launch_iota(sorter.idx(), m, s);
+    sorter.sort_by(d_v1.p, m, d_acc, s);
+    sorter.sort_by(d_v0.p, m, d_acc, s);
+    launch_md_single_dups(sorter.idx(), d_v0.p, d_v1.p, d_rec.p, m, d_dup, s);
+    SBX_HIP(hipStreamSynchronize(s));
+    *n_pairs_out = n_pairs;
+    *n_single_out = n_single;
+}
+
+// what both paths know before the first batch: the output header, the libraries of the read groups (on the device), the key widths
+struct MdJob {
+    std::vector<uint8_t> header;
+    int32_t n_ref = 0;
+    uint32_t ref_bits = 0;
+    uint64_t hash_mask = ~0ull;
+    std::string rg_ids;
+    std::vector<uint32_t> rg_off;
+    std::vector<int32_t> library_of;
+    DevBuf<char> d_rg_ids;
+    DevBuf<uint32_t> d_rg_off;
+    DevBuf<int32_t> d_rg_lib;
+    void upload(hipStream_t s) {
+        d_rg_ids.alloc(rg_ids.size() + 1);
+        d_rg_off.alloc(rg_off.size() + 1);
+        d_rg_lib.alloc(library_of.size() + 1);
+        if (rg_off.empty()) return;
+        SBX_HIP(hipMemcpyAsync(d_rg_ids.p, rg_ids.data(), rg_ids.size(), hipMemcpyHostToDevice, s));
+        SBX_HIP(hipMemcpyAsync(d_rg_off.p, rg_off.data(), rg_off.size() * 4, hipMemcpyHostToDevice, s));
+        SBX_HIP(hipMemcpyAsync(d_rg_lib.p, library_of.data(), library_of.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    LibTable table() const { return LibTable{d_rg_ids.p, d_rg_off.p, d_rg_lib.p, (int32_t)rg_off.size()}; }
+};
+
+// the `[sbx] markdup:` line of SBX_TIMING; the four wall-clock phases in ms
+void print_markdup_line(const sbx_markdup_stats& st, double open_ms, double read_ms, double dup_ms, double write_ms) {
+    fprintf(stderr, "[sbx] markdup: n_records_in=%llu n_records_out=%llu n_end_pairs=%llu n_single_ends=%llu n_unmatched_pairs=%llu "
+                    "n_duplicates=%llu inflated_bytes=%llu stream_bytes=%llu compressed_bytes=%llu n_sort_passes=%u n_batches=%u "
+                    "ms_inflate=%.2f ms_index=%.2f ms_ends=%.2f ms_pairing=%.2f ms_groups=%.2f ms_gather=%.2f ms_deflate=%.2f "
+                    "ms_total_wall=%.1f (open %.1f, read pass %.1f, duplicates %.1f, write %.1f)\n",
+            (unsigned long long)st.n_records_in, (unsigned long long)st.n_records_out, (unsigned long long)st.n_end_pairs,
+            (unsigned long long)st.n_single_ends, (unsigned long long)st.n_unmatched_pairs, (unsigned long long)st.n_duplicates,
+            (unsigned long long)st.inflated_bytes, (unsigned long long)st.stream_bytes, (unsigned long long)st.compressed_bytes,
+            st.n_sort_passes, st.n_batches, st.ms_inflate, st.ms_index, st.ms_ends, st.ms_pairing, st.ms_groups, st.ms_gather, st.ms_deflate,
+            st.ms_total_wall, open_ms, read_ms, dup_ms, write_ms);
+}
+
+// SBX_MARKDUP_WINDOW_BYTES (tests, measurements): forces the streamed path with windows of this many bytes, rounded up to whole
+// pieces.  0: unset (or not a positive decimal number).
+uint64_t markdup_window_hook() {
+    const char* e = getenv("SBX_MARKDUP_WINDOW_BYTES");
+    if (!e || *e < '0' || *e > '9') return 0;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    return *end ? 0 : (uint64_t)v;
+}
+
+// Bytes of per-record arrays at the peak of the streamed path, which is K10c.  The key pass keeps 39 per record (off 8, len 4, class 1,
+// position key 8, score 4, hash 8, rg_at 4, flag 2); pairing adds mate 4, dup 1 and the hash sort's two (key, index) buffers, 24 per
+// pairable record; for K10c the hashes (8) and the key store are gone and the pair words (4 x 8 per pair = 16 per paired record), the
+// first-of-pair list (2) and the single-end entries (20 per entry, at most one per record) come: 39 - 8 + 5 + 24 + 2 + 16 + 20 = 98.
+// While the windows are written 17 remain (len 4, output length 4, destination 8, flag byte 1).
+constexpr uint64_t kStreamedPerRecord = 98;
+// Estimate of the key store per record of the file: an entry is 2 + l_read_name + the RG value's length, only pairable records have
+// one, and the store grows by half whenever a batch does not fit (the old and the new buffer exist side by side for that moment).
+constexpr uint64_t kStreamedKeyBytes = 48;
+
+// The streamed path (see the head of this file).  hook: SBX_MARKDUP_WINDOW_BYTES or 0.
+void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool remove, int level, uint64_t hook, double w0,
+                      sbx_markdup_stats* stats, sbx_markdup_stream_stats* stream_stats) {
+    const std::vector<uint8_t>& header = job.header;
+    const uint64_t hlen = header.size();
+    const uint64_t u_total = c->blocks.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
+    const uint64_t piece_blocks = bgzf_piece_blocks(), piece_bytes = piece_blocks * (uint64_t)kBgzfPayload;
+    // the encoder's buffers, as plan_store_bytes reserves them, and the smallest window: one piece, or the whole stream when it is shorter
+    const uint64_t stream_est = u_total - u_first + hlen;
+    const uint64_t cap_bytes = std::min<uint64_t>(piece_bytes, stream_est + kBgzfPayload);
+    const uint64_t out_reserve = cap_bytes * 3 + (8ull << 20);
+    const uint64_t est_records = (u_total - u_first) / 160 + 4096;
+    const uint64_t arrays_est = est_records * kStreamedPerRecord, keys_est = est_records * kStreamedKeyBytes;
+    {
+        size_t free_b = 0, total_b = 0;
+        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t min_batch = 5ull * (64ull << 20);
+        const uint64_t need = arrays_est + keys_est + min_batch + out_reserve + cap_bytes;
+        if (need > free_b)
+            throw Error(SBX_ENOMEM, "the file does not fit the device: marking its duplicates in windows needs " + std::to_string(need) +
+                                        " bytes of device memory (" + std::to_string(arrays_est) + " for the per-record arrays, " + std::to_string(keys_est) +
+                                        " for the key store (an estimate), " + std::to_string(min_batch) + " for one read batch, " +
+                                        std::to_string(out_reserve) + " for the encoder and " + std::to_string(cap_bytes) + " for a window of one piece), " +
+                                        std::to_string(free_b) + " are free");
+    }
+    const uint64_t batch_u = std::min<uint64_t>(index_batch_bytes(arrays_est + keys_est + out_reserve + cap_bytes), kWindowedBatchBytes);
+    hipStream_t s = c->stream.get();
+    job.upload(s);
+    DevBuf<uint64_t> d_off, d_pos_key, d_hash, d_key_off, d_tile_sum;
+    DevBuf<uint32_t> d_len, d_score, d_rg_at, d_key_len;
+    DevBuf<uint8_t> d_cls, d_keys;
+    DevBuf<uint16_t> d_flag;
+    DevBuf<unsigned long long> d_acc(kMdAccWords);
+    SBX_HIP(hipMemsetAsync(d_acc.p, 0, kMdAccWords * sizeof(unsigned long long), s));
+    SBX_HIP(hipStreamSynchronize(s));
+    const double w1 = wall_now();
+
+    // ---- the key pass: K10a + K10e, nothing copied; the batches are saved ----
+    sbx_markdup_stats st{};
+    sbx_markdup_stream_stats ss{};
+    EventTimer t_k, t_m, t_e;
+    std::vector<SavedBatch> saved;
+    uint64_t n = 0, key_bytes = 0;
+    uint32_t n_batches = 0;
+    bool too_many = false;
+    unsigned long long acc[kMdAccWords] = {0};
+    for_each_record_batch(c.get(), batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        if (n + nrec > 0xFFFFFFF0ull) { too_many = true; return false; }
+        const size_t want = (size_t)(n + nrec + 2);
+        grow_keeping(d_off, (size_t)n, want, s);
+        grow_keeping(d_pos_key, (size_t)n, want, s);
+        grow_keeping(d_hash, (size_t)n, want, s);
+        grow_keeping(d_len, (size_t)n, want, s);
+        grow_keeping(d_score, (size_t)n, want, s);
+        grow_keeping(d_rg_at, (size_t)n, want, s);
+        grow_keeping(d_cls, (size_t)n, want, s);
+        grow_keeping(d_flag, (size_t)n, want, s);
+        d_key_len.ensure((size_t)nrec + 2);
+        d_key_off.ensure((size_t)nrec + 2);
+        d_tile_sum.ensure(len_tiles(nrec) + 2);
+        MdEndsArgs a{};
+        a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base;
+        a.n_ref = job.n_ref; a.ref_bits = job.ref_bits; a.hash_mask = job.hash_mask;
+        a.store_delta = 0;                               // (no store: K10e overwrites off[] of the pairable records)
+        a.out_base = n;
+        a.lib = job.table();
+        a.r = MdRecords{d_off.p, d_len.p, d_cls.p, d_pos_key.p, d_score.p, d_hash.p, d_rg_at.p};
+        a.acc = d_acc.p;
+        MdKeyArgs k{};
+        k.U = a.U; k.desc = a.desc; k.n = nrec; k.out_base = n; k.r = a.r;
+        k.flag = d_flag.p; k.key_len = d_key_len.p; k.key_off = d_key_off.p;
+        t_k.start(s);
+        launch_md_ends(a, s);
+        t_k.stop(s);
+        t_m.start(s);
+        launch_md_key_measure(k, s);
+        launch_sorted_offsets(d_key_len.p, nullptr, nrec, key_bytes, d_tile_sum.p, d_key_off.p, s);
+        t_m.stop(s);
+        uint64_t key_end = key_bytes;
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        if (nrec) SBX_HIP(hipMemcpyAsync(&key_end, d_key_off.p + nrec, 8, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_ends += t_k.ms() + t_m.ms();
+        ss.ms_keys += t_m.ms();
+        saved.back().first_kept = n;
+        saved.back().n_kept = nrec;
+        n += nrec;
+        if (acc[kMdAccBad]) return false;
+        grow_keeping(d_keys, (size_t)key_bytes, (size_t)key_end + 64, s);       // (SBX_ENOMEM when the keys do not fit)
+        k.key_store = d_keys.p;
+        t_e.start(s);
+        launch_md_key_emit(k, s);
+        t_e.stop(s);
+        // (the next batch's K1 / K2 overwrite U and the descriptors: K10e ends first)
+        SBX_HIP(hipStreamSynchronize(s));
+        st.ms_ends += t_e.ms();
+        ss.ms_keys += t_e.ms();
+        key_bytes = key_end;
+        return true;
+    }, &saved);
+    if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
+    if (acc[kMdAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kMdAccBad]));
+    const double w2 = wall_now();
+
+    // ---- K10b over the key store ----
+    const MdRecords r{d_off.p, d_len.p, d_cls.p, d_pos_key.p, d_score.p, d_hash.p, d_rg_at.p};
+    DevBuf<uint8_t> d_dup((size_t)n + 2);
+    uint64_t n_pairable = 0, n_pairs = 0, n_single = 0;
+    uint32_t n_passes = 0;
+    {
+        DevBuf<uint32_t> d_mate((size_t)n + 2), d_cnt(md_groups(n) + 4);
+        DevBuf<uint64_t> d_base(md_groups(n) + 4);
+        WordSorter sorter;
+        sorter.reserve(n);
+        EventTimer t_pair, t_groups;
+        t_pair.start(s);
+        launch_fill32(d_mate.p, kMdNone, n, s);
+        SBX_HIP(hipMemsetAsync(d_dup.p, 0, (size_t)n + 2, s));
+        n_pairable = compact(kMdPredPairable, d_cls.p, d_mate.p, n, d_cnt, d_base, sorter.idx(), s);
+        sorter.sort_by(d_hash.p, n_pairable, d_acc.p, s);
+        launch_md_pair_runs_keys(sorter.keys(), sorter.idx(), n_pairable, d_keys.p, r, d_mate.p, s);
+        t_pair.stop(s);
+        SBX_HIP(hipStreamSynchronize(s));
+        st.ms_pairing = t_pair.ms();
+        d_hash.release();
+        d_keys.release();
+        d_off.release();
+        d_rg_at.release();
+
+        // ---- K10c ----
+        GroupBuffers groups;
+        t_groups.start(s);
+        mark_groups(r, n, n_pairable, d_mate.p, job.ref_bits, sorter, d_cnt, d_base, d_acc.p, d_dup.p, s, groups, &n_pairs, &n_single);
+        t_groups.stop(s);
+        SBX_HIP(hipStreamSynchronize(s));
+        st.ms_groups = t_groups.ms();
+        n_passes = sorter.passes;
+    }
+    d_pos_key.release(); d_score.release(); d_cls.release();
+
+    // ---- the output plan: lengths in the output, destinations, the span of every batch ----
+    DevBuf<uint8_t> d_hi((size_t)n + 2);
+    DevBuf<uint32_t> d_out_len((size_t)n + 2);
+    DevBuf<uint64_t> d_dest((size_t)n + 2);
+    std::vector<uint64_t> span_lo(saved.size(), ~0ull), span_hi(saved.size(), 0);
+    uint64_t total = hlen;
+    {
+        std::vector<uint64_t> first(saved.size() + 1, n);
+        for (size_t b = 0; b < saved.size(); ++b) first[b] = saved[b].first_kept;
+        DevBuf<uint64_t> d_first(first.size()), d_lo(saved.size() + 1), d_hi_span(saved.size() + 1);
+        d_tile_sum.ensure(len_tiles(n) + 2);
+        SBX_HIP(hipMemcpyAsync(d_first.p, first.data(), first.size() * 8, hipMemcpyHostToDevice, s));
+        EventTimer t;
+        t.start(s);
+        launch_md_out_plan(d_flag.p, d_dup.p, d_len.p, n, remove ? 1u : 0u, d_hi.p, d_out_len.p, d_acc.p, s);
+        launch_sorted_offsets(d_out_len.p, nullptr, n, hlen, d_tile_sum.p, d_dest.p, s);
+        launch_batch_spans(d_dest.p, d_out_len.p, d_first.p, (uint32_t)saved.size(), d_lo.p, d_hi_span.p, s);
+        t.stop(s);
+        if (n) SBX_HIP(hipMemcpyAsync(&total, d_dest.p + n, 8, hipMemcpyDeviceToHost, s));
+        if (!saved.empty()) {
+            SBX_HIP(hipMemcpyAsync(span_lo.data(), d_lo.p, saved.size() * 8, hipMemcpyDeviceToHost, s));
+            SBX_HIP(hipMemcpyAsync(span_hi.data(), d_hi_span.p, saved.size() * 8, hipMemcpyDeviceToHost, s));
+        }
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        ss.ms_plan = t.ms();
+    }
+    d_flag.release(); d_dup.release(); d_tile_sum.release(); d_key_len.release(); d_key_off.release();
+    const uint64_t n_out = acc[kMdAccKept];
+    if (!remove && (n_out != n || total != hlen + acc[kMdAccBytes])) throw Error(SBX_EFORMAT, "internal error: the offsets of the records do not add up");
+
+    // ---- the window: what is free next to the batch buffers (they stay) less the encoder's ----
+    const uint32_t cap_blocks = (uint32_t)std::min<uint64_t>(piece_blocks, std::max<uint64_t>(1, (total + kBgzfPayload - 1) / kBgzfPayload));
+    uint64_t window_bytes = hook;
+    if (!window_bytes) {
+        size_t free_b = 0, total_b = 0;
+        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+        const uint64_t reserve = out_reserve + (64ull << 20);
+        const uint64_t avail = free_b > reserve ? free_b - reserve : 0;
+        const uint64_t smallest = std::min<uint64_t>(piece_bytes, total);
+        if (avail < smallest)
+            throw Error(SBX_ENOMEM, "the file does not fit the device: marking its duplicates in windows needs " + std::to_string(smallest + reserve) +
+                                        " bytes of device memory (a window of one piece and the encoder, next to the read batch and 17 bytes per "
+                                        "record), " + std::to_string(free_b) + " are free");
+        window_bytes = std::max<uint64_t>(avail / piece_bytes, 1) * piece_bytes;
+    }
+    const std::vector<sortc::Window> windows = sortc::plan_windows(total, piece_bytes, window_bytes);
+    const uint64_t span = sortc::window_span(piece_bytes, window_bytes);
+    DevBuf<uint8_t> d_win((size_t)std::min<uint64_t>(span, total) + 64);
+    DevBuf<unsigned long long> d_wacc(kWindowAccWords);
+    BgzfPieceCompressor comp(cap_blocks, level, true);
+    BgzfPieceTimes bt_times;
+    const double w3 = wall_now();
+
+    FILE* f = fopen(out_file.c_str(), "wb");
+    if (!f) throw Error(SBX_EIO, "cannot write " + out_file.path);
+    out_file.arm();
+    bool ok = true;
+    EventTimer t_s;
+    try {
+        for (const sortc::Window& w : windows) {
+            SBX_HIP(hipMemsetAsync(d_wacc.p, 0, kWindowAccWords * sizeof(unsigned long long), s));
+            if (w.w0 < hlen) SBX_HIP(hipMemcpyAsync(d_win.p, header.data() + w.w0, std::min<uint64_t>(hlen, w.w1) - w.w0, hipMemcpyHostToDevice, s));
+            for (size_t b = 0; b < saved.size(); ++b) {
+                const SavedBatch& sb = saved[b];
+                if (!sortc::span_meets_window(span_lo[b], span_hi[b], w.w0, w.w1)) { ++ss.n_batches_skipped; continue; }
+                ++ss.n_batch_runs;
+                run_record_batch(c.get(), sb, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+                    if (nrec != sb.nrec || base != sb.base || next != sb.next)
+                        throw Error(SBX_EIO, "the input changed while its duplicates were being marked (a batch of the read pass holds other records than before)");
+                    MdScatterArgs a{};
+                    a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base; a.first = sb.first_kept;
+                    a.dest = d_dest.p; a.len = d_len.p; a.out_len = d_out_len.p; a.hi = d_hi.p;
+                    a.w0 = w.w0; a.w1 = w.w1; a.window = d_win.p; a.acc = d_wacc.p;
+                    t_s.start(s);
+                    launch_md_window_scatter(a, s);
+                    t_s.stop(s);
+                    // (the next batch's K1 / K2 overwrite U and the descriptors: K10f ends first)
+                    SBX_HIP(hipStreamSynchronize(s));
+                    ss.ms_scatter += t_s.ms();
+                    ss.ms_inflate_replay += c->stats.ms_inflate;
+                    ss.ms_index_replay += c->stats.ms_index;
+                    return true;
+                });
+            }
+            unsigned long long wacc[kWindowAccWords] = {0, 0};
+            SBX_HIP(hipMemcpyAsync(wacc, d_wacc.p, sizeof wacc, hipMemcpyDeviceToHost, s));
+            SBX_HIP(hipStreamSynchronize(s));
+            std::string why = sortc::window_refusal(w.w0, w.w1, hlen, wacc[kWindowAccBytes], wacc[kWindowAccMismatch]);
+            if (!why.empty()) {
+                // (the check and its figures are the windowed sort's; the words are this command's)
+                static const char* const subs[][2] = {{"while it was being sorted", "while its duplicates were being marked"},
+                                                      {"of the sorted stream", "of the output stream"},
+                                                      {"the keys were taken from", "the key pass read"}};
+                for (const auto& sub : subs) {
+                    const size_t at = why.find(sub[0]);
+                    if (at != std::string::npos) why.replace(at, strlen(sub[0]), sub[1]);
+                }
+                throw Error(SBX_EIO, why);
+            }
+            comp.run((size_t)(w.w1 - w.w0), false, &bt_times,
+                     [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
+                         SBX_HIP(hipMemcpyAsync(d_in, d_win.p + done, bytes, hipMemcpyDeviceToDevice, ps));
+                     },
+                     [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
+        }
+    } catch (...) { fclose(f); throw; }
+    ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
+    if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out_file.path);
+    out_file.disarm();
+    const double w4 = wall_now();
+
+    st.ms_gather = ss.ms_plan + ss.ms_scatter;
+    st.n_records_in = n; st.n_records_out = n_out;
+    st.n_end_pairs = n_pairs; st.n_single_ends = n_single; st.n_unmatched_pairs = acc[kMdAccUnmatched]; st.n_duplicates = acc[kMdAccDup];
+    st.inflated_bytes = u_total; st.stream_bytes = total; st.compressed_bytes = bt_times.out_bytes + 28;
+    st.n_sort_passes = n_passes; st.n_batches = n_batches;
+    st.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+    st.ms_total_wall = (w4 - w0) * 1e3;
+    ss.n_windows = (uint32_t)windows.size();
+    ss.window_bytes = span; ss.key_store_bytes = key_bytes; ss.n_key_records = n_pairable;
+    if (getenv("SBX_TIMING")) {
+        fprintf(stderr, "[sbx] output: stream_bytes=%llu compressed_bytes=%llu n_pieces=%u piece_blocks=%llu\n", (unsigned long long)total,
+                (unsigned long long)st.compressed_bytes, bt_times.n_pieces, (unsigned long long)piece_blocks);
+        fprintf(stderr, "[sbx] markdup-stream: n_windows=%u window_bytes=%llu n_batch_runs=%u n_batches_skipped=%u key_store_bytes=%llu "
+                        "n_key_records=%llu ms_keys=%.2f ms_plan=%.2f ms_scatter=%.2f ms_inflate_replay=%.2f ms_index_replay=%.2f\n",
+                ss.n_windows, (unsigned long long)ss.window_bytes, ss.n_batch_runs, ss.n_batches_skipped, (unsigned long long)ss.key_store_bytes,
+                (unsigned long long)ss.n_key_records, ss.ms_keys, ss.ms_plan, ss.ms_scatter, ss.ms_inflate_replay, ss.ms_index_replay);
+        print_markdup_line(st, (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
+    }
+    if (stats) *stats = st;
+    if (stream_stats) {
+        ss.struct_size = stream_stats->struct_size;
+        memcpy(stream_stats, &ss, sizeof ss);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -65,50 +449,64 @@ int sbx_markdup_header_text(const char* text, size_t n, const char* pg_command_l
     return copy_to_caller(t, out, cap, out_len);
 }
 
-int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates, int level, const char* pg_command_line, int device,
-                sbx_markdup_stats* stats, char* err, size_t errlen) {
+int sbx_markdup_run(const char* in_path, const char* out_path, int remove_duplicates, int level, const char* pg_command_line, int device,
+                    sbx_markdup_stats* stats, sbx_markdup_stream_stats* stream_stats, char* err, size_t errlen) {
     return run_entry(err, errlen, [&] {
         if (!in_path || !out_path) throw Error(SBX_EINVAL, "null argument");
+        if (stream_stats) {
+            if (stream_stats->struct_size < sizeof(sbx_markdup_stream_stats))
+                throw Error(SBX_EINVAL, "sbx_markdup_stream_stats: struct_size " + std::to_string(stream_stats->struct_size) + " is smaller than the struct");
+            const uint32_t size = stream_stats->struct_size;                 // the resident path: everything else is 0
+            memset(stream_stats, 0, sizeof *stream_stats);
+            stream_stats->struct_size = size;
+        }
         check_level(level);
         refuse_overwrite(in_path, out_path);
         const double w0 = wall_now();
         Standalone c = open_record_pass(in_path, device, nullptr, false);
         OutputGuard out_file(out_path);
-        const int32_t n_ref = (int32_t)c->hdr.refs.size();
+        MdJob job;
+        const int32_t n_ref = job.n_ref = (int32_t)c->hdr.refs.size();
         std::string text, why;
         if (!mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why)) throw Error(SBX_EFORMAT, "SAM header: " + why);
-        const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
+        job.header = bam_header_bytes(text, c->hdr.refs);
+        const std::vector<uint8_t>& header = job.header;
         const uint64_t hlen = header.size();
 
         // read groups -> libraries
         sortc::ParsedHeader ph;
         sortc::parse_header(c->hdr.text.data(), c->hdr.text.size(), &ph, nullptr);
-        std::vector<int32_t> library_of;
-        const int32_t n_lib = mdc::read_group_libraries(ph, &library_of);
+        const int32_t n_lib = mdc::read_group_libraries(ph, &job.library_of);
         if (!mdc::key_fits(n_lib, n_ref))
             throw Error(SBX_EUNSUPPORTED, std::to_string(n_lib) + " libraries and " + std::to_string(n_ref) + " references do not fit the 64-bit position key");
-        const uint32_t ref_bits = mdc::ref_bits_of(n_ref);
-        std::string rg_ids;
-        std::vector<uint32_t> rg_off;
-        for (const sortc::HeaderLine& l : ph.rg) { rg_off.push_back((uint32_t)rg_ids.size()); rg_ids += l.id; rg_ids.push_back('\0'); }
-        uint64_t hash_mask = ~0ull;
+        const uint32_t ref_bits = job.ref_bits = mdc::ref_bits_of(n_ref);
+        for (const sortc::HeaderLine& l : ph.rg) { job.rg_off.push_back((uint32_t)job.rg_ids.size()); job.rg_ids += l.id; job.rg_ids.push_back('\0'); }
         if (const char* e = getenv("SBX_MARKDUP_HASH_BITS")) {
             const unsigned long b = strtoul(e, nullptr, 10);
-            if (b < 64) hash_mask = (1ull << b) - 1ull;
+            if (b < 64) job.hash_mask = (1ull << b) - 1ull;
         }
+        const uint64_t hash_mask = job.hash_mask;
 
-        const StorePlan plan = plan_record_store(c.get(), hlen, 96, "marking the duplicates of");
+        // The records stay on the device when they fit; otherwise (or when the hook says so) the file is streamed.
+        const uint64_t hook = markdup_window_hook();
+        StorePlan plan{};
+        bool streamed = hook != 0;
+        if (!streamed) {
+            try {
+                plan = plan_record_store(c.get(), hlen, 96, "marking the duplicates of");
+            } catch (const Error& e) {
+                if (e.code != SBX_ENOMEM) throw;
+                streamed = true;
+            }
+        }
+        if (streamed) {
+            markdup_streamed(c, out_file, job, remove_duplicates != 0, level, hook, w0, stats, stream_stats);
+            return;
+        }
         const uint64_t u_first = plan.u_first;
         hipStream_t s = c->stream.get();
         DevBuf<uint8_t> d_store((size_t)plan.store_bytes + 64);
-        DevBuf<char> d_rg_ids(rg_ids.size() + 1);
-        DevBuf<uint32_t> d_rg_off(rg_off.size() + 1);
-        DevBuf<int32_t> d_rg_lib(library_of.size() + 1);
-        if (!rg_off.empty()) {
-            SBX_HIP(hipMemcpyAsync(d_rg_ids.p, rg_ids.data(), rg_ids.size(), hipMemcpyHostToDevice, s));
-            SBX_HIP(hipMemcpyAsync(d_rg_off.p, rg_off.data(), rg_off.size() * 4, hipMemcpyHostToDevice, s));
-            SBX_HIP(hipMemcpyAsync(d_rg_lib.p, library_of.data(), library_of.size() * 4, hipMemcpyHostToDevice, s));
-        }
+        job.upload(s);
         DevBuf<uint64_t> d_off, d_pos_key, d_hash;
         DevBuf<uint32_t> d_len, d_score, d_rg_at;
         DevBuf<uint8_t> d_cls;
@@ -141,7 +539,7 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
             a.n_ref = n_ref; a.ref_bits = ref_bits; a.hash_mask = hash_mask;
             a.store_delta = (int64_t)base - (int64_t)u_first;
             a.out_base = n;
-            a.lib = LibTable{d_rg_ids.p, d_rg_off.p, d_rg_lib.p, (int32_t)rg_off.size()};
+            a.lib = job.table();
             a.r = MdRecords{d_off.p, d_len.p, d_cls.p, d_pos_key.p, d_score.p, d_hash.p, d_rg_at.p};
             a.acc = d_acc.p;
             launch_md_ends(a, s);
@@ -184,30 +582,9 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
 
         // ---- K10c: pair groups, fragment groups; K10d ----
         t_groups.start(s);
-        DevBuf<uint32_t> d_first((size_t)n_pairable / 2 + 2);
-        const uint64_t n_pairs = compact(kMdPredPairFirst, d_cls.p, d_mate.p, n, d_cnt, d_base, d_first.p, s);
-        DevBuf<uint64_t> d_w0((size_t)n_pairs + 2), d_w1((size_t)n_pairs + 2), d_w2((size_t)n_pairs + 2), d_end2((size_t)n_pairs + 2);
-        launch_md_pair_keys(d_first.p, d_mate.p, n_pairs, r, ref_bits, d_w0.p, d_w1.p, d_w2.p, d_end2.p, s);
-        launch_iota(sorter.idx(), n_pairs, s);
-        sorter.sort_by(d_w2.p, n_pairs, d_acc.p, s);
-        sorter.sort_by(d_w1.p, n_pairs, d_acc.p, s);
-        sorter.sort_by(d_w0.p, n_pairs, d_acc.p, s);
-        launch_md_pair_dups(sorter.idx(), d_w0.p, d_w1.p, n_pairs, d_first.p, d_mate.p, d_dup.p, s);
-        d_w1.release(); d_w2.release();
-        uint64_t n_single = 0;
-        {
-            DevBuf<uint32_t> d_single((size_t)(n - 2 * n_pairs) + 2);
-            n_single = compact(kMdPredSingle, d_cls.p, d_mate.p, n, d_cnt, d_base, d_single.p, s);
-            const uint64_t m = 2 * n_pairs + n_single;
-            DevBuf<uint64_t> d_v0((size_t)m + 2), d_v1((size_t)m + 2);
-            DevBuf<uint32_t> d_rec((size_t)m + 2);
-            launch_md_single_entries(d_w0.p, d_end2.p, n_pairs, d_single.p, n_single, r, d_v0.p, d_v1.p, d_rec.p, d_acc.p, s);
-            launch_iota(sorter.idx(), m, s);
-            sorter.sort_by(d_v1.p, m, d_acc.p, s);
-            sorter.sort_by(d_v0.p, m, d_acc.p, s);
-            launch_md_single_dups(sorter.idx(), d_v0.p, d_v1.p, d_rec.p, m, d_dup.p, s);
-            SBX_HIP(hipStreamSynchronize(s));
-        }
+        uint64_t n_pairs = 0, n_single = 0;
+        GroupBuffers groups;
+        mark_groups(r, n, n_pairable, d_mate.p, ref_bits, sorter, d_cnt, d_base, d_acc.p, d_dup.p, s, groups, &n_pairs, &n_single);
         launch_md_patch_flags(d_store.p, d_off.p, d_dup.p, n, remove_duplicates ? 1u : 0u, d_keep.p, d_acc.p, s);
         // the records that are written, in file order
         DevBuf<uint32_t> d_perm((size_t)n + 2);
@@ -220,7 +597,8 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
         st.ms_groups = t_groups.ms();
         const uint32_t n_passes = sorter.passes;
         sorter = WordSorter();
-        d_w0.release(); d_end2.release(); d_first.release(); d_mate.release(); d_dup.release(); d_keep.release();
+        groups = GroupBuffers();
+        d_mate.release(); d_dup.release(); d_keep.release();
         d_pos_key.release(); d_score.release(); d_rg_at.release(); d_cls.release();
 
         // ---- the output ----
@@ -235,18 +613,14 @@ int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates
         st.n_sort_passes = n_passes; st.n_batches = n_batches;
         st.ms_deflate = w.ms_deflate;
         st.ms_total_wall = (w4 - w0) * 1e3;
-        if (getenv("SBX_TIMING"))
-            fprintf(stderr, "[sbx] markdup: n_records_in=%llu n_records_out=%llu n_end_pairs=%llu n_single_ends=%llu n_unmatched_pairs=%llu "
-                            "n_duplicates=%llu inflated_bytes=%llu stream_bytes=%llu compressed_bytes=%llu n_sort_passes=%u n_batches=%u "
-                            "ms_inflate=%.2f ms_index=%.2f ms_ends=%.2f ms_pairing=%.2f ms_groups=%.2f ms_gather=%.2f ms_deflate=%.2f "
-                            "ms_total_wall=%.1f (open %.1f, read pass %.1f, duplicates %.1f, write %.1f)\n",
-                    (unsigned long long)st.n_records_in, (unsigned long long)st.n_records_out, (unsigned long long)st.n_end_pairs,
-                    (unsigned long long)st.n_single_ends, (unsigned long long)st.n_unmatched_pairs, (unsigned long long)st.n_duplicates,
-                    (unsigned long long)st.inflated_bytes, (unsigned long long)st.stream_bytes, (unsigned long long)st.compressed_bytes,
-                    st.n_sort_passes, st.n_batches, st.ms_inflate, st.ms_index, st.ms_ends, st.ms_pairing, st.ms_groups, st.ms_gather, st.ms_deflate,
-                    st.ms_total_wall, (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
+        if (getenv("SBX_TIMING")) print_markdup_line(st, (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
         if (stats) *stats = st;
     });
+}
+
+int sbx_markdup(const char* in_path, const char* out_path, int remove_duplicates, int level, const char* pg_command_line, int device,
+                sbx_markdup_stats* stats, char* err, size_t errlen) {
+    return sbx_markdup_run(in_path, out_path, remove_duplicates, level, pg_command_line, device, stats, nullptr, err, errlen);
 }
 
 }  // extern "C"

@@ -16,8 +16,8 @@
 // destinations per batch (K9d-2); then, for every window of whole pieces of the stream that fits the device, the batches whose span
 // meets the window are run again (run_record_batch: the same K1 + K2, the same U and descriptors) and K9d-3 scatters their records
 // into the window, which goes through the same encoder to the file.  No temporary file and no merge; the file is the resident
-// path's byte for byte.  The name orders, sbx_markdup, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins stay resident
-// and refuse with SBX_ENOMEM what does not fit.
+// path's byte for byte.  The name orders, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins stay resident and refuse with
+// SBX_ENOMEM what does not fit; sbx_markdup has a path of its own kind (engine_markdup.cpp: the output is in input order).
 //
 // sbx_sort_bam_by_name (`sambamba sort -n / -N`, with or without -M) is the same call with another order: next to K9a, K14a
 // (namesort.hip) builds the key of every kept record's name in a key store of 64-bit words, and the order is an LSD sort over those
@@ -142,11 +142,6 @@ uint64_t window_bytes_hook() {
     return *end ? 0 : (uint64_t)v;
 }
 
-// Inflated bytes per batch of the windowed sort.  The batch buffers (~5 x this) stay allocated from the key pass to the last window
-// and are taken from what the windows could have: a batch is kept small against a window, and a short batch has a narrow span of
-// destinations, which is what lets a window skip it.  K1 + K2 run at ~300 GB/s of inflated bytes (README), so 2 GiB is ~7 ms of
-// kernels per batch -- far above the cost of launching them.
-constexpr uint64_t kWindowedBatchBytes = 2ull << 30;
 constexpr uint64_t kWindowedPerRecord = 36;     // bytes per record while the keys are sorted: key, key2, len, val, val2, dest / out_off
 
 // The coordinate sort of a file whose records do not stay on the device (or SBX_SORT_WINDOW_BYTES): the keys of the whole file are

@@ -84,6 +84,12 @@ inline void copy_batch_to_store(sbx_ctx* c, uint8_t* d_store, uint64_t u_first, 
     if (next > cur) SBX_HIP(hipMemcpyAsync(d_store + (cur - u_first), c->U() + (cur - base), next - cur, hipMemcpyDeviceToDevice, s));
 }
 
+// Inflated bytes per batch of the paths that keep no record store (the windowed sort, the streamed markdup).  The batch buffers
+// (~5 x this) stay allocated from the key pass to the last window and are taken from what the windows could have: a batch is kept
+// small against a window, and a short batch has a narrow span of destinations, which is what lets a window skip it.  K1 + K2 run at
+// ~300 GB/s of inflated bytes (README), so 2 GiB is ~7 ms of kernels per batch -- far above the cost of launching them.
+constexpr uint64_t kWindowedBatchBytes = 2ull << 30;
+
 // ---- K9b over the keys of the resident records ----
 struct ResidentOrder {
     DevBuf<uint64_t> key2;          // the second key buffer; free for the output offsets once the sort is done

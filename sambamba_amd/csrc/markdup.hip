@@ -15,9 +15,16 @@
 //                           a fragment is a duplicate <=> it is not the first entry of its position.  Both tests look at the
 //                           neighbour in sorted order only: a group may be of any size.
 //   K10d k_md_patch_flags   the flag of every record in the store gets 0x400 set or cleared, byte stores at any address.
+// The streamed path (a file whose records do not stay on the device; engine_markdup.cpp) has no record store:
+//   K10e k_md_key_measure / per batch, next to K10a: the flag of every record as read, and for every pairable record the bytes K10b
+//        k_md_key_emit      compares -- l_read_name, the name, the RG value, NUL (markdup_core.hpp) -- in a compact key store; K10b
+//                           runs over those entries (k_md_pair_runs<true>).
+//        k_md_out_plan      flag as read + duplicate bit -> the high flag byte to write and the length in the output (0: dropped).
+//   K10f k_md_window_scatter  the records of a replayed batch go to their place in a window of the output stream, byte 19 patched.
 #include "common.hpp"
 #include "markdup.hpp"
 #include "markdup_core.hpp"
+#include "sort.hpp"
 #include "wave_prims.hpp"
 
 namespace sbx {
@@ -168,6 +175,13 @@ __device__ bool md_same_key(const uint8_t* store, const MdRecords& r, uint32_t x
     }
 }
 
+// the key store's reader of the same comparison (the streamed path): the entries K10e wrote, r.off[record] their offsets
+__device__ bool md_same_entry(const uint8_t* keys, const MdRecords& r, uint32_t x, uint32_t y) {
+    return mdc::pair_keys_equal(keys + r.off[x], keys + r.off[y]);
+}
+
+// kKeyStore: `store` is the key store and md_same_entry compares; otherwise the record store and md_same_key
+template <bool kKeyStore>
 __global__ __launch_bounds__(kMdThreads) void k_md_pair_runs(const uint64_t* __restrict__ hash, const uint32_t* __restrict__ rec, uint64_t n,
                                                              const uint8_t* __restrict__ store, MdRecords r, uint32_t* mate) {
     const uint64_t j = (uint64_t)blockIdx.x * kMdThreads + threadIdx.x;
@@ -182,7 +196,7 @@ __global__ __launch_bounds__(kMdThreads) void k_md_pair_runs(const uint64_t* __r
         if (mate[rx] != kMdNone) continue;
         for (uint64_t y = x + 1; y < e; ++y) {
             const uint32_t ry = rec[y];
-            if (mate[ry] != kMdNone || !md_same_key(store, r, rx, ry)) continue;
+            if (mate[ry] != kMdNone || !(kKeyStore ? md_same_entry(store, r, rx, ry) : md_same_key(store, r, rx, ry))) continue;
             mate[rx] = ry;
             mate[ry] = rx;
             break;
@@ -254,15 +268,116 @@ __global__ __launch_bounds__(kMdThreads) void k_md_patch_flags(uint8_t* __restri
     bool marked = false;
     if (i < n) {
         uint8_t* f = store + off[i] + 18;                 // flag: bytes 18-19 of the record, block_size included
-        uint32_t flag = f[0] | (uint32_t)f[1] << 8;
         marked = dup[i] != 0;
-        if (marked) flag |= 0x400u;
-        else if (!(flag & 0x900u)) flag &= ~0x400u;
+        const uint32_t flag = mdc::flag_after(f[0] | (uint32_t)f[1] << 8, marked);
         f[1] = (uint8_t)(flag >> 8);                      // (0x400 lives in the high byte)
-        keep[i] = !(remove && (flag & 0x400u));
+        keep[i] = mdc::kept(flag, remove != 0);
     }
     const unsigned long long m = __ballot(marked);
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(acc + kMdAccDup, (unsigned long long)__popcll(m));
+}
+
+// ---- K10e: the key store of the streamed path ---------------------------------------------------------------------------------
+// Nothing is read that K10a's checks did not cover: a record K10a refused has len 0 and is left alone; the flag lies in the fixed
+// part; the RG value was found terminated inside the record (find_rg), and the walk to its NUL stops at the record's end anyway.
+__global__ __launch_bounds__(kMdThreads) void k_md_key_measure(MdKeyArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kMdThreads + threadIdx.x;
+    if (i >= a.n) return;
+    const uint64_t at = a.out_base + i;
+    const uint32_t len = a.r.len[at];
+    uint32_t flag = 0, klen = 0;
+    if (len) {
+        const uint8_t* p = a.U + a.desc[i].rec_off;
+        flag = p[18] | (uint32_t)p[19] << 8;
+        if (a.r.cls[at] == kMdPairable) {
+            const uint32_t rg_at = a.r.rg_at[at];
+            uint32_t rg_len = 0;
+            if (rg_at) while (rg_at + rg_len < len && p[rg_at + rg_len]) ++rg_len;
+            klen = mdc::pair_key_len(p[12], rg_len);
+        }
+    }
+    a.flag[at] = (uint16_t)flag;
+    a.key_len[i] = klen;
+}
+
+__global__ __launch_bounds__(kMdThreads) void k_md_key_emit(MdKeyArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * (kMdThreads / kCopyGroup) + threadIdx.x / kCopyGroup;
+    const uint32_t l = threadIdx.x % kCopyGroup;
+    if (i >= a.n) return;
+    const uint32_t klen = a.key_len[i];
+    if (!klen) return;
+    const uint64_t at = a.out_base + i, ko = a.key_off[i];
+    const uint8_t* p = a.U + a.desc[i].rec_off;
+    const uint32_t l_name = p[12], rg_at = a.r.rg_at[at], rg_len = klen - 2u - l_name;
+    uint8_t* dst = a.key_store + ko;
+    for (uint32_t k = l; k < klen; k += kCopyGroup) dst[k] = mdc::pair_key_byte(p, l_name, rg_at, rg_len, k);
+    if (l == 0) a.r.off[at] = ko;
+}
+
+// ---- the output plan of the streamed path -----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMdThreads) void k_md_out_plan(const uint16_t* __restrict__ flag, const uint8_t* __restrict__ dup,
+                                                            const uint32_t* __restrict__ len, uint64_t n, uint32_t remove,
+                                                            uint8_t* __restrict__ hi, uint32_t* __restrict__ out_len,
+                                                            unsigned long long* __restrict__ acc) {
+    __shared__ uint32_t wsum[kMdThreads / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * kMdThreads + threadIdx.x;
+    uint32_t marked = 0, keep = 0;
+    if (i < n) {
+        marked = dup[i] != 0;
+        const uint32_t f = mdc::flag_after(flag[i], marked != 0);
+        keep = mdc::kept(f, remove != 0);
+        hi[i] = (uint8_t)(f >> 8);
+        out_len[i] = keep ? len[i] : 0u;
+    }
+    const uint32_t n_marked = block_sum(marked, wsum), n_keep = block_sum(keep, wsum);
+    if (threadIdx.x == 0) {
+        if (n_marked) atomicAdd(acc + kMdAccDup, (unsigned long long)n_marked);
+        if (n_keep) atomicAdd(acc + kMdAccKept, (unsigned long long)n_keep);
+    }
+}
+
+// ---- K10f -------------------------------------------------------------------------------------------------------------------------
+// Sixteen lanes per record, kMdScatterRounds records per lane group: in every round the sixteen groups of a workgroup move sixteen
+// consecutive records, whose destinations ascend with the record number, so the workgroup's stores are adjacent.  The two counts are
+// summed over the workgroup (block_sum) and cost one atomic each per 64 records -- K9d-3 issues one per wave, four records.
+constexpr uint32_t kMdScatterThreads = 256, kMdScatterGroups = kMdScatterThreads / kCopyGroup, kMdScatterRounds = 4;
+constexpr uint32_t kMdScatterRecs = kMdScatterGroups * kMdScatterRounds;
+
+__global__ __launch_bounds__(kMdScatterThreads) void k_md_window_scatter(MdScatterArgs a) {
+    __shared__ unsigned long long wsum[kMdScatterThreads / 64];
+    const uint32_t g = threadIdx.x / kCopyGroup, l = threadIdx.x % kCopyGroup;
+    unsigned long long wrote = 0, bad_n = 0;
+    for (uint32_t round = 0; round < kMdScatterRounds; ++round) {
+        const uint64_t i = (uint64_t)blockIdx.x * kMdScatterRecs + round * kMdScatterGroups + g;
+        if (i >= a.n) break;
+        const uint64_t rec_off = a.desc[i].rec_off, ord = a.first + i;
+        // the record as it is in THIS pass: its frame bounds the loads, the clip of [dest, dest + its length) the stores
+        bool bad = rec_off + 4 > a.u_end;
+        uint32_t bs = 0;
+        if (!bad) { bs = ld32(a.U + rec_off); bad = !record_len_ok(bs, rec_off, a.u_end); }
+        const uint64_t len = (uint64_t)bs + 4u;
+        bad = bad || len != a.len[ord];
+        const uint32_t out_len = a.out_len[ord];
+        sortc::PieceClip c;
+        const uint64_t d = a.dest[ord];
+        if (!bad && out_len && sortc::clip_to_piece(d, d + len, a.w0, a.w1, &c)) {
+            // bytes [s0, s1) of the record go to dst[0 ..): what lies in front of byte 19, byte 19 patched, what lies behind it
+            const uint8_t* src = a.U + rec_off;
+            uint8_t* dst = a.window + c.dst;
+            const uint64_t s0 = c.src, s1 = c.src + c.len;
+            if (s0 < 19) { const uint64_t e = s1 < 19 ? s1 : 19; copy_span16(dst, src + s0, e - s0, l); }
+            if (l == 0 && s0 <= 19 && 19 < s1) dst[19 - s0] = a.hi[ord];
+            if (s1 > 20) { const uint64_t b = s0 > 20 ? s0 : 20; copy_span16(dst + (b - s0), src + b, s1 - b, l); }
+            if (l == 0) wrote += c.len;
+        }
+        if (l == 0 && bad) ++bad_n;
+    }
+    wrote = block_sum(wrote, wsum);
+    bad_n = block_sum(bad_n, wsum);
+    if (threadIdx.x == 0) {
+        if (wrote) atomicAdd(a.acc + kWindowAccBytes, wrote);
+        if (bad_n) atomicAdd(a.acc + kWindowAccMismatch, bad_n);
+    }
 }
 
 template <class... A, class... B>
@@ -291,7 +406,12 @@ void launch_md_gather_keys(const uint64_t* d_word, const uint32_t* d_idx, uint64
 
 void launch_md_pair_runs(const uint64_t* d_hash, const uint32_t* d_rec, uint64_t n, const uint8_t* d_store, const MdRecords& r, uint32_t* d_mate,
                          hipStream_t stream) {
-    md_launch(k_md_pair_runs, n, stream, d_hash, d_rec, n, d_store, r, d_mate);
+    md_launch(k_md_pair_runs<false>, n, stream, d_hash, d_rec, n, d_store, r, d_mate);
+}
+
+void launch_md_pair_runs_keys(const uint64_t* d_hash, const uint32_t* d_rec, uint64_t n, const uint8_t* d_key_store, const MdRecords& r,
+                              uint32_t* d_mate, hipStream_t stream) {
+    md_launch(k_md_pair_runs<true>, n, stream, d_hash, d_rec, n, d_key_store, r, d_mate);
 }
 
 void launch_md_pair_keys(const uint32_t* d_first, const uint32_t* d_mate, uint64_t n_pairs, const MdRecords& r, uint32_t ref_bits, uint64_t* d_w0,
@@ -317,6 +437,26 @@ void launch_md_single_dups(const uint32_t* d_perm, const uint64_t* d_v0, const u
 void launch_md_patch_flags(uint8_t* d_store, const uint64_t* d_off, const uint8_t* d_dup, uint64_t n, uint32_t remove, uint8_t* d_keep,
                            unsigned long long* d_acc, hipStream_t stream) {
     md_launch(k_md_patch_flags, n, stream, d_store, d_off, d_dup, n, remove, d_keep, d_acc);
+}
+
+void launch_md_key_measure(const MdKeyArgs& a, hipStream_t stream) { md_launch(k_md_key_measure, a.n, stream, a); }
+
+void launch_md_key_emit(const MdKeyArgs& a, hipStream_t stream) {
+    if (!a.n) return;
+    const uint64_t per_group = kMdThreads / kCopyGroup;
+    hipLaunchKernelGGL(k_md_key_emit, dim3((uint32_t)((a.n + per_group - 1) / per_group)), dim3(kMdThreads), 0, stream, a);
+    SBX_HIP(hipGetLastError());
+}
+
+void launch_md_out_plan(const uint16_t* d_flag, const uint8_t* d_dup, const uint32_t* d_len, uint64_t n, uint32_t remove, uint8_t* d_hi,
+                        uint32_t* d_out_len, unsigned long long* d_acc, hipStream_t stream) {
+    md_launch(k_md_out_plan, n, stream, d_flag, d_dup, d_len, n, remove, d_hi, d_out_len, d_acc);
+}
+
+void launch_md_window_scatter(const MdScatterArgs& a, hipStream_t stream) {
+    if (!a.n || a.w1 <= a.w0) return;
+    hipLaunchKernelGGL(k_md_window_scatter, dim3((uint32_t)((a.n + kMdScatterRecs - 1) / kMdScatterRecs)), dim3(kMdScatterThreads), 0, stream, a);
+    SBX_HIP(hipGetLastError());
 }
 
 }  // namespace sbx

@@ -98,6 +98,39 @@ SBX_SORT_HD void pair_words(uint64_t key_a, uint32_t score_a, uint64_t key_b, ui
 // second word of a single end: markers and unmatched paired reads (0) in front of the fragments, those by descending score
 SBX_SORT_HD uint64_t single_word(bool fragment, uint32_t score) { return fragment ? kFragmentBit | (uint32_t)~score : 0ull; }
 
+// ---- the flag rule (markdup.d:1286-1298), in one place: K10d, the streamed path's output plan and the CPU test use these ----
+// the flag a record is written with: a marked record gets 0x400; an unmarked one loses it unless it is secondary or supplementary
+SBX_SORT_HD uint32_t flag_after(uint32_t flag, bool dup) {
+    if (dup) return flag | 0x400u;
+    return (flag & 0x900u) ? flag : flag & ~0x400u;
+}
+// is a record with that resulting flag written?  (-r drops whatever carries 0x400, a secondary record that came with it included)
+SBX_SORT_HD bool kept(uint32_t flag_after_, bool remove) { return !(remove && (flag_after_ & 0x400u)); }
+
+// ---- the key store of the streamed path (K10e): what K10b compares of a pairable record, without the record ----
+// An entry is  l_read_name (one byte) | the l_read_name bytes of the name | the RG:Z value | NUL  -- an absent RG is the NUL alone, so
+// absent equals empty, as in the resident comparison.  The leading length byte makes two entries equal exactly when the resident
+// comparison (same l_read_name, same name bytes, same RG string) says so -- also for a name that lacks its NUL or holds one inside,
+// where name bytes and RG bytes could otherwise change places.  It also makes an entry self-describing: no array of lengths is kept.
+// rec: the record from its block_size on; rg_at: offset of the RG:Z value in it (0: none); rg_len: its length without the NUL.
+SBX_SORT_HD uint32_t pair_key_len(uint32_t l_name, uint32_t rg_len) { return 1u + l_name + rg_len + 1u; }
+SBX_SORT_HD uint8_t pair_key_byte(const uint8_t* rec, uint32_t l_name, uint32_t rg_at, uint32_t rg_len, uint32_t k) {
+    if (k == 0) return (uint8_t)l_name;
+    if (k <= l_name) return rec[36u + k - 1u];
+    const uint32_t j = k - 1u - l_name;
+    return (rg_at && j < rg_len) ? rec[rg_at + j] : (uint8_t)0;
+}
+// two entries of the key store: same length and same bytes (the RG part ends at the entry's own NUL)
+SBX_SORT_HD bool pair_keys_equal(const uint8_t* p, const uint8_t* q) {
+    const uint32_t ln = p[0];
+    if (ln != q[0]) return false;
+    for (uint32_t k = 1; k <= ln; ++k) if (p[k] != q[k]) return false;
+    for (uint32_t k = ln + 1u;; ++k) {
+        if (p[k] != q[k]) return false;
+        if (!p[k]) return true;
+    }
+}
+
 }  // namespace mdc
 }  // namespace sbx
 
