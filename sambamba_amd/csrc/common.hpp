@@ -8,18 +8,12 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
-#include "../../include/sbx_depth.h"
+#include "entry_util.hpp"           // (Error, and what else needs no HIP)
 
 namespace sbx {
-
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 #define SBX_HIP(expr)                                                                               \
     do {                                                                                            \

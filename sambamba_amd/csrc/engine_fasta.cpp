@@ -17,15 +17,7 @@ namespace {
 
 // Text bytes per chunk: 64 MiB (import's value; NOT tuned), or SBX_FASTA_CHUNK_BYTES (tests: a decimal number of at least 16, rounded
 // down to a multiple of 16 and capped at fastac::kChunkLimit; anything else counts as unset).  The output does not depend on it.
-uint64_t fasta_chunk_bytes() {
-    constexpr uint64_t kDefault = 64ull << 20;
-    const char* e = getenv("SBX_FASTA_CHUNK_BYTES");
-    if (!e || *e < '0' || *e > '9') return kDefault;
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (*end || v < 16) return kDefault;
-    return std::min<uint64_t>(v & ~15ull, fastac::kChunkLimit);
-}
+uint64_t fasta_chunk_bytes() { return std::min<uint64_t>(env_size("SBX_FASTA_CHUNK_BYTES", 64ull << 20, 16) & ~15ull, fastac::kChunkLimit); }
 
 struct FileCloser {
     FILE* f;
@@ -155,11 +147,9 @@ int sbx_index_fasta(const char* fasta_path, const char* fai_path, int device, sb
         if (carry.failed()) throw Error(SBX_EFORMAT, carry.complaint(fasta_path));
         const std::string text = carry.fai_text();
         OutputGuard out_file(fai_path);
-        FILE* f = fopen(fai_path, "wb");
-        if (!f) throw Error(SBX_EIO, std::string("cannot write ") + fai_path);
-        out_file.arm();
-        const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
-        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + fai_path);
+        OutputFile f(out_file);
+        f.write(text.data(), text.size());
+        f.finish(false);
         out_file.disarm();
         st.n_sequences = carry.recs.size();
         st.n_lines = carry.n_lines;

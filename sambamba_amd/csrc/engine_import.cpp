@@ -16,14 +16,7 @@ namespace {
 
 // Text bytes per chunk: 64 MiB (not tuned), or SBX_IMPORT_CHUNK_BYTES (tests: a decimal number of at least 1; anything else counts
 // as unset).  Chunks are cut at line ends and their records land in the store in order, so the value does not change a byte of the output.
-uint64_t import_chunk_bytes() {
-    constexpr uint64_t kDefault = 64ull << 20;
-    const char* e = getenv("SBX_IMPORT_CHUNK_BYTES");
-    if (!e || *e < '0' || *e > '9') return kDefault;
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    return *end || !v ? kDefault : (uint64_t)v;
-}
+uint64_t import_chunk_bytes() { return env_size("SBX_IMPORT_CHUNK_BYTES", 64ull << 20); }
 
 // The input, read front to back: the bytes between `head` and the end of `buf` are read and not yet handed out.
 struct TextInput {

@@ -15,8 +15,10 @@
 // is written window by window -- the saved batches whose records have a byte in the window are run again (run_record_batch) and K10f
 // puts their records in place with byte 19 patched.  Batches and windows are both consecutive stretches of one ordered stream, so a
 // batch is run again for at most the windows its stretch touches: the file goes through K1 + K2 about twice in all.  The file
-// written is the resident path's byte for byte.
-#include "engine_store.hpp"
+// written is the resident path's byte for byte.  The budget of device memory, the spans of the batches, the choice of the window and
+// the loop over windows and batches are engine_windows.hpp, shared with the windowed sort; what is here is the key pass, the marking,
+// the output plan and the callback that launches K10f.
+#include "engine_windows.hpp"
 #include "markdup.hpp"
 #include "markdup_core.hpp"
 
@@ -143,13 +145,7 @@ void print_markdup_line(const sbx_markdup_stats& st, double open_ms, double read
 
 // SBX_MARKDUP_WINDOW_BYTES (tests, measurements): forces the streamed path with windows of this many bytes, rounded up to whole
 // pieces.  0: unset (or not a positive decimal number).
-uint64_t markdup_window_hook() {
-    const char* e = getenv("SBX_MARKDUP_WINDOW_BYTES");
-    if (!e || *e < '0' || *e > '9') return 0;
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    return *end ? 0 : (uint64_t)v;
-}
+uint64_t markdup_window_hook() { return env_u64("SBX_MARKDUP_WINDOW_BYTES").value_or(0); }
 
 // Bytes of per-record arrays at the peak of the streamed path, which is K10c.  The key pass keeps 39 per record (off 8, len 4, class 1,
 // position key 8, score 4, hash 8, rg_at 4, flag 2); pairing adds mate 4, dup 1 and the hash sort's two (key, index) buffers, 24 per
@@ -166,27 +162,12 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
                       sbx_markdup_stats* stats, sbx_markdup_stream_stats* stream_stats) {
     const std::vector<uint8_t>& header = job.header;
     const uint64_t hlen = header.size();
-    const uint64_t u_total = c->blocks.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
-    const uint64_t piece_blocks = bgzf_piece_blocks(), piece_bytes = piece_blocks * (uint64_t)kBgzfPayload;
-    // the encoder's buffers, as plan_store_bytes reserves them, and the smallest window: one piece, or the whole stream when it is shorter
-    const uint64_t stream_est = u_total - u_first + hlen;
-    const uint64_t cap_bytes = std::min<uint64_t>(piece_bytes, stream_est + kBgzfPayload);
-    const uint64_t out_reserve = cap_bytes * 3 + (8ull << 20);
-    const uint64_t est_records = (u_total - u_first) / 160 + 4096;
-    const uint64_t arrays_est = est_records * kStreamedPerRecord, keys_est = est_records * kStreamedKeyBytes;
-    {
-        size_t free_b = 0, total_b = 0;
-        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t min_batch = 5ull * (64ull << 20);
-        const uint64_t need = arrays_est + keys_est + min_batch + out_reserve + cap_bytes;
-        if (need > free_b)
-            throw Error(SBX_ENOMEM, "the file does not fit the device: marking its duplicates in windows needs " + std::to_string(need) +
-                                        " bytes of device memory (" + std::to_string(arrays_est) + " for the per-record arrays, " + std::to_string(keys_est) +
-                                        " for the key store (an estimate), " + std::to_string(min_batch) + " for one read batch, " +
-                                        std::to_string(out_reserve) + " for the encoder and " + std::to_string(cap_bytes) + " for a window of one piece), " +
-                                        std::to_string(free_b) + " are free");
-    }
-    const uint64_t batch_u = std::min<uint64_t>(index_batch_bytes(arrays_est + keys_est + out_reserve + cap_bytes), kWindowedBatchBytes);
+    WindowBudget budget(c.get(), hlen, sortc::kMarkdupWindowWords, hook);
+    const uint64_t arrays_est = budget.est_records * kStreamedPerRecord, keys_est = budget.est_records * kStreamedKeyBytes;
+    budget.fit(arrays_est + keys_est,
+               std::to_string(arrays_est) + " for the per-record arrays, " + std::to_string(keys_est) + " for the key store (an estimate), " +
+                   std::to_string(WindowBudget::kMinBatch) + " for one read batch, " + std::to_string(budget.out_reserve) +
+                   " for the encoder and " + std::to_string(budget.cap_bytes) + " for a window of one piece");
     hipStream_t s = c->stream.get();
     job.upload(s);
     DevBuf<uint64_t> d_off, d_pos_key, d_hash, d_key_off, d_tile_sum;
@@ -207,7 +188,7 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
     uint32_t n_batches = 0;
     bool too_many = false;
     unsigned long long acc[kMdAccWords] = {0};
-    for_each_record_batch(c.get(), batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+    for_each_record_batch(c.get(), budget.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
         if (n + nrec > 0xFFFFFFF0ull) { too_many = true; return false; }
         const size_t want = (size_t)(n + nrec + 2);
         grow_keeping(d_off, (size_t)n, want, s);
@@ -305,126 +286,49 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
     DevBuf<uint8_t> d_hi((size_t)n + 2);
     DevBuf<uint32_t> d_out_len((size_t)n + 2);
     DevBuf<uint64_t> d_dest((size_t)n + 2);
-    std::vector<uint64_t> span_lo(saved.size(), ~0ull), span_hi(saved.size(), 0);
+    BatchSpans spans;
     uint64_t total = hlen;
     {
-        std::vector<uint64_t> first(saved.size() + 1, n);
-        for (size_t b = 0; b < saved.size(); ++b) first[b] = saved[b].first_kept;
-        DevBuf<uint64_t> d_first(first.size()), d_lo(saved.size() + 1), d_hi_span(saved.size() + 1);
+        spans.upload(saved, n, s);
         d_tile_sum.ensure(len_tiles(n) + 2);
-        SBX_HIP(hipMemcpyAsync(d_first.p, first.data(), first.size() * 8, hipMemcpyHostToDevice, s));
         EventTimer t;
         t.start(s);
         launch_md_out_plan(d_flag.p, d_dup.p, d_len.p, n, remove ? 1u : 0u, d_hi.p, d_out_len.p, d_acc.p, s);
         launch_sorted_offsets(d_out_len.p, nullptr, n, hlen, d_tile_sum.p, d_dest.p, s);
-        launch_batch_spans(d_dest.p, d_out_len.p, d_first.p, (uint32_t)saved.size(), d_lo.p, d_hi_span.p, s);
+        spans.launch(d_dest.p, d_out_len.p, s);
         t.stop(s);
         if (n) SBX_HIP(hipMemcpyAsync(&total, d_dest.p + n, 8, hipMemcpyDeviceToHost, s));
-        if (!saved.empty()) {
-            SBX_HIP(hipMemcpyAsync(span_lo.data(), d_lo.p, saved.size() * 8, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipMemcpyAsync(span_hi.data(), d_hi_span.p, saved.size() * 8, hipMemcpyDeviceToHost, s));
-        }
         SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
+        spans.read_back(s);
         ss.ms_plan = t.ms();
     }
     d_flag.release(); d_dup.release(); d_tile_sum.release(); d_key_len.release(); d_key_off.release();
     const uint64_t n_out = acc[kMdAccKept];
     if (!remove && (n_out != n || total != hlen + acc[kMdAccBytes])) throw Error(SBX_EFORMAT, "internal error: the offsets of the records do not add up");
 
-    // ---- the window: what is free next to the batch buffers (they stay) less the encoder's ----
-    const uint32_t cap_blocks = (uint32_t)std::min<uint64_t>(piece_blocks, std::max<uint64_t>(1, (total + kBgzfPayload - 1) / kBgzfPayload));
-    uint64_t window_bytes = hook;
-    if (!window_bytes) {
-        size_t free_b = 0, total_b = 0;
-        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t reserve = out_reserve + (64ull << 20);
-        const uint64_t avail = free_b > reserve ? free_b - reserve : 0;
-        const uint64_t smallest = std::min<uint64_t>(piece_bytes, total);
-        if (avail < smallest)
-            throw Error(SBX_ENOMEM, "the file does not fit the device: marking its duplicates in windows needs " + std::to_string(smallest + reserve) +
-                                        " bytes of device memory (a window of one piece and the encoder, next to the read batch and 17 bytes per "
-                                        "record), " + std::to_string(free_b) + " are free");
-        window_bytes = std::max<uint64_t>(avail / piece_bytes, 1) * piece_bytes;
-    }
-    const std::vector<sortc::Window> windows = sortc::plan_windows(total, piece_bytes, window_bytes);
-    const uint64_t span = sortc::window_span(piece_bytes, window_bytes);
-    DevBuf<uint8_t> d_win((size_t)std::min<uint64_t>(span, total) + 64);
-    DevBuf<unsigned long long> d_wacc(kWindowAccWords);
-    BgzfPieceCompressor comp(cap_blocks, level, true);
-    BgzfPieceTimes bt_times;
-    const double w3 = wall_now();
-
-    FILE* f = fopen(out_file.c_str(), "wb");
-    if (!f) throw Error(SBX_EIO, "cannot write " + out_file.path);
-    out_file.arm();
-    bool ok = true;
-    EventTimer t_s;
-    try {
-        for (const sortc::Window& w : windows) {
-            SBX_HIP(hipMemsetAsync(d_wacc.p, 0, kWindowAccWords * sizeof(unsigned long long), s));
-            if (w.w0 < hlen) SBX_HIP(hipMemcpyAsync(d_win.p, header.data() + w.w0, std::min<uint64_t>(hlen, w.w1) - w.w0, hipMemcpyHostToDevice, s));
-            for (size_t b = 0; b < saved.size(); ++b) {
-                const SavedBatch& sb = saved[b];
-                if (!sortc::span_meets_window(span_lo[b], span_hi[b], w.w0, w.w1)) { ++ss.n_batches_skipped; continue; }
-                ++ss.n_batch_runs;
-                run_record_batch(c.get(), sb, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-                    if (nrec != sb.nrec || base != sb.base || next != sb.next)
-                        throw Error(SBX_EIO, "the input changed while its duplicates were being marked (a batch of the read pass holds other records than before)");
-                    MdScatterArgs a{};
-                    a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base; a.first = sb.first_kept;
-                    a.dest = d_dest.p; a.len = d_len.p; a.out_len = d_out_len.p; a.hi = d_hi.p;
-                    a.w0 = w.w0; a.w1 = w.w1; a.window = d_win.p; a.acc = d_wacc.p;
-                    t_s.start(s);
-                    launch_md_window_scatter(a, s);
-                    t_s.stop(s);
-                    // (the next batch's K1 / K2 overwrite U and the descriptors: K10f ends first)
-                    SBX_HIP(hipStreamSynchronize(s));
-                    ss.ms_scatter += t_s.ms();
-                    ss.ms_inflate_replay += c->stats.ms_inflate;
-                    ss.ms_index_replay += c->stats.ms_index;
-                    return true;
-                });
-            }
-            unsigned long long wacc[kWindowAccWords] = {0, 0};
-            SBX_HIP(hipMemcpyAsync(wacc, d_wacc.p, sizeof wacc, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipStreamSynchronize(s));
-            std::string why = sortc::window_refusal(w.w0, w.w1, hlen, wacc[kWindowAccBytes], wacc[kWindowAccMismatch]);
-            if (!why.empty()) {
-                // (the check and its figures are the windowed sort's; the words are this command's)
-                static const char* const subs[][2] = {{"while it was being sorted", "while its duplicates were being marked"},
-                                                      {"of the sorted stream", "of the output stream"},
-                                                      {"the keys were taken from", "the key pass read"}};
-                for (const auto& sub : subs) {
-                    const size_t at = why.find(sub[0]);
-                    if (at != std::string::npos) why.replace(at, strlen(sub[0]), sub[1]);
-                }
-                throw Error(SBX_EIO, why);
-            }
-            comp.run((size_t)(w.w1 - w.w0), false, &bt_times,
-                     [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
-                         SBX_HIP(hipMemcpyAsync(d_in, d_win.p + done, bytes, hipMemcpyDeviceToDevice, ps));
-                     },
-                     [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
-        }
-    } catch (...) { fclose(f); throw; }
-    ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
-    if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out_file.path);
+    // ---- the windows: K10f for every saved batch that meets one ----
+    const WindowedOutput w = write_windows(c.get(), out_file, header, total, budget, spans, level, [&](const SavedBatch& sb, const RecordBatch& rb,
+                                           const sortc::Window& win, uint8_t* d_win, unsigned long long* d_wacc, hipStream_t ws) {
+        MdScatterArgs a{};
+        a.U = c->U(); a.desc = c->d_desc.p; a.n = rb.nrec; a.u_end = rb.next - rb.base; a.first = sb.first_kept;
+        a.dest = d_dest.p; a.len = d_len.p; a.out_len = d_out_len.p; a.hi = d_hi.p;
+        a.w0 = win.w0; a.w1 = win.w1; a.window = d_win; a.acc = d_wacc;
+        launch_md_window_scatter(a, ws);
+    });
     out_file.disarm();
-    const double w4 = wall_now();
+    const double w3 = w.w_planned, w4 = w.w_written;
 
+    ss.ms_scatter = w.ms_scatter; ss.ms_inflate_replay = w.ms_inflate_replay; ss.ms_index_replay = w.ms_index_replay;
+    ss.n_windows = w.n_windows; ss.n_batch_runs = (uint32_t)w.n_batch_runs; ss.n_batches_skipped = (uint32_t)w.n_batches_skipped;
     st.ms_gather = ss.ms_plan + ss.ms_scatter;
     st.n_records_in = n; st.n_records_out = n_out;
     st.n_end_pairs = n_pairs; st.n_single_ends = n_single; st.n_unmatched_pairs = acc[kMdAccUnmatched]; st.n_duplicates = acc[kMdAccDup];
-    st.inflated_bytes = u_total; st.stream_bytes = total; st.compressed_bytes = bt_times.out_bytes + 28;
+    st.inflated_bytes = budget.u_total; st.stream_bytes = total; st.compressed_bytes = w.compressed_bytes;
     st.n_sort_passes = n_passes; st.n_batches = n_batches;
-    st.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+    st.ms_deflate = w.ms_deflate;
     st.ms_total_wall = (w4 - w0) * 1e3;
-    ss.n_windows = (uint32_t)windows.size();
-    ss.window_bytes = span; ss.key_store_bytes = key_bytes; ss.n_key_records = n_pairable;
+    ss.window_bytes = w.span; ss.key_store_bytes = key_bytes; ss.n_key_records = n_pairable;
     if (getenv("SBX_TIMING")) {
-        fprintf(stderr, "[sbx] output: stream_bytes=%llu compressed_bytes=%llu n_pieces=%u piece_blocks=%llu\n", (unsigned long long)total,
-                (unsigned long long)st.compressed_bytes, bt_times.n_pieces, (unsigned long long)piece_blocks);
         fprintf(stderr, "[sbx] markdup-stream: n_windows=%u window_bytes=%llu n_batch_runs=%u n_batches_skipped=%u key_store_bytes=%llu "
                         "n_key_records=%llu ms_keys=%.2f ms_plan=%.2f ms_scatter=%.2f ms_inflate_replay=%.2f ms_index_replay=%.2f\n",
                 ss.n_windows, (unsigned long long)ss.window_bytes, ss.n_batch_runs, ss.n_batches_skipped, (unsigned long long)ss.key_store_bytes,

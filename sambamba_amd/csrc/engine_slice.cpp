@@ -263,20 +263,17 @@ int sbx_slice_bam(const char* in_path, const char* out_path, const char* const* 
 
         // ---- the splice writer ----
         const double w_write = wall_now();
-        FILE* f = fopen(out_file.c_str(), "wb");
-        if (!f) throw Error(SBX_EIO, "cannot write " + out_file.path);
-        out_file.arm();
-        bool ok = true;
+        OutputFile f(out_file);
         BgzfPieceTimes bt_times;
-        try {
-            // the longest compressed segment sizes the buffers
-            uint64_t longest = hlen, cur = hlen;
-            for (size_t g = 0; g < segs.size(); ++g) {
-                cur += segs[g].r1_bytes + h_len[2 * g];
-                if (segs[g].sp.blk1 > segs[g].sp.blk0) { longest = std::max(longest, cur); cur = 0; }
-                cur += h_len[2 * g + 1];
-            }
-            longest = std::max(longest, cur);
+        // the longest compressed segment sizes the buffers
+        uint64_t longest = hlen, cur = hlen;
+        for (size_t g = 0; g < segs.size(); ++g) {
+            cur += segs[g].r1_bytes + h_len[2 * g];
+            if (segs[g].sp.blk1 > segs[g].sp.blk0) { longest = std::max(longest, cur); cur = 0; }
+            cur += h_len[2 * g + 1];
+        }
+        longest = std::max(longest, cur);
+        {
             const size_t piece_blocks = bgzf_piece_blocks();
             const uint32_t cap_blocks = (uint32_t)std::min<uint64_t>(piece_blocks, std::max<uint64_t>(1, (longest + kBgzfPayload - 1) / kBgzfPayload));
             BgzfPieceCompressor comp(cap_blocks, -1, true);
@@ -288,7 +285,7 @@ int sbx_slice_bam(const char* in_path, const char* out_path, const char* const* 
                              if (p0 < hlen) SBX_HIP(hipMemcpyAsync(d_in, header.data() + p0, std::min<uint64_t>(hlen, p1) - p0, hipMemcpyHostToDevice, ps));
                              launch_gather_records(c->U(), d_off.p, order.perm, d_out_off.p, e0, e1, p0, p1, d_in, ps);
                          },
-                         [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
+                         [&](const uint8_t* p, size_t k) { f.write(p, k); });
                 st.stream_bytes += v1 - v0;
             };
             uint64_t e0 = 0, v0 = 0, e = 0, v = hlen;
@@ -301,10 +298,7 @@ int sbx_slice_bam(const char* in_path, const char* out_path, const char* const* 
                     const uint64_t f0 = bt.coffset[sp.blk0];
                     const uint64_t f1 = sp.blk1 < nbk ? bt.coffset[sp.blk1] : bt.comp_off[nbk - 1] + bt.comp_len[nbk - 1] + 8;
                     constexpr uint64_t kCopy = 8ull << 20;      // (the mapping of the input, written in bounded pieces)
-                    for (uint64_t o = f0; o < f1 && ok; o += kCopy) {
-                        const size_t k = (size_t)std::min<uint64_t>(kCopy, f1 - o);
-                        ok = fwrite(c->file.data + o, 1, k, f) == k;
-                    }
+                    for (uint64_t o = f0; o < f1 && f.ok(); o += kCopy) f.write(c->file.data + o, (size_t)std::min<uint64_t>(kCopy, f1 - o));
                     st.blocks_copied += sp.blk1 - sp.blk0;
                     st.bytes_copied += f1 - f0;
                     e0 = e; v0 = v;
@@ -313,9 +307,8 @@ int sbx_slice_bam(const char* in_path, const char* out_path, const char* const* 
                 v += h_len[2 * g + 1];
             }
             compress(e0, e, v0, v);
-        } catch (...) { fclose(f); throw; }
-        ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
-        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out_file.path);
+        }                                                   // (the encoder's buffers are freed inside ms_write)
+        f.finish(true);
         out_file.disarm();
         st.compressed_bytes = bt_times.out_bytes;
         st.ms_write = (wall_now() - w_write) * 1e3;

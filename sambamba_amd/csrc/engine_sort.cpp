@@ -16,13 +16,15 @@
 // destinations per batch (K9d-2); then, for every window of whole pieces of the stream that fits the device, the batches whose span
 // meets the window are run again (run_record_batch: the same K1 + K2, the same U and descriptors) and K9d-3 scatters their records
 // into the window, which goes through the same encoder to the file.  No temporary file and no merge; the file is the resident
-// path's byte for byte.  The name orders, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins stay resident and refuse with
-// SBX_ENOMEM what does not fit; sbx_markdup has a path of its own kind (engine_markdup.cpp: the output is in input order).
+// path's byte for byte.  The budget of device memory, the spans, the choice of the window and the loop over windows and batches are
+// engine_windows.hpp, shared with sbx_markdup (whose output is in input order); what is here is the key pass, the order and the
+// callback that launches K9d-3.  The name orders, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins stay resident and
+// refuse with SBX_ENOMEM what does not fit.
 //
 // sbx_sort_bam_by_name (`sambamba sort -n / -N`, with or without -M) is the same call with another order: next to K9a, K14a
 // (namesort.hip) builds the key of every kept record's name in a key store of 64-bit words, and the order is an LSD sort over those
 // words -- the -M word first, then the words from the last to word 0, each one K14b + K9b, and only the words and bits that vary.
-#include "engine_store.hpp"
+#include "engine_windows.hpp"
 #include "namesort.hpp"
 #include "sort_core.hpp"
 
@@ -134,42 +136,20 @@ void print_sort_line(const sbx_sort_stats& st, const char* by, double open_ms, d
 
 // SBX_SORT_WINDOW_BYTES (tests, measurements): forces the windowed path with windows of this many bytes, rounded up to whole pieces.
 // 0: unset (or not a positive decimal number).
-uint64_t window_bytes_hook() {
-    const char* e = getenv("SBX_SORT_WINDOW_BYTES");
-    if (!e || *e < '0' || *e > '9') return 0;
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    return *end ? 0 : (uint64_t)v;
-}
+uint64_t window_bytes_hook() { return env_u64("SBX_SORT_WINDOW_BYTES").value_or(0); }
 
 constexpr uint64_t kWindowedPerRecord = 36;     // bytes per record while the keys are sorted: key, key2, len, val, val2, dest / out_off
 
 // The coordinate sort of a file whose records do not stay on the device (or SBX_SORT_WINDOW_BYTES): the keys of the whole file are
-// sorted as in sort_file, the order becomes one destination per record (K9d-1), and the sorted stream is written window by window:
-// the batches of the key pass whose destinations meet the window (K9d-2) are run again and K9d-3 puts their records in place.  The
-// stream is cut into BGZF blocks exactly as write_permuted_bam cuts it, so the file is the resident path's byte for byte.
+// sorted as in sort_file, the order becomes one destination per record (K9d-1), and the sorted stream is written window by window
+// (write_windows): the batches of the key pass whose destinations meet the window (K9d-2) are run again and K9d-3 puts their records
+// in place.  The stream is cut into BGZF blocks exactly as write_permuted_bam cuts it, so the file is the resident path's byte for byte.
 void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<uint8_t>& header, bool use_filter, int level, uint64_t hook,
                         double w0, sbx_sort_stats* stats) {
     const uint64_t hlen = header.size();
     const int32_t n_ref = (int32_t)c->hdr.refs.size();
-    const uint64_t u_total = c->blocks.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
-    const uint64_t piece_blocks = bgzf_piece_blocks(), piece_bytes = piece_blocks * (uint64_t)kBgzfPayload;
-    // the encoder's buffers, as plan_store_bytes reserves them, and the smallest window: one piece, or the whole stream when it is shorter
-    const uint64_t stream_est = u_total - u_first + hlen;
-    const uint64_t cap_bytes = std::min<uint64_t>(piece_bytes, stream_est + kBgzfPayload);
-    const uint64_t out_reserve = cap_bytes * 3 + (8ull << 20);
-    const uint64_t est_records = (u_total - u_first) / 160 + 4096;
-    auto refuse = [&](uint64_t need, uint64_t free_b, const char* what) {
-        throw Error(SBX_ENOMEM, std::string("the file does not fit the device: sorting it in windows needs ") + std::to_string(need) +
-                                    " bytes of device memory (" + what + "), " + std::to_string(free_b) + " are free");
-    };
-    {
-        size_t free_b = 0, total_b = 0;
-        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t need = est_records * kWindowedPerRecord + 5ull * (64ull << 20) + out_reserve + cap_bytes;
-        if (need > free_b) refuse(need, free_b, "the keys of its records, one read batch, the encoder and a window of one piece");
-    }
-    const uint64_t batch_u = std::min<uint64_t>(index_batch_bytes(est_records * kWindowedPerRecord + out_reserve + cap_bytes), kWindowedBatchBytes);
+    WindowBudget budget(c.get(), hlen, sortc::kSortWindowWords, hook);
+    budget.fit(budget.est_records * kWindowedPerRecord, "the keys of its records, one read batch, the encoder and a window of one piece");
     hipStream_t s = c->stream.get();
     DevBuf<uint64_t> d_key;
     DevBuf<uint32_t> d_len, d_group_count, d_rank;
@@ -186,7 +166,7 @@ void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<
     std::vector<SavedBatch> saved;
     uint64_t n_in = 0, n_kept = 0;
     uint32_t n_batches = 0;
-    for_each_record_batch(c.get(), batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+    for_each_record_batch(c.get(), budget.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
         const size_t want = (size_t)(n_kept + nrec + 2);
         grow_keeping(d_key, (size_t)n_kept, want, s);
         grow_keeping(d_len, (size_t)n_kept, want, s);
@@ -218,7 +198,7 @@ void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<
     // ---- K9b, the offsets, K9d-1 and K9d-2 ----
     double ms_dest = 0;
     DevBuf<uint64_t> d_dest((size_t)n + 2);
-    std::vector<uint64_t> span_lo(saved.size(), ~0ull), span_hi(saved.size(), 0);
+    BatchSpans spans;
     uint64_t total = hlen;
     {
         ResidentOrder order;
@@ -228,112 +208,45 @@ void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<
         const OutputPlan plan = plan_output(d_len.p, order.perm, n, hlen, order.key2.p, s, &st.ms_gather);
         total = plan.total;
         if (total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the sorted records do not add up");
-        std::vector<uint64_t> first(saved.size() + 1, n);
-        for (size_t b = 0; b < saved.size(); ++b) first[b] = saved[b].first_kept;
-        DevBuf<uint64_t> d_first(first.size()), d_lo(saved.size() + 1), d_hi(saved.size() + 1);
-        SBX_HIP(hipMemcpyAsync(d_first.p, first.data(), first.size() * 8, hipMemcpyHostToDevice, s));
+        spans.upload(saved, n, s);
         EventTimer t;
         t.start(s);
         launch_window_dest(order.perm, order.key2.p, n, d_dest.p, s);
-        launch_batch_spans(d_dest.p, d_len.p, d_first.p, (uint32_t)saved.size(), d_lo.p, d_hi.p, s);
+        spans.launch(d_dest.p, d_len.p, s);
         t.stop(s);
-        if (!saved.empty()) {
-            SBX_HIP(hipMemcpyAsync(span_lo.data(), d_lo.p, saved.size() * 8, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipMemcpyAsync(span_hi.data(), d_hi.p, saved.size() * 8, hipMemcpyDeviceToHost, s));
-        }
-        SBX_HIP(hipStreamSynchronize(s));
+        spans.read_back(s);
         ms_dest = t.ms();
-        // keys, key2, val / val2 and the offsets go before the first window comes (order and the small tables: end of this scope)
+        // keys, key2, val / val2 and the offsets go before the first window comes (order: end of this scope)
         d_key.release();
     }
 
-    // ---- the window: what is free next to the batch buffers (they stay) less the encoder's ----
-    const uint32_t cap_blocks = (uint32_t)std::min<uint64_t>(piece_blocks, std::max<uint64_t>(1, (total + kBgzfPayload - 1) / kBgzfPayload));
-    uint64_t window_bytes = hook;
-    if (!window_bytes) {
-        size_t free_b = 0, total_b = 0;
-        SBX_HIP(hipMemGetInfo(&free_b, &total_b));
-        const uint64_t reserve = out_reserve + (64ull << 20);
-        const uint64_t avail = free_b > reserve ? free_b - reserve : 0;
-        const uint64_t smallest = std::min<uint64_t>(piece_bytes, total);
-        if (avail < smallest) refuse(smallest + reserve, free_b, "one window of one piece and the encoder, next to the read batch and 12 bytes per record");
-        window_bytes = std::max<uint64_t>(avail / piece_bytes, 1) * piece_bytes;
-    }
-    const std::vector<sortc::Window> windows = sortc::plan_windows(total, piece_bytes, window_bytes);
-    const uint64_t span = sortc::window_span(piece_bytes, window_bytes);
-    DevBuf<uint8_t> d_win((size_t)std::min<uint64_t>(span, total) + 64);
-    DevBuf<unsigned long long> d_wacc(kWindowAccWords);
-    BgzfPieceCompressor comp(cap_blocks, level, true);
-    BgzfPieceTimes bt_times;
-    const double w3 = wall_now();
-
-    FILE* f = fopen(out_file.c_str(), "wb");
-    if (!f) throw Error(SBX_EIO, "cannot write " + out_file.path);
-    out_file.arm();
-    bool ok = true;
-    uint64_t n_batch_runs = 0, n_batches_skipped = 0;
-    double ms_scatter = 0, ms_inflate_replay = 0, ms_index_replay = 0;
-    EventTimer t_s;
-    try {
-        for (const sortc::Window& w : windows) {
-            SBX_HIP(hipMemsetAsync(d_wacc.p, 0, kWindowAccWords * sizeof(unsigned long long), s));
-            if (w.w0 < hlen) SBX_HIP(hipMemcpyAsync(d_win.p, header.data() + w.w0, std::min<uint64_t>(hlen, w.w1) - w.w0, hipMemcpyHostToDevice, s));
-            for (size_t b = 0; b < saved.size(); ++b) {
-                const SavedBatch& sb = saved[b];
-                if (!sortc::span_meets_window(span_lo[b], span_hi[b], w.w0, w.w1)) { ++n_batches_skipped; continue; }
-                ++n_batch_runs;
-                run_record_batch(c.get(), sb, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-                    if (nrec != sb.nrec || base != sb.base || next != sb.next)
-                        throw Error(SBX_EIO, "the input changed while it was being sorted (a batch of the read pass holds other records than before)");
-                    if (use_filter) {
-                        d_group_count.ensure(sort_keys_groups(nrec) + 4);
-                        d_group_base.ensure(sort_keys_groups(nrec) + 4);
-                        d_rank.ensure((size_t)nrec + 2);
-                    }
-                    WindowScatterArgs a{};
-                    a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base; a.use_filter = use_filter ? 1u : 0u;
-                    a.first_kept = sb.first_kept; a.n_kept = sb.n_kept;
-                    a.dest = d_dest.p; a.len = d_len.p; a.w0 = w.w0; a.w1 = w.w1; a.window = d_win.p; a.acc = d_wacc.p;
-                    t_s.start(s);
-                    launch_window_scatter(a, d_group_count.p, d_group_base.p, d_rank.p, s);
-                    t_s.stop(s);
-                    // (the next batch's K1 / K2 overwrite U and the descriptors: K9d-3 ends first)
-                    SBX_HIP(hipStreamSynchronize(s));
-                    ms_scatter += t_s.ms();
-                    ms_inflate_replay += c->stats.ms_inflate;
-                    ms_index_replay += c->stats.ms_index;
-                    return true;
-                });
-            }
-            unsigned long long wacc[kWindowAccWords] = {0, 0};
-            SBX_HIP(hipMemcpyAsync(wacc, d_wacc.p, sizeof wacc, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipStreamSynchronize(s));
-            const std::string why = sortc::window_refusal(w.w0, w.w1, hlen, wacc[kWindowAccBytes], wacc[kWindowAccMismatch]);
-            if (!why.empty()) throw Error(SBX_EIO, why);
-            comp.run((size_t)(w.w1 - w.w0), false, &bt_times,
-                     [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
-                         SBX_HIP(hipMemcpyAsync(d_in, d_win.p + done, bytes, hipMemcpyDeviceToDevice, ps));
-                     },
-                     [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
+    // ---- the windows: K9d-3 for every saved batch that meets one ----
+    const WindowedOutput w = write_windows(c.get(), out_file, header, total, budget, spans, level, [&](const SavedBatch& sb, const RecordBatch& rb,
+                                           const sortc::Window& win, uint8_t* d_win, unsigned long long* d_wacc, hipStream_t ws) {
+        if (use_filter) {
+            d_group_count.ensure(sort_keys_groups(rb.nrec) + 4);
+            d_group_base.ensure(sort_keys_groups(rb.nrec) + 4);
+            d_rank.ensure((size_t)rb.nrec + 2);
         }
-    } catch (...) { fclose(f); throw; }
-    ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
-    if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out_file.path);
+        WindowScatterArgs a{};
+        a.U = c->U(); a.desc = c->d_desc.p; a.n = rb.nrec; a.u_end = rb.next - rb.base; a.use_filter = use_filter ? 1u : 0u;
+        a.first_kept = sb.first_kept; a.n_kept = sb.n_kept;
+        a.dest = d_dest.p; a.len = d_len.p; a.w0 = win.w0; a.w1 = win.w1; a.window = d_win; a.acc = d_wacc;
+        launch_window_scatter(a, d_group_count.p, d_group_base.p, d_rank.p, ws);
+    });
     out_file.disarm();
-    const double w4 = wall_now();
+    const double w3 = w.w_planned, w4 = w.w_written;
 
-    st.ms_gather += ms_dest + ms_scatter;
+    st.ms_gather += ms_dest + w.ms_scatter;
     st.n_records_in = n_in; st.n_records_out = n;
-    st.inflated_bytes = u_total; st.sorted_stream_bytes = total; st.compressed_bytes = bt_times.out_bytes + 28;
-    st.n_batches = n_batches; st.n_windows = (uint32_t)windows.size();
-    st.ms_deflate = bt_times.ms_deflate + bt_times.ms_pack;
+    st.inflated_bytes = budget.u_total; st.sorted_stream_bytes = total; st.compressed_bytes = w.compressed_bytes;
+    st.n_batches = n_batches; st.n_windows = w.n_windows;
+    st.ms_deflate = w.ms_deflate;
     st.ms_total_wall = (w4 - w0) * 1e3;
     if (getenv("SBX_TIMING")) {
-        fprintf(stderr, "[sbx] output: stream_bytes=%llu compressed_bytes=%llu n_pieces=%u piece_blocks=%llu\n", (unsigned long long)total,
-                (unsigned long long)st.compressed_bytes, bt_times.n_pieces, (unsigned long long)piece_blocks);
         fprintf(stderr, "[sbx] sort-windows: n_windows=%u window_bytes=%llu n_batch_runs=%llu n_batches_skipped=%llu ms_dest=%.2f ms_scatter=%.2f "
-                        "ms_inflate_replay=%.2f ms_index_replay=%.2f\n", st.n_windows, (unsigned long long)span, (unsigned long long)n_batch_runs,
-                (unsigned long long)n_batches_skipped, ms_dest, ms_scatter, ms_inflate_replay, ms_index_replay);
+                        "ms_inflate_replay=%.2f ms_index_replay=%.2f\n", st.n_windows, (unsigned long long)w.span, (unsigned long long)w.n_batch_runs,
+                (unsigned long long)w.n_batches_skipped, ms_dest, w.ms_scatter, w.ms_inflate_replay, w.ms_index_replay);
         print_sort_line(st, "", (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);
     }
     if (stats) *stats = st;

@@ -5,7 +5,8 @@
 // tail (write_store_output) that turns "header + records of the store in the order of a permutation" into a BGZF file piece by piece
 // (offsets, piece bounds, K9c gather, deflate) and hands back the figures every stats struct takes from it.  The permutation is a
 // list of record numbers: it may leave records out (a filter) or name one several times (sbx_view_bam with listed regions).  The
-// stream written never exists as a whole.  What the kernels share is wave_prims.hpp.
+// stream written never exists as a whole.  What the kernels share is wave_prims.hpp.  A file that does not fit the store goes, for
+// sort and markdup, through engine_windows.hpp instead: the same reading order, a key pass for the plan, the windowed writer for the tail.
 #pragma once
 #include "engine_ctx.hpp"
 #include "engine_stream.hpp"
@@ -212,31 +213,25 @@ inline void write_permuted_bam(OutputGuard& out, const std::vector<uint8_t>& hea
                                const uint64_t* d_off, const uint32_t* d_perm, const uint64_t* d_out_off, uint64_t n, int level,
                                double* ms_gather, BgzfPieceTimes* bt_times) {
     const uint64_t hlen = header.size();
-    FILE* f = fopen(out.c_str(), "wb");
-    if (!f) throw Error(SBX_EIO, "cannot write " + out.path);
-    out.arm();
-    bool ok = true;
+    OutputFile f(out);
     EventTimer t_gather;
-    try {
-        bgzf_compress_pieces((size_t)plan.total, (size_t)plan.piece_blocks, level, true, false, bt_times,
-                             [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
-                                 const uint64_t p0 = done, p1 = done + bytes;
-                                 const size_t k = (size_t)(p0 / plan.piece_bytes());
-                                 t_gather.start(ps);
-                                 if (p0 < hlen) {
-                                     const uint64_t he = std::min<uint64_t>(hlen, p1);
-                                     SBX_HIP(hipMemcpyAsync(d_in, header.data() + p0, he - p0, hipMemcpyHostToDevice, ps));
-                                 }
-                                 uint64_t r0, r1;
-                                 sortc::piece_records(plan.bounds.data(), k, n, &r0, &r1);
-                                 launch_gather_records(d_store, d_off, d_perm, d_out_off, r0, r1, p0, p1, d_in, ps);
-                                 t_gather.stop(ps);
-                                 *ms_gather += t_gather.ms();
-                             },
-                             [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
-    } catch (...) { fclose(f); throw; }
-    ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
-    if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out.path);
+    bgzf_compress_pieces((size_t)plan.total, (size_t)plan.piece_blocks, level, true, false, bt_times,
+                         [&](uint8_t* d_in, size_t done, size_t bytes, hipStream_t ps) {
+                             const uint64_t p0 = done, p1 = done + bytes;
+                             const size_t k = (size_t)(p0 / plan.piece_bytes());
+                             t_gather.start(ps);
+                             if (p0 < hlen) {
+                                 const uint64_t he = std::min<uint64_t>(hlen, p1);
+                                 SBX_HIP(hipMemcpyAsync(d_in, header.data() + p0, he - p0, hipMemcpyHostToDevice, ps));
+                             }
+                             uint64_t r0, r1;
+                             sortc::piece_records(plan.bounds.data(), k, n, &r0, &r1);
+                             launch_gather_records(d_store, d_off, d_perm, d_out_off, r0, r1, p0, p1, d_in, ps);
+                             t_gather.stop(ps);
+                             *ms_gather += t_gather.ms();
+                         },
+                         [&](const uint8_t* p, size_t k) { f.write(p, k); });
+    f.finish(true);
 }
 
 // ---- the output tail of the four commands ----

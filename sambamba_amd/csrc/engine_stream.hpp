@@ -12,20 +12,13 @@
 
 namespace sbx {
 
-constexpr uint8_t kEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
 constexpr size_t kBgzfPieceBlocks = 32768;      // BGZF blocks compressed per launch: a piece of the stream is at most this many payloads
 
 // BGZF blocks per piece for one call: kBgzfPieceBlocks, or SBX_BGZF_PIECE_BLOCKS (tests: a decimal number, brought into
 // [1, kBgzfPieceBlocks]; anything else counts as unset).  Blocks are cut every kBgzfPayload bytes whatever the piece, so the value
 // does not change a byte of the output.  Read once per call: the caller hands the value to everything that depends on it.
 inline size_t bgzf_piece_blocks() {
-    const char* e = getenv("SBX_BGZF_PIECE_BLOCKS");
-    if (!e || *e < '0' || *e > '9') return kBgzfPieceBlocks;
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    if (*end) return kBgzfPieceBlocks;
-    return (size_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 1), kBgzfPieceBlocks);
+    return (size_t)std::min<uint64_t>(std::max<uint64_t>(env_u64("SBX_BGZF_PIECE_BLOCKS").value_or(kBgzfPieceBlocks), 1), kBgzfPieceBlocks);
 }
 
 struct BgzfPieceTimes { double ms_fill = 0, ms_deflate = 0, ms_pack = 0, ms_d2h = 0; uint64_t out_bytes = 0; uint32_t n_pieces = 0; };

@@ -391,14 +391,7 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
 
 // Text bytes per piece of sbx_view_sam: 64 MiB (not tuned), or SBX_SAM_PIECE_BYTES (tests: a decimal number of at least 1; anything
 // else counts as unset).  Pieces are cut at line ends and written in order, so the value does not change a byte of the output.
-uint64_t sam_piece_bytes() {
-    constexpr uint64_t kDefault = 64ull << 20;
-    const char* e = getenv("SBX_SAM_PIECE_BYTES");
-    if (!e || *e < '0' || *e > '9') return kDefault;
-    char* end = nullptr;
-    const unsigned long long v = strtoull(e, &end, 10);
-    return *end || !v ? kDefault : (uint64_t)v;
-}
+uint64_t sam_piece_bytes() { return env_size("SBX_SAM_PIECE_BYTES", 64ull << 20); }
 
 }  // namespace
 
@@ -585,10 +578,8 @@ int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter
         Event ev_copy[2];
         Stream copy;
         copy.create();
-        FILE* f = fopen(out_file.c_str(), "wb");
-        if (!f) throw Error(SBX_EIO, "cannot write " + out_file.path);
-        out_file.arm();
-        bool ok = text.empty() || fwrite(text.data(), 1, text.size(), f) == text.size();
+        OutputFile f(out_file);
+        f.write(text.data(), text.size());
         try {
             auto finish = [&](uint32_t k) {             // piece k: its copy has arrived; check, write
                 const int b = (int)(k & 1u);
@@ -597,7 +588,7 @@ int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter
                 if (h_acc.p[b * kSamAccWords + kSamAccOverrun])
                     throw Error(SBX_EFORMAT, "internal error: a SAM line did not have the length it was measured with");
                 const size_t bytes = (size_t)(first_off[k + 1] - first_off[k]);
-                ok = ok && fwrite(h_piece[b].p, 1, bytes, f) == bytes;
+                f.write(h_piece[b].p, bytes);
             };
             for (uint32_t k = 0; k < n_pieces; ++k) {
                 const int b = (int)(k & 1u);
@@ -611,13 +602,12 @@ int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter
                 SBX_HIP(hipEventRecord(ev_copy[b].get(), copy.get()));
             }
             if (n_pieces) finish(n_pieces - 1);
-        } catch (...) {
+        } catch (...) {                                 // (the pinned buffers die with this scope: nothing may still be copying into them)
             (void)hipStreamSynchronize(s);
             (void)hipStreamSynchronize(copy.get());
-            fclose(f);
             throw;
         }
-        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, "error writing " + out_file.path);
+        f.finish(false);
         out_file.disarm();
         st.stream_bytes = n ? first_off[n_pieces] : 0;
         st.ms_total_wall = (wall_now() - w0) * 1e3;

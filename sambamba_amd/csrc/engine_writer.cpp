@@ -207,10 +207,9 @@ int build_index_impl(const char* bam_path, const char* bai_path, bool check_bins
         if (getenv("SBX_TIMING"))
             fprintf(stderr, "[sbx] build_index: %u batch(es) of <= %llu inflated bytes, records consumed %s\n", n_batches, (unsigned long long)batch_u,
                     on_device ? "on the device" : "by the serial builder on the host");
-        FILE* f = fopen(bai_path, "wb");
-        if (!f) throw Error(SBX_EIO, std::string("cannot write ") + bai_path);
-        const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
-        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + bai_path);
+        OutputFile f(bai_path);
+        f.write(bytes.data(), bytes.size());
+        f.finish(false);
     });
 }
 }  // namespace
@@ -316,14 +315,9 @@ int sbx_write_bam(const char* path, const uint8_t* stream, size_t n, int level, 
         if (!path || (!stream && n)) throw Error(SBX_EINVAL, "null argument");
         check_level(level);
         require_device(device);
-        FILE* f = fopen(path, "wb");
-        if (!f) throw Error(SBX_EIO, std::string("cannot write ") + path);
-        bool ok = true;
-        try {
-            bgzf_compress_stream(stream, n, level, [&](const uint8_t* p, size_t k) { ok = ok && fwrite(p, 1, k, f) == k; });
-        } catch (...) { fclose(f); throw; }
-        ok = ok && fwrite(kEofBlock, 1, 28, f) == 28;
-        if (fclose(f) != 0 || !ok) throw Error(SBX_EIO, std::string("error writing ") + path);
+        OutputFile f(path);
+        bgzf_compress_stream(stream, n, level, [&](const uint8_t* p, size_t k) { f.write(p, k); });
+        f.finish(true);
     });
     if (rc != SBX_OK || !with_index) return rc;
     return sbx_build_index(path, (std::string(path) + ".bai").c_str(), device, err, errlen);

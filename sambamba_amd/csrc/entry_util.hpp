@@ -1,15 +1,45 @@
 // entry_util.hpp -- the host-only pieces the standalone entry points (sbx_sort_bam, sbx_markdup, sbx_merge_bam, sbx_view_*, ...)
-// share and that need neither the HIP runtime nor a context: tests/native/entry_host.cpp compiles them alone.
+// share and that need neither the HIP runtime nor a context: the error type, the decimal environment hook, the output guard and
+// the output file.  tests/native/entry_host.cpp compiles them alone.
 #pragma once
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <optional>
+#include <stdexcept>
 #include <string>
 
 #include "../../include/sbx_depth.h"
 
 namespace sbx {
+
+struct Error : std::runtime_error {
+    int code;
+    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
+};
+
+// the empty BGZF block that ends a BAM file
+constexpr uint8_t kEofBlock[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// A hook of the tests and measurements: the decimal number in environment variable `name`.  Nothing when the variable is missing,
+// does not start with a digit or goes on behind the number: anything but a plain number counts as unset.
+inline std::optional<uint64_t> env_u64(const char* name) {
+    const char* e = getenv(name);
+    if (!e || *e < '0' || *e > '9') return std::nullopt;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (*end) return std::nullopt;
+    return (uint64_t)v;
+}
+// the same for a size that has a default: `dflt` when the variable is unset or its number is below `least`
+inline uint64_t env_size(const char* name, uint64_t dflt, uint64_t least = 1) {
+    const std::optional<uint64_t> v = env_u64(name);
+    return v && *v >= least ? *v : dflt;
+}
 
 inline bool same_file(const char* a, const char* b) {
     struct stat sa, sb;
@@ -46,6 +76,34 @@ struct OutputGuard {
     void arm() { armed = !to_stdout; }
     void disarm() { armed = false; }
     const char* c_str() const { return path.c_str(); }
+};
+
+// The file a command writes piece by piece: opened "wb" (SBX_EIO "cannot write <path>"), and `guard`, when there is one, armed as
+// soon as the file exists.  write() latches a failure; finish() appends the BGZF EOF block when asked, closes, and throws SBX_EIO
+// "error writing <path>" when anything failed.  A file that is not finished (an exception passes by) is closed by the destructor;
+// the guard is never disarmed here: the caller does that when nothing can fail any more.
+class OutputFile {
+    std::string path_;
+    FILE* f_;
+    bool ok_ = true;
+
+public:
+    explicit OutputFile(const std::string& path, OutputGuard* guard = nullptr) : path_(path), f_(fopen(path.c_str(), "wb")) {
+        if (!f_) throw Error(SBX_EIO, "cannot write " + path_);
+        if (guard) guard->arm();
+    }
+    explicit OutputFile(OutputGuard& guard) : OutputFile(guard.path, &guard) {}
+    OutputFile(const OutputFile&) = delete;
+    OutputFile& operator=(const OutputFile&) = delete;
+    ~OutputFile() { if (f_) fclose(f_); }
+    bool ok() const { return ok_; }
+    void write(const void* p, size_t k) { ok_ = ok_ && fwrite(p, 1, k, f_) == k; }
+    void finish(bool with_eof_block) {
+        if (with_eof_block) write(kEofBlock, sizeof kEofBlock);
+        const bool closed = fclose(f_) == 0;
+        f_ = nullptr;
+        if (!closed || !ok_) throw Error(SBX_EIO, "error writing " + path_);
+    }
 };
 
 }  // namespace sbx

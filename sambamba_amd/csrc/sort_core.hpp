@@ -2,7 +2,8 @@
 // radix sort has to look at, the arithmetic of the pieces the output stream is produced in and of the windows a file larger than the
 // device is written in, and the header text of the output.  The key, piece and window functions are `__host__ __device__` (K9a,
 // k_piece_bounds, K9c and K9d of sort.hip run the very statements the CPU tests check: tests/native/sort_host.cpp and
-// tests/native/sortwin_host.cpp); the header text, plan_windows and window_refusal are host code.
+// tests/native/sortwin_host.cpp); the header text, plan_windows and the refusals of the windowed writer (engine_windows.hpp), worded
+// for sort or for markdup by a WindowWords, are host code.
 //
 // Order (compareCoordinatesAndStrand, BioD bio/std/hts/bam/read.d:1632-1642, applied by a stable merge sort): ref_id -1 last, ascending
 // ref_id, ascending position as a signed number, forward strand in front of reverse strand, ties in file order.  Records with ref_id -1
@@ -97,7 +98,7 @@ SBX_SORT_HD bool clip_to_piece(uint64_t o, uint64_t e, uint64_t p0, uint64_t p1,
     return true;
 }
 
-// ---- the windows of the output stream (the windowed sort: engine_sort.cpp; K9d, sort.hip) ----
+// ---- the windows of the output stream (engine_windows.hpp: the windowed sort and the streamed markdup; K9d, sort.hip; K10f, markdup.hip) ----
 // A file whose records do not fit the device is written window by window: a window is a run of whole pieces [w0, w1) of the stream
 // that fits the device, filled by passing the file through the read pass again and putting every record that has bytes in it at
 // dest - w0 (the clip of a record to a window is clip_to_piece).  window_bytes is rounded UP to whole pieces, at least one; the last
@@ -141,16 +142,38 @@ inline std::vector<Window> plan_windows(uint64_t total_stream_bytes, uint64_t pi
     return w;
 }
 
-// The two checks on a window before it is compressed (K9d-3's accumulator): the record bytes written must be the window less the
-// header bytes that lie in it (header: [0, hlen) of the stream), and no record may have had another length than the key pass saw.
-// Empty: the window is whole; otherwise the text of the SBX_EIO refusal.
-inline std::string window_refusal(uint64_t w0, uint64_t w1, uint64_t hlen, uint64_t bytes_written, uint64_t mismatches) {
+// The windowed writer (engine_windows.hpp) serves two commands; the phrases of its refusals that differ between them:
+struct WindowWords {
+    const char* task;           // "... does not fit the device: <task> in windows needs ..."
+    const char* window_needs;   // what the window itself needs, for that refusal
+    const char* doing;          // "the input changed while <doing>"
+    const char* stream;         // "bytes [w0, w1) of the <stream>"
+    const char* source;         // "record(s) are not the ones <source>"
+};
+constexpr WindowWords kSortWindowWords{"sorting it", "one window of one piece and the encoder, next to the read batch and 12 bytes per record",
+                                       "it was being sorted", "sorted stream", "the keys were taken from"};
+constexpr WindowWords kMarkdupWindowWords{"marking its duplicates", "a window of one piece and the encoder, next to the read batch and 17 bytes per record",
+                                          "its duplicates were being marked", "output stream", "the key pass read"};
+
+// the SBX_ENOMEM refusal of a file that does not even go through in windows; parts: what the `need` bytes are for
+inline std::string windows_do_not_fit(const WindowWords& words, uint64_t need, uint64_t free_bytes, const std::string& parts) {
+    return std::string("the file does not fit the device: ") + words.task + " in windows needs " + std::to_string(need) +
+           " bytes of device memory (" + parts + "), " + std::to_string(free_bytes) + " are free";
+}
+// the SBX_EIO refusal of a batch that came out of the read pass differently the second time
+inline std::string batch_refusal(const WindowWords& words) {
+    return std::string("the input changed while ") + words.doing + " (a batch of the read pass holds other records than before)";
+}
+// The two checks on a window before it is compressed (the accumulator of K9d-3 / K10f): the record bytes written must be the window
+// less the header bytes that lie in it (header: [0, hlen) of the stream), and no record may have had another length than the key pass
+// saw.  Empty: the window is whole; otherwise the text of the SBX_EIO refusal.
+inline std::string window_refusal(uint64_t w0, uint64_t w1, uint64_t hlen, uint64_t bytes_written, uint64_t mismatches, const WindowWords& words = kSortWindowWords) {
     PieceClip h;
     const uint64_t header_bytes = clip_to_piece(0, hlen, w0, w1, &h) ? h.len : 0;
     if (!mismatches && bytes_written == w1 - w0 - header_bytes) return std::string();
-    return "the input changed while it was being sorted (bytes [" + std::to_string(w0) + ", " + std::to_string(w1) + ") of the sorted stream: " +
-           std::to_string(bytes_written) + " record bytes arrived where " + std::to_string(w1 - w0 - header_bytes) + " belong, " +
-           std::to_string(mismatches) + " record(s) are not the ones the keys were taken from)";
+    return std::string("the input changed while ") + words.doing + " (bytes [" + std::to_string(w0) + ", " + std::to_string(w1) + ") of the " +
+           words.stream + ": " + std::to_string(bytes_written) + " record bytes arrived where " + std::to_string(w1 - w0 - header_bytes) +
+           " belong, " + std::to_string(mismatches) + " record(s) are not the ones " + words.source + ")";
 }
 
 // A SAM header text as SamHeader's constructor reads it (BioD bio/std/hts/sam/header.d:473-545) and SamHeader.toSam prints it back

@@ -10,7 +10,10 @@
 //                               stdout: the windows one behind the other.  stderr per window: "window k w0 w1 unwritten twice outside
 //                               runs skipped whole" -- bytes of [0, w1 - w0) written never / more than once, writes outside it, batches
 //                               run and skipped, and whether window_refusal accepts the bytes counted.
-//   sortwin_host refusal W0 W1 HLEN BYTES MISMATCHES   -> the text of window_refusal on stdout; exit status 3 when there is one
+//   sortwin_host refusal W0 W1 HLEN BYTES MISMATCHES [sort|markdup]   -> the text of window_refusal in the command's words (sort when
+//                               not given) on stdout; exit status 3 when there is one
+//   sortwin_host words sort|markdup              -> the two other refusals in the command's words, one per line: batch_refusal, and
+//                               windows_do_not_fit for 1000 bytes needed, 10 free and the command's own window_needs
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -97,10 +100,18 @@ int main(int argc, char** argv) {
     auto num = [&](int k) { return strtoull(argv[k], nullptr, 10); };
     if (mode == "plan" && argc == 5) return plan(num(2), num(3), num(4));
     if (mode == "clip" && argc == 6) return clip(num(2), num(3), num(4), num(5));
-    if (mode == "refusal" && argc == 7) {
-        const std::string why = window_refusal(num(2), num(3), num(4), num(5), num(6));
+    auto words = [&](int k) -> const WindowWords* {
+        if (k >= argc || std::string(argv[k]) == "sort") return &kSortWindowWords;
+        return std::string(argv[k]) == "markdup" ? &kMarkdupWindowWords : nullptr;
+    };
+    if (mode == "refusal" && (argc == 7 || argc == 8) && words(7)) {
+        const std::string why = window_refusal(num(2), num(3), num(4), num(5), num(6), *words(7));
         printf("%s", why.c_str());
         return why.empty() ? 0 : 3;
+    }
+    if (mode == "words" && argc == 3 && words(2)) {
+        printf("%s\n%s\n", batch_refusal(*words(2)).c_str(), windows_do_not_fit(*words(2), 1000, 10, words(2)->window_needs).c_str());
+        return 0;
     }
     return 2;
 }

@@ -1,5 +1,6 @@
 """The host-only helpers of the standalone entry points (sambamba_amd/csrc/entry_util.hpp: the text-to-caller-buffer copy, the
-malformed-records message, the output guard's unlink-unless-disarmed, the same-file test), compiled for the host with g++ and
+malformed-records message, the output guard's unlink-unless-disarmed, the same-file test, the decimal environment hook and what the
+six size hooks make of it, the output file with its latched write failure and its EOF block), compiled for the host with g++ and
 -fsanitize=address,undefined into tests/native/entry_host.cpp and run as a program of their own -- no GPU, no Python in the process."""
 import os
 import subprocess

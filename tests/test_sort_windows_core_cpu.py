@@ -125,6 +125,31 @@ def test_window_refusal_wording(host):
     for args in ([100, 300, 150, 149, 0], [100, 300, 150, 151, 0], [100, 300, 150, 150, 1], [0, 100, 150, 1, 0]):
         r = run(host, ["refusal"] + args)
         assert r.returncode == 3 and b"the input changed while it was being sorted" in r.stdout, args
+    # the whole sentence, in the words of either command: the windowed writer is one, the phrases are the command's
+    phrases = {"sort": ("it was being sorted", "sorted stream", "the keys were taken from"),
+               "markdup": ("its duplicates were being marked", "output stream", "the key pass read")}
+    for cmd, (doing, stream, source) in phrases.items():
+        # (window, header bytes, record bytes arrived, mismatches) -> record bytes that belong: a record that is another one; a byte
+        # short in the window that holds the 100 header bytes; both at once
+        for args, belong in (([65280, 130560, 100, 65280, 2], 65280), ([0, 65280, 100, 65179, 0], 65180), ([65280, 130560, 100, 65279, 2], 65280)):
+            r = run(host, ["refusal"] + args + [cmd])
+            want = ("the input changed while %s (bytes [%d, %d) of the %s: %d record bytes arrived where %d belong, %d record(s) are not the ones %s)"
+                    % (doing, args[0], args[1], stream, args[3], belong, args[4], source))
+            assert (r.returncode, r.stdout.decode()) == (3, want)
+        assert run(host, ["refusal", 65280, 130560, 100, 65280, 0, cmd]).returncode == 0
+    assert run(host, ["refusal", 65280, 130560, 100, 65279, 2, "markdup"]).stdout == (
+        b"the input changed while its duplicates were being marked (bytes [65280, 130560) of the output stream: 65279 record bytes arrived "
+        b"where 65280 belong, 2 record(s) are not the ones the key pass read)")
+    assert run(host, ["refusal", 0, 1, 0, 0, 0, "view"]).returncode == 2
+    # the refusal of a batch that came out differently, and of a file for which not even one window fits
+    assert run(host, ["words", "sort"]).stdout.decode().splitlines() == [
+        "the input changed while it was being sorted (a batch of the read pass holds other records than before)",
+        "the file does not fit the device: sorting it in windows needs 1000 bytes of device memory (one window of one piece and the encoder, "
+        "next to the read batch and 12 bytes per record), 10 are free"]
+    assert run(host, ["words", "markdup"]).stdout.decode().splitlines() == [
+        "the input changed while its duplicates were being marked (a batch of the read pass holds other records than before)",
+        "the file does not fit the device: marking its duplicates in windows needs 1000 bytes of device memory (a window of one piece and the "
+        "encoder, next to the read batch and 17 bytes per record), 10 are free"]
 
 
 def test_n_windows_word_of_the_stats():
