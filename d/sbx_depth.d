@@ -165,6 +165,15 @@ extern (C) nothrow @nogc {
     enum SBX_VIEW_INDEX_AUTO = 2;
     int sbx_view_run_indexed(const(sbx_view_request)* request, int index_mode, ulong* count, sbx_view_stats* stats,
                              sbx_view_index_stats* index, char* err, size_t errlen);
+    // the streamed path of the commands whose output order is the input order (a file larger than the device, or
+    // SBX_STREAM_WINDOW_BYTES); all zeros: the resident path
+    struct sbx_stream_stats {
+        ulong window_bytes; ulong n_pack_launches;
+        uint n_windows; uint reserved;
+        double ms_pack;
+    }
+    int sbx_view_run_streamed(const(sbx_view_request)* request, int index_mode, ulong* count, sbx_view_stats* stats,
+                              sbx_view_index_stats* index, sbx_stream_stats* stream_stats, char* err, size_t errlen);
     // which records are valid (alignment.d's isValid), and why not: class k of the report is bit k of a record's mask
     enum SBX_VALIDATE_CLASSES = 10;
     struct sbx_validate_report {
@@ -209,6 +218,8 @@ extern (C) nothrow @nogc {
     }
     // `sambamba fixbins`
     int sbx_fixbins(const(char)* in_path, const(char)* out_path, int level, int device, sbx_fixbins_stats* stats, char* err, size_t errlen);
+    int sbx_fixbins_run(const(char)* in_path, const(char)* out_path, int level, int device, sbx_fixbins_stats* stats,
+                        sbx_stream_stats* stream_stats, char* err, size_t errlen);
     struct sbx_fasta_stats {
         ulong n_sequences; ulong n_lines; ulong n_bytes;
         uint n_chunks; uint reserved;

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_markdup_stream_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_markdup_stream_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats", "sbx_stream_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -208,8 +208,9 @@ int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, si
  *             not the one its key was taken with -- the call fails with SBX_EIO ("the input changed while it was being sorted") and
  *             the output file is removed.  SBX_ENOMEM only when not even the keys, one minimal read batch and a window of one piece
  *             fit.
- * sbx_sort_bam_by_name, sbx_merge_bam, sbx_view_bam, sbx_import_sam and sbx_fixbins have the resident path only and
- * refuse what does not fit with SBX_ENOMEM (a name order needs the names next to the keys: not built).
+ * sbx_sort_bam_by_name, sbx_merge_bam, sbx_import_sam and view with two or more listed regions have
+ * the resident path only and refuse what does not fit with SBX_ENOMEM (a name order needs the names next to the keys: not built);
+ * sbx_fixbins and both sinks of view in file order stream such a file (sbx_stream_stats).
  * Milliseconds are device time of the kernels (inflate = K1, index = K2, keys = K9a + the copy into the record store, sort = K9b,
  * gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index.
  * On the windowed path inflate and index are those of the key pass alone (SBX_TIMING=1 reports the replays in a `[sbx] sort-windows:`
@@ -456,6 +457,31 @@ typedef struct {
 #define SBX_VIEW_INDEX_AUTO 2
 int sbx_view_run_indexed(const sbx_view_request* request, int index_mode, uint64_t* count, sbx_view_stats* stats,
                          sbx_view_index_stats* index, char* err, size_t errlen);
+/* What the streamed path of a command whose output order is the input order did (sbx_view_run_streamed, sbx_fixbins_run).  All
+ * zeros: the resident path.  The streamed path keeps no record store: while a batch of the read pass is on the device K21 puts its
+ * selected records into one staging window of the output stream, and a full window goes through the BGZF encoder into the file, so
+ * a file larger than the device works and the file written is the resident path's byte for byte.  It is taken when the resident
+ * store would be refused with SBX_ENOMEM, or when SBX_STREAM_WINDOW_BYTES=<n> is set (tests and measurements: a window of n bytes
+ * rounded up to whole pieces of the output stream; anything but a positive decimal counts as unset).  n_windows: windows handed to
+ * the encoder; window_bytes: bytes of the output stream per window; n_pack_launches: launches of K21's copy kernel (one per batch
+ * and window the batch has bytes in); ms_pack: device time of K21.  SBX_ENOMEM is left for one minimal read batch, the encoder and a
+ * window of one piece not fitting; the message states the bytes needed and free.  With SBX_TIMING=1 the same figures are printed in
+ * a `[sbx] stream:` line. */
+typedef struct {
+    uint64_t window_bytes, n_pack_launches;
+    uint32_t n_windows, reserved;
+    double ms_pack;
+} sbx_stream_stats;
+/* sbx_view_run_indexed with the figures of the streamed path: stream_stats may be NULL, and sbx_view_run_indexed is this call with
+ * NULL.  The BAM and the SAM sink stream when the output order is the file order -- no region, exactly one listed region, or a BED
+ * file -- with or without filter, num-filter, subsampling and valid_only, on the whole-file and on the indexed pass.  Two or more
+ * listed regions order the output by region and keep the resident store and its SBX_ENOMEM.  The SAM sink has no window: per batch
+ * K12b, K13a and K13b run over the records where K1 left them, n_windows counts the pieces of text written, window_bytes is the
+ * piece size, n_pack_launches and ms_pack stay 0.  On the streamed path a malformed selected record of a later batch is met after
+ * earlier windows or pieces were written: the call fails with the same code and message, an output file is removed, an output on
+ * stdout has received bytes by then. */
+int sbx_view_run_streamed(const sbx_view_request* request, int index_mode, uint64_t* count, sbx_view_stats* stats,
+                          sbx_view_index_stats* index, sbx_stream_stats* stream_stats, char* err, size_t errlen);
 
 /* ---- validate: which records of a BAM are valid, and why not (`sambamba view -v`; `sambamba validate` is an empty stub) ----
  * A record is valid when isValid of BioD bio/std/hts/bam/validation/alignment.d says so.  K19 evaluates every class of error on its
@@ -569,6 +595,11 @@ typedef struct {
     double ms_inflate, ms_index, ms_bins, ms_gather, ms_deflate, ms_total_wall;
 } sbx_fixbins_stats;
 int sbx_fixbins(const char* in_path, const char* out_path, int level, int device, sbx_fixbins_stats* stats, char* err, size_t errlen);
+/* sbx_fixbins with the figures of the streamed path (sbx_stream_stats above): stream_stats may be NULL, and sbx_fixbins is this call
+ * with NULL.  On the streamed path K16b computes the bin of every record of a batch and K21 writes the two bytes while it copies the
+ * record into the window: the patched record never exists in a store.  ms_gather is 0 there (the copy is ms_pack). */
+int sbx_fixbins_run(const char* in_path, const char* out_path, int level, int device, sbx_fixbins_stats* stats,
+                    sbx_stream_stats* stream_stats, char* err, size_t errlen);
 /* `sambamba index -F` (buildFai, BioD bio/std/file/fai.d:78-101): the .fai of a FASTA file, its lines found and added up on the
  * device (K17).  The line terminator is "\r\n" when the first line ends in it, "\n" otherwise, for the whole file; the text is split
  * at it only (a last line without terminator is a line; with "\n" a '\r' is a byte of its line).  A line starting with '>' opens a

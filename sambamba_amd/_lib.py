@@ -171,6 +171,12 @@ class ViewIndexStats(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("blocks_in_file", "blocks_read", "runs", "compressed_bytes_read", "inflated_bytes_read")] +
                 [("ms_plan", C.c_double)])
 
+class StreamStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("window_bytes", "n_pack_launches")] + [(k, C.c_uint32) for k in ("n_windows", "reserved")] +
+                [("ms_pack", C.c_double)])
+
+STREAM_KEYS = ("n_windows", "window_bytes", "n_pack_launches", "ms_pack")
+
 VIEW_INDEX_MODES = {False: 0, True: 1, "auto": 2}       # SBX_VIEW_INDEX_OFF / _REQUIRED / _AUTO
 
 WRITE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_char), C.c_size_t)
@@ -184,11 +190,11 @@ EXPORTS = [
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
     "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_run", "sbx_markdup_header_text",
     "sbx_merge_bam", "sbx_merge_header_text",
-    "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_run", "sbx_view_run_indexed", "sbx_view_num_filter", "sbx_view_reference_info",
+    "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_run", "sbx_view_run_indexed", "sbx_view_run_streamed", "sbx_view_num_filter", "sbx_view_reference_info",
     "sbx_validate_bam", "sbx_format_validate_report",
     "sbx_slice_bam",
     "sbx_import_sam",
-    "sbx_index_bam", "sbx_fixbins", "sbx_index_fasta",
+    "sbx_index_bam", "sbx_fixbins", "sbx_fixbins_run", "sbx_index_fasta",
 ]
 
 _lib = None
@@ -330,6 +336,8 @@ def lib():
     L.sbx_view_run.argtypes = [C.POINTER(ViewRequest), C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
     L.sbx_view_run_indexed.argtypes = [C.POINTER(ViewRequest), C.c_int, C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.POINTER(ViewIndexStats),
                                        C.c_char_p, C.c_size_t]
+    L.sbx_view_run_streamed.argtypes = [C.POINTER(ViewRequest), C.c_int, C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.POINTER(ViewIndexStats),
+                                        C.POINTER(StreamStats), C.c_char_p, C.c_size_t]
     L.sbx_validate_bam.argtypes = [C.c_char_p, C.c_int, C.POINTER(ValidateReport), C.POINTER(ValidateStats), C.c_char_p, C.c_size_t]
     L.sbx_format_validate_report.argtypes = [C.c_char_p, C.POINTER(ValidateReport), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_view_num_filter.argtypes = [C.c_char_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
@@ -339,6 +347,7 @@ def lib():
     L.sbx_import_sam.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(ImportStats), C.c_char_p, C.c_size_t]
     L.sbx_index_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.sbx_fixbins.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(FixbinsStats), C.c_char_p, C.c_size_t]
+    L.sbx_fixbins_run.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(FixbinsStats), C.POINTER(StreamStats), C.c_char_p, C.c_size_t]
     L.sbx_index_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(FastaStats), C.c_char_p, C.c_size_t]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -360,7 +369,7 @@ def lib():
                      ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats),
                      ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats), ("sbx_slice_stats", SliceStats),
                      ("sbx_view_request", ViewRequest), ("sbx_validate_report", ValidateReport), ("sbx_validate_stats", ValidateStats),
-                     ("sbx_view_index_stats", ViewIndexStats)):
+                     ("sbx_view_index_stats", ViewIndexStats), ("sbx_stream_stats", StreamStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -426,14 +435,19 @@ def build_index(bam_path, bai_path=None, device=-1, check_bins=False):
 
 def fixbins(in_path, out_path, level=-1, device=-1):
     """sbx_fixbins (`sambamba fixbins`): in_path written to out_path with the bin of every record set to reg2bin of its position and
-    CIGAR; nothing else changes.  Returns the fields of sbx_fixbins_stats as a dict."""
+    CIGAR; nothing else changes.  Returns the fields of sbx_fixbins_stats as a dict, plus n_windows, window_bytes, n_pack_launches and
+    ms_pack of sbx_stream_stats: zeros when the records stayed on the device, the figures of the streamed path when they did not fit
+    (or SBX_STREAM_WINDOW_BYTES is set)."""
     L = lib()
     st = FixbinsStats()
+    ss = StreamStats()
     err = C.create_string_buffer(512)
-    rc = L.sbx_fixbins(in_path.encode(), out_path.encode(), int(level), device, C.byref(st), err, 512)
+    rc = L.sbx_fixbins_run(in_path.encode(), out_path.encode(), int(level), device, C.byref(st), C.byref(ss), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
-    return {k: getattr(st, k) for k, _ in FixbinsStats._fields_ if k != "reserved"}
+    out = {k: getattr(st, k) for k, _ in FixbinsStats._fields_ if k != "reserved"}
+    out.update({k: getattr(ss, k) for k in STREAM_KEYS})
+    return out
 
 
 def index_fasta(path, fai_path=None, device=-1):
@@ -828,7 +842,10 @@ def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, r
     use_index (sbx_view_run_indexed): False reads the whole file, as ever; True reads only the blocks the .bai of in_path names for
     the regions or the BED file and fails with SBX_ENOINDEX (-7) without one; "auto" falls back to the whole file then.  The stats
     dict then also carries the fields of sbx_view_index_stats (blocks_in_file, blocks_read, runs, ...), and n_records_in counts the
-    records that were described.  with_stats=True makes count=True return (count, stats dict)."""
+    records that were described.  with_stats=True makes count=True return (count, stats dict).  The dict also carries n_windows,
+    window_bytes, n_pack_launches and ms_pack of sbx_stream_stats (sbx_view_run_streamed): zeros on the resident path, the figures of
+    the streamed path when a BAM or SAM output in file order did not fit the device (or SBX_STREAM_WINDOW_BYTES is set); for
+    format="sam", which has no window, n_windows counts the pieces of text written and window_bytes is the piece size."""
     if use_index not in (False, True, "auto"):
         raise ValueError("view: use_index must be False, True or 'auto'")
     if format not in ("bam", "sam"):
@@ -865,13 +882,12 @@ def view(in_path, out_path=None, *, count=False, filter=None, num_filter=None, r
     q.valid_only = int(bool(valid))
     n = C.c_uint64(0)
     ix = ViewIndexStats()
-    if use_index is False:
-        rc = L.sbx_view_run(C.byref(q), C.byref(n), C.byref(st), err, 512)
-    else:
-        rc = L.sbx_view_run_indexed(C.byref(q), VIEW_INDEX_MODES[use_index], C.byref(n), C.byref(st), C.byref(ix), err, 512)
+    ss = StreamStats()
+    rc = L.sbx_view_run_streamed(C.byref(q), VIEW_INDEX_MODES[use_index], C.byref(n), C.byref(st), C.byref(ix), C.byref(ss), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
     stats = {k: getattr(st, k) for k, _ in ViewStats._fields_ if k != "reserved"}
+    stats.update({k: getattr(ss, k) for k in STREAM_KEYS})
     if use_index is not False:
         stats.update({k: getattr(ix, k) for k, _ in ViewIndexStats._fields_})
     if count:

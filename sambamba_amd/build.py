@@ -24,7 +24,7 @@ INDEX_CLI = os.path.join(CSRC, "sbx-index")
 FIXBINS_CLI = os.path.join(CSRC, "sbx-fixbins")
 SLICE_CLI = os.path.join(CSRC, "sbx-slice")
 VALIDATE_CLI = os.path.join(CSRC, "sbx-validate")
-SOURCES = ["inflate.hip", "index.hip", "scan.hip", "lines.hip", "depth.hip", "reduce.hip", "mates.hip", "format.hip", "deflate.hip", "flagstat.hip", "sort.hip", "markdup.hip", "merge.hip", "view.hip", "sam.hip", "namesort.hip", "samparse.hip", "bins.hip", "fasta.hip", "slice.hip", "valid.hip", "engine.cpp",
+SOURCES = ["inflate.hip", "index.hip", "scan.hip", "lines.hip", "depth.hip", "reduce.hip", "mates.hip", "format.hip", "deflate.hip", "flagstat.hip", "sort.hip", "markdup.hip", "merge.hip", "view.hip", "sam.hip", "namesort.hip", "samparse.hip", "bins.hip", "fasta.hip", "slice.hip", "valid.hip", "stream.hip", "engine.cpp",
            "engine_worklist.cpp", "engine_run.cpp", "engine_stats.cpp", "engine_text.cpp", "engine_writer.cpp", "engine_sort.cpp", "engine_markdup.cpp", "engine_merge.cpp", "engine_view.cpp", "engine_import.cpp", "engine_fixbins.cpp", "engine_fasta.cpp", "engine_slice.cpp", "engine_valid.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "sbx_depth.h")]
 

@@ -6,7 +6,8 @@
 //                       the CIGAR itself.  Mismatches are counted once per wave; the lowest record number among them is kept (atomicMin).
 //   K16b k_fix_bins     one lane per record of a batch of sbx_fixbins' read pass, behind the copy of the batch into the resident
 //                       store: offset and length of the record for the writer, and the two bytes of the bin stored when they differ.
-//                       Every store of a lane lies inside its own record.
+//                       Every store of a lane lies inside its own record.  On the streamed path (BinFixArgs::bin_out) the records
+//                       are read where K1 left them and the bin of a record that changes goes to bin_out for K21 (stream.hip).
 //
 // Both read 36 bytes + name length + CIGAR per record, scattered by record; K16b writes two bytes of the records it changes.  Next to
 // the inflate and record-index kernels of the same pass this is small; NOTHING here has a measured time.
@@ -43,6 +44,7 @@ __global__ __launch_bounds__(kBinThreads) void k_fix_bins(BinFixArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * kBinThreads + threadIdx.x;
     bool bad = false, changed = false;
     unsigned long long len = 0;
+    uint32_t patch = streamc::kNoPatch;
     if (i < a.n) {
         const uint64_t at = a.out_base + i;
         const uint64_t so = (uint64_t)((int64_t)a.desc[i].rec_off + a.store_delta);
@@ -55,11 +57,12 @@ __global__ __launch_bounds__(kBinThreads) void k_fix_bins(BinFixArgs a) {
                 bad = false;
                 len = bs + 4ull;
                 changed = want != binc::stored_bin(p);
-                if (changed) { p[14] = (uint8_t)want; p[15] = (uint8_t)(want >> 8); }
+                if (changed && !a.bin_out) { p[14] = (uint8_t)want; p[15] = (uint8_t)(want >> 8); }
+                if (changed) patch = want;
             }
         }
-        a.off[at] = so;
-        a.len[at] = (uint32_t)len;
+        if (a.bin_out) a.bin_out[i] = patch;             // (K21 writes the two bytes on their way into the window)
+        else { a.off[at] = so; a.len[at] = (uint32_t)len; }
     }
     const unsigned long long bytes = block_sum<unsigned long long>(len, w_sum);
     const unsigned long long mb = __ballot(bad), mc = __ballot(changed);

@@ -1,6 +1,7 @@
 // bins.hpp -- launchers of K16 (bins.hip): the bin of every record against reg2bin of its position and CIGAR (bins_core.hpp).
 #pragma once
 #include "kernels.hpp"
+#include "stream_core.hpp"
 
 namespace sbx {
 
@@ -29,6 +30,9 @@ struct BinFixArgs {
     uint64_t* off;              // out, [out_base + i]: offset of the record in the store
     uint32_t* len;              // out: its bytes, block_size field included (0 for a record that is refused)
     unsigned long long* acc;    // [kBinFixWords]
+    uint32_t* bin_out;          // null: the resident path.  Otherwise the streamed path (engine_streamout.hpp): `store` is the batch's U
+                                // (store_delta 0, store_end its end), nothing is stored into it, off / len are not written, and
+                                // bin_out[i] = the expected bin of a record that carries another one, streamc::kNoPatch for every other
 };
 // One lane per record of a batch: bytes 14 .. 15 of the record in the store become the expected bin; records whose bin changes are
 // counted, the bytes of all records added up, a record whose name and CIGAR run past its block_size is counted as bad and left alone.

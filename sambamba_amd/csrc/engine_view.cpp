@@ -14,13 +14,17 @@
 // 64-bit offsets, and K13b writes the text piece by piece -- two device and two pinned buffers, so that the copy and the write of
 // a piece overlap the kernel of the next.
 //
+// An output in file order -- no region, one listed region, -L -- whose records do not fit the store (or SBX_STREAM_WINDOW_BYTES) keeps
+// none.  view_bam_streamed hands every batch, while it is in U, to the StreamedOutput of engine_streamout.hpp (K21, stream.hip);
+// view_sam_streamed runs K12b, K13a and K13b per batch with the batch as the store.  StreamedSelect is what the two share.
+//
 // sbx_view_run and the three calls of before it read the whole file whatever the regions say (their stats promise n_records_in =
 // the records of the file, and they need no .bai).  sbx_view_run_indexed reads only the blocks the .bai names for the regions: the
 // runs of build_runs over all regions of the call, the stretch of `*` (index_starts.hpp), joined and cut into batches by the planner
 // of view_index_core.hpp.  Both paths feed the same consumers (read_batches); K12a / K12b select over whatever was described, so the
 // result is the one of the whole-file pass as long as the file is in coordinate order -- which K12c checks on every batch that was
 // read (SBX_ENOTSORTED).  The record store of the BAM and SAM sinks is then sized by the inflated bytes of the runs' blocks.
-#include "engine_store.hpp"
+#include "engine_streamout.hpp"
 #include "index_starts.hpp"
 #include "markdup_core.hpp"
 #include "sam.hpp"
@@ -389,9 +393,274 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
     st.n_regions = sel.given(); st.n_batches = n_batches;
 }
 
+// ---- the streamed BAM sink: no store; K12a per batch, then K21 into the staging window (engine_streamout.hpp) ----
+// The output order is the file order when no region orders it: no region, one listed region, or the merged list of a BED file.
+bool in_file_order(const ViewRegions& sel) { return sel.merged || sel.list.size() <= 1; }
+
+// does the resident store of select_resident fit?  (its refusal is SBX_ENOMEM; anything else is passed on)
+bool resident_store_fits(sbx_ctx* c, const IndexedRead& rd, uint64_t hlen, uint64_t per_record) {
+    try {
+        if (rd.on) plan_store_bytes(rd.store_bytes, hlen, per_record, "selecting records of", "the blocks the index names for the regions do");
+        else plan_record_store(c, hlen, per_record, "selecting records of");
+    } catch (const Error& e) {
+        if (e.code != SBX_ENOMEM) throw;
+        return false;
+    }
+    return true;
+}
+
+// What the two streamed sinks share: per batch K19 and K12a (for the SAM sink with the group sums and their scans, which K12b
+// needs), the accumulators read back, the checks the resident path makes, raised when the batch that trips them is met; at the end
+// the errors and the counts of the stats.
+struct StreamedSelect {
+    const sbx_view_opts* opts;
+    uint64_t threshold;
+    const ViewRegions& sel;
+    bool groups;
+    DevBuf<sbx_region> d_regions;
+    DevBuf<uint32_t> d_count, d_group_entries, d_group_records;
+    DevBuf<uint64_t> d_group_entry_base, d_group_record_base;
+    DevBuf<unsigned long long> d_acc;
+    ValidPass valid;
+    EventTimer t_a;
+    unsigned long long acc[kViewAccWords] = {0}, before[kViewAccWords] = {0};       // after / in front of the last batch
+    uint64_t n_in = 0, inflated = 0;
+    uint32_t n_batches = 0;
+    bool too_many = false;
+    ViewSelectArgs a{};                                 // K12a's arguments for the last batch
+
+    StreamedSelect(const sbx_view_opts* o, uint64_t thr, const ViewRegions& regions, bool valid_only, bool with_groups, hipStream_t s)
+        : opts(o), threshold(thr), sel(regions), groups(with_groups), d_acc(kViewAccWords) {
+        upload_regions(sel, &d_regions, s);
+        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kViewAccWords * sizeof(unsigned long long), s));
+        SBX_HIP(hipStreamSynchronize(s));
+        valid.init(valid_only, s);
+    }
+    // false: the pass stops here (finish() says why)
+    bool run(sbx_ctx* c, const ViewBatch& vb, hipStream_t s, sbx_view_stats* st) {
+        const uint64_t nrec = vb.nrec;
+        const uint32_t n_groups = view_groups(nrec);
+        memcpy(before, acc, sizeof acc);
+        d_count.ensure((size_t)nrec + 2);
+        if (groups) {
+            d_group_entries.ensure(n_groups + 4); d_group_records.ensure(n_groups + 4);
+            d_group_entry_base.ensure(n_groups + 4); d_group_record_base.ensure(n_groups + 4);
+        }
+        t_a.start(s);
+        const uint16_t* d_invalid = valid.run(c, nrec, vb.u_end, s);
+        a = select_args(c, opts, threshold, sel, d_regions.p, nrec, vb.u_end, d_acc.p, d_invalid);
+        a.with_lengths = 1;
+        a.count = d_count.p;
+        if (groups) { a.group_entries = d_group_entries.p; a.group_records = d_group_records.p; }
+        launch_view_select(a, s);
+        if (groups && nrec) {
+            launch_count_scan(d_group_entries.p, n_groups, d_group_entry_base.p, s);
+            launch_count_scan(d_group_records.p, n_groups, d_group_record_base.p, s);
+        }
+        t_a.stop(s);
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        st->ms_inflate += c->stats.ms_inflate; st->ms_index += c->stats.ms_index; st->ms_select += t_a.ms();
+        n_in += nrec;
+        if (acc[kViewAccBad]) return false;
+        if (acc[kViewAccEntries] > 0xFFFFFFF0ull) { too_many = true; return false; }
+        return true;
+    }
+    void finish(sbx_view_stats* st) const {
+        if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
+        if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 output records");
+        if (acc[kViewAccEntries] != acc[kViewAccRecords])
+            throw Error(SBX_EFORMAT, "internal error: " + std::to_string(acc[kViewAccEntries]) + " entries for " + std::to_string(acc[kViewAccRecords]) + " records");
+        st->n_records_in = n_in; st->n_records_selected = acc[kViewAccRecords]; st->n_entries_out = acc[kViewAccEntries];
+        st->inflated_bytes = inflated;
+        st->n_regions = sel.given(); st->n_batches = n_batches;
+    }
+};
+
+// no more record bytes than this reach the output of a pass
+uint64_t record_bytes_max(const sbx_ctx* c, const IndexedRead& rd) {
+    const uint64_t u_total = c->blocks.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
+    return rd.on ? rd.store_bytes : u_total - u_first;
+}
+const char* iview_hint(const IndexedRead& rd) { return rd.on ? "" : "; sbx-iview reads only the blocks the index names for a region"; }
+
+void view_bam_streamed(Standalone& c, OutputGuard& out_file, const std::vector<uint8_t>& header, const sbx_view_opts* opts, uint64_t threshold,
+                       const ViewRegions& sel, const IndexedRead& rd, bool valid_only, uint64_t hook, int level, sbx_view_stats* st,
+                       sbx_stream_stats* stream_stats) {
+    const uint64_t stream_max = header.size() + record_bytes_max(c.get(), rd);
+    const StreamBudget budget(stream_max, hook, 18, "selecting records of", "18 bytes per record of it", iview_hint(rd));
+    hipStream_t s = c->stream.get();
+    StreamedOutput out(out_file, header, stream_max, budget, level, s);
+    StreamedSelect pick(opts, threshold, sel, valid_only, false, s);
+    read_batches(c.get(), rd, budget.batch_u, &pick.n_batches, &pick.inflated, [&](const ViewBatch& vb) -> bool {
+        if (!pick.run(c.get(), vb, s, st)) return false;
+        PackArgs p{};
+        p.U = c->U(); p.desc = c->d_desc.p; p.n = vb.nrec; p.u_end = vb.u_end;
+        p.count = pick.d_count.p;
+        // (the next batch's K1 / K2 overwrite U and the descriptors: add_batch returns when K21 has read them)
+        out.add_batch(p, pick.acc[kViewAccBytes] - pick.before[kViewAccBytes]);
+        return true;
+    });
+    pick.finish(st);
+    out.finish();
+    st->stream_bytes = out.stream_bytes(); st->compressed_bytes = out.compressed_bytes();
+    st->ms_deflate = out.ms_deflate();
+    if (stream_stats) *stream_stats = out.stats();
+}
+
 // Text bytes per piece of sbx_view_sam: 64 MiB (not tuned), or SBX_SAM_PIECE_BYTES (tests: a decimal number of at least 1; anything
 // else counts as unset).  Pieces are cut at line ends and written in order, so the value does not change a byte of the output.
 uint64_t sam_piece_bytes() { return env_size("SBX_SAM_PIECE_BYTES", 64ull << 20); }
+
+// The text of a set of entries (sbx_view_sam): measure() runs K13a, the offsets of the lines and the cut into pieces, and throws when
+// a record is malformed -- nothing has been written by then --; emit() runs K13b piece by piece through two device and two pinned
+// buffers, so that the copy and the write of a piece overlap the kernel of the next.  The resident sink calls the pair once over all
+// entries, the streamed sink once per batch: the buffers are kept, the figures add up.
+struct SamText {
+    uint64_t budget = sam_piece_bytes();
+    uint64_t text_bytes = 0;
+    uint32_t n_pieces = 0;
+    double ms = 0;                                      // device time of K13a, the offsets and K13b
+    DevBuf<uint32_t> d_line_len, d_n_pieces, d_first;
+    DevBuf<uint64_t> d_group, d_line_off, d_first_off;
+    DevBuf<unsigned long long> d_acc;
+    std::vector<uint32_t> first;
+    std::vector<uint64_t> first_off;
+    uint32_t pieces = 0;                                // of the entries measured last
+    DevBuf<uint8_t> d_piece[2];
+    PinnedBuf<uint8_t> h_piece[2];
+    PinnedBuf<unsigned long long> h_acc;
+    EventTimer t_a, t_b[2];
+    Event ev_copy[2];
+    Stream copy;
+
+    void measure(const SamEntries& e, hipStream_t s) {
+        const uint64_t n = e.n;
+        const uint32_t groups = group_count(n);
+        d_line_len.ensure((size_t)n + 2); d_n_pieces.ensure(1);
+        d_group.ensure(groups + 2); d_line_off.ensure((size_t)n + 2);
+        d_acc.ensure(kSamAccWords);
+        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kSamAccWords * sizeof(unsigned long long), s));
+        t_a.start(s);
+        launch_sam_measure(e, d_line_len.p, d_group.p, d_acc.p, s);
+        if (n) {
+            launch_scan64(d_group.p, groups, 0, s);
+            launch_group_offsets(d_line_len.p, d_group.p, n, 0, d_line_off.p, s);
+        }
+        t_a.stop(s);
+        launch_sam_pieces(d_line_off.p, n, budget, nullptr, nullptr, d_n_pieces.p, s);
+        unsigned long long acc[kSamAccWords] = {0};
+        pieces = 0;
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipMemcpyAsync(&pieces, d_n_pieces.p, 4, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        if (acc[kSamAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSamAccBad]));
+        if (acc[kSamAccTooLong]) throw Error(SBX_EUNSUPPORTED, "a SAM line of 4 GiB or more");
+        if (n) ms += t_a.ms();
+        d_first.ensure((size_t)pieces + 2);
+        d_first_off.ensure((size_t)pieces + 2);
+        first.assign((size_t)pieces + 1, 0);
+        first_off.assign((size_t)pieces + 1, 0);
+        launch_sam_pieces(d_line_off.p, n, budget, d_first.p, d_first_off.p, d_n_pieces.p, s);
+        SBX_HIP(hipMemcpyAsync(first.data(), d_first.p, first.size() * 4, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipMemcpyAsync(first_off.data(), d_first_off.p, first_off.size() * 8, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+    }
+    // the entries measure() saw, into f; returns when the last piece is written (the entries' bytes may then be overwritten)
+    void emit(const SamEntries& e, hipStream_t s, OutputFile& f) {
+        uint64_t max_piece = 0;
+        for (uint32_t k = 0; k < pieces; ++k) max_piece = std::max(max_piece, first_off[k + 1] - first_off[k]);
+        h_acc.ensure(2 * kSamAccWords);
+        for (int b = 0; b < 2 && b < (int)pieces; ++b) { d_piece[b].ensure((size_t)max_piece + 64); h_piece[b].ensure((size_t)max_piece + 64); }
+        if (!copy.get()) copy.create();
+        try {
+            auto finish = [&](uint32_t k) {             // piece k: its copy has arrived; check, write
+                const int b = (int)(k & 1u);
+                SBX_HIP(hipEventSynchronize(ev_copy[b].get()));
+                ms += t_b[b].ms();
+                if (h_acc.p[b * kSamAccWords + kSamAccOverrun])
+                    throw Error(SBX_EFORMAT, "internal error: a SAM line did not have the length it was measured with");
+                const size_t bytes = (size_t)(first_off[k + 1] - first_off[k]);
+                f.write(h_piece[b].p, bytes);
+            };
+            for (uint32_t k = 0; k < pieces; ++k) {
+                const int b = (int)(k & 1u);
+                t_b[b].start(s);
+                launch_sam_emit(e, d_line_len.p, d_line_off.p, first[k], first[k + 1], d_piece[b].p, d_acc.p, s);
+                t_b[b].stop(s);
+                if (k) finish(k - 1);
+                SBX_HIP(hipStreamWaitEvent(copy.get(), t_b[b].b, 0));
+                SBX_HIP(hipMemcpyAsync(h_piece[b].p, d_piece[b].p, (size_t)(first_off[k + 1] - first_off[k]), hipMemcpyDeviceToHost, copy.get()));
+                SBX_HIP(hipMemcpyAsync(h_acc.p + b * kSamAccWords, d_acc.p, kSamAccWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, copy.get()));
+                SBX_HIP(hipEventRecord(ev_copy[b].get(), copy.get()));
+            }
+            if (pieces) finish(pieces - 1);
+        } catch (...) {                                 // (the pinned buffers may die with the caller's scope: nothing may still be copying into them)
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamSynchronize(copy.get());
+            throw;
+        }
+        if (e.n) text_bytes += first_off[pieces];
+        n_pieces += pieces;
+    }
+};
+
+
+// ---- the streamed SAM sink: no store and no new kernel; per batch K12a, K12b with offsets into U, K13a, the offsets, K13b ----
+void view_sam_streamed(Standalone& c, OutputGuard& out_file, const std::string& text, const sbx_view_opts* opts, uint64_t threshold,
+                       const ViewRegions& sel, const IndexedRead& rd, bool valid_only, sbx_view_stats* st, sbx_stream_stats* stream_stats) {
+    SamText sam;
+    // next to a batch: 34 bytes per record of it (count, off, len, perm, line length and offset, the mask of -v) and the two device
+    // pieces of the text -- no encoder and no window
+    const uint64_t pieces = 2 * std::min<uint64_t>(sam.budget, 4 * record_bytes_max(c.get(), rd) + (1ull << 20)) + (8ull << 20);
+    const StreamBudget budget(pieces, 34, "selecting records of", "34 bytes per record of it and two pieces of text", iview_hint(rd));
+    hipStream_t s = c->stream.get();
+    DeviceRefNames names;
+    upload_ref_names(c->hdr.refs, s, &names);
+    StreamedSelect pick(opts, threshold, sel, valid_only, true, s);
+    DevBuf<uint64_t> d_off;
+    DevBuf<uint32_t> d_len, d_perm;
+    OutputFile f(out_file);                             // `out_file` is armed from here to the end
+    f.write(text.data(), text.size());
+    EventTimer t_b;
+    read_batches(c.get(), rd, budget.batch_u, &pick.n_batches, &pick.inflated, [&](const ViewBatch& vb) -> bool {
+        if (!pick.run(c.get(), vb, s, st)) return false;
+        const uint64_t n_sel = pick.acc[kViewAccRecords] - pick.before[kViewAccRecords];
+        if (!n_sel) return true;
+        // K12b with batch-local ordinals and offsets of U: the batch is the store
+        d_off.ensure((size_t)n_sel + 2); d_len.ensure((size_t)n_sel + 2); d_perm.ensure((size_t)n_sel + 2);
+        ViewEmitArgs b{};
+        b.s = pick.a;
+        b.group_entry_base = pick.d_group_entry_base.p; b.group_record_base = pick.d_group_record_base.p;
+        b.store_delta = 0;
+        b.record_base = 0; b.entry_base = 0;
+        b.off = d_off.p; b.len = d_len.p;
+        t_b.start(s);
+        launch_view_emit(b, s);
+        launch_iota(d_perm.p, n_sel, s);
+        t_b.stop(s);
+        const SamEntries e{c->U(), d_off.p, d_len.p, d_perm.p, n_sel, samc::RefNames{names.off.p, names.bytes.p, names.n()}};
+        sam.measure(e, s);          // (a malformed selected record of this batch: earlier batches are written by now)
+        st->ms_emit += t_b.ms();
+        // (the next batch's K1 / K2 overwrite U and the descriptors: emit returns when K13b has read them)
+        sam.emit(e, s, f);
+        return true;
+    });
+    pick.finish(st);
+    f.finish(false);
+    st->stream_bytes = sam.text_bytes;
+    st->ms_gather = sam.ms;
+    // the text has no window of its own: what is handed to the file is a piece of text
+    sbx_stream_stats ss{};
+    ss.n_windows = sam.n_pieces; ss.window_bytes = sam.budget;
+    if (getenv("SBX_TIMING")) {
+        fprintf(stderr, "[sbx] output: text_bytes=%llu n_pieces=%u piece_bytes=%llu\n", (unsigned long long)st->stream_bytes, sam.n_pieces,
+                (unsigned long long)sam.budget);
+        fprintf(stderr, "[sbx] stream: n_windows=%u window_bytes=%llu n_pack_launches=%llu ms_pack=%.3f\n", ss.n_windows,
+                (unsigned long long)ss.window_bytes, (unsigned long long)ss.n_pack_launches, ss.ms_pack);
+    }
+    if (stream_stats) *stream_stats = ss;
+}
 
 }  // namespace
 
@@ -466,7 +735,7 @@ int view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opt
 
 int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
              size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device, int valid_only,
-             int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, char* err, size_t errlen) {
+             int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, sbx_stream_stats* stream_stats, char* err, size_t errlen) {
     const bool to_stdout = !out_path || !strcmp(out_path, "-");
     const char* const path = to_stdout ? "/dev/stdout" : out_path;
     const int rc = run_entry(err, errlen, [&] {
@@ -487,6 +756,16 @@ int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter
         const uint64_t hlen = header.size();
 
         sbx_view_stats st{};
+        // in file order: the stream when the hook asks for it or the store does not fit (two or more listed regions: the store, and its refusal)
+        const uint64_t hook = stream_window_hook();
+        if (in_file_order(sel) && (hook || !resident_store_fits(c.get(), rd, hlen, 48))) {
+            view_bam_streamed(c, out_file, header, opts, threshold, sel, rd, valid_only != 0, hook, level, &st, stream_stats);
+            out_file.disarm();
+            st.ms_total_wall = (wall_now() - w0) * 1e3;
+            print_timing(st, "bam");
+            if (stats) *stats = st;
+            return;
+        }
         SelectedRecords r;
         select_resident(c, opts, threshold, sel, rd, valid_only != 0, hlen, 48, &r, &st);
         const uint64_t n = r.n;
@@ -507,7 +786,7 @@ int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter
 
 int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
              size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device, int valid_only,
-             int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, char* err, size_t errlen) {
+             int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, sbx_stream_stats* stream_stats, char* err, size_t errlen) {
     const bool to_stdout = !out_path || !strcmp(out_path, "-");
     const char* const path = to_stdout ? "/dev/stdout" : out_path;
     return run_entry(err, errlen, [&] {
@@ -525,6 +804,15 @@ int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter
             throw Error(SBX_EFORMAT, "SAM header: " + why);
         const std::vector<RefSeq> refs = c->hdr.refs;       // (select_resident lets go of the context)
         sbx_view_stats st{};
+        // in file order: the stream when the hook asks for it or the store does not fit (two or more listed regions: the store, and its refusal)
+        if (in_file_order(sel) && (stream_window_hook() || !resident_store_fits(c.get(), rd, text.size(), 48 + 12))) {
+            view_sam_streamed(c, out_file, text, opts, threshold, sel, rd, valid_only != 0, &st, stream_stats);
+            out_file.disarm();
+            st.ms_total_wall = (wall_now() - w0) * 1e3;
+            print_timing(st, "sam");
+            if (stats) *stats = st;
+            return;
+        }
         SelectedRecords r;
         select_resident(c, opts, threshold, sel, rd, valid_only != 0, text.size(), 48 + 12, &r, &st);       // (+ length and offset of every line)
         const uint64_t n = r.n;
@@ -533,83 +821,18 @@ int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter
         upload_ref_names(refs, s, &names);
         const SamEntries e{r.store.p, r.off.p, r.len.p, r.perm.p, n, samc::RefNames{names.off.p, names.bytes.p, names.n()}};
 
-        // ---- K13a over all entries, the offsets of the lines, the pieces ----
-        const uint32_t groups = group_count(n);
-        DevBuf<uint32_t> d_line_len((size_t)n + 2), d_n_pieces(1);
-        DevBuf<uint64_t> d_group(groups + 2), d_line_off((size_t)n + 2);
-        DevBuf<unsigned long long> d_acc(kSamAccWords);
-        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kSamAccWords * sizeof(unsigned long long), s));
-        EventTimer t_a;
-        t_a.start(s);
-        launch_sam_measure(e, d_line_len.p, d_group.p, d_acc.p, s);
-        if (n) {
-            launch_scan64(d_group.p, groups, 0, s);
-            launch_group_offsets(d_line_len.p, d_group.p, n, 0, d_line_off.p, s);
-        }
-        t_a.stop(s);
-        const uint64_t budget = sam_piece_bytes();
-        launch_sam_pieces(d_line_off.p, n, budget, nullptr, nullptr, d_n_pieces.p, s);
-        unsigned long long acc[kSamAccWords] = {0};
-        uint32_t n_pieces = 0;
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipMemcpyAsync(&n_pieces, d_n_pieces.p, 4, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        if (acc[kSamAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSamAccBad]));       // (before a byte is written)
-        if (acc[kSamAccTooLong]) throw Error(SBX_EUNSUPPORTED, "a SAM line of 4 GiB or more");
-        if (n) st.ms_gather += t_a.ms();
-        DevBuf<uint32_t> d_first((size_t)n_pieces + 2);
-        DevBuf<uint64_t> d_first_off((size_t)n_pieces + 2);
-        std::vector<uint32_t> first((size_t)n_pieces + 1, 0);
-        std::vector<uint64_t> first_off((size_t)n_pieces + 1, 0);
-        launch_sam_pieces(d_line_off.p, n, budget, d_first.p, d_first_off.p, d_n_pieces.p, s);
-        SBX_HIP(hipMemcpyAsync(first.data(), d_first.p, first.size() * 4, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipMemcpyAsync(first_off.data(), d_first_off.p, first_off.size() * 8, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        uint64_t max_piece = 0;
-        for (uint32_t k = 0; k < n_pieces; ++k) max_piece = std::max(max_piece, first_off[k + 1] - first_off[k]);
-
-        // ---- K13b piece by piece: while the host copies and writes piece k, the device formats piece k + 1 ----
-        DevBuf<uint8_t> d_piece[2];
-        PinnedBuf<uint8_t> h_piece[2];
-        PinnedBuf<unsigned long long> h_acc;
-        h_acc.ensure(2 * kSamAccWords);
-        for (int b = 0; b < 2 && b < (int)n_pieces; ++b) { d_piece[b].alloc((size_t)max_piece + 64); h_piece[b].ensure((size_t)max_piece + 64); }
-        EventTimer t_b[2];
-        Event ev_copy[2];
-        Stream copy;
-        copy.create();
+        // ---- K13a over all entries; then K13b piece by piece into the file, the header first ----
+        SamText sam;
+        sam.measure(e, s);                              // (a malformed selected record: SBX_EFORMAT before a byte is written)
         OutputFile f(out_file);
         f.write(text.data(), text.size());
-        try {
-            auto finish = [&](uint32_t k) {             // piece k: its copy has arrived; check, write
-                const int b = (int)(k & 1u);
-                SBX_HIP(hipEventSynchronize(ev_copy[b].get()));
-                st.ms_gather += t_b[b].ms();
-                if (h_acc.p[b * kSamAccWords + kSamAccOverrun])
-                    throw Error(SBX_EFORMAT, "internal error: a SAM line did not have the length it was measured with");
-                const size_t bytes = (size_t)(first_off[k + 1] - first_off[k]);
-                f.write(h_piece[b].p, bytes);
-            };
-            for (uint32_t k = 0; k < n_pieces; ++k) {
-                const int b = (int)(k & 1u);
-                t_b[b].start(s);
-                launch_sam_emit(e, d_line_len.p, d_line_off.p, first[k], first[k + 1], d_piece[b].p, d_acc.p, s);
-                t_b[b].stop(s);
-                if (k) finish(k - 1);
-                SBX_HIP(hipStreamWaitEvent(copy.get(), t_b[b].b, 0));
-                SBX_HIP(hipMemcpyAsync(h_piece[b].p, d_piece[b].p, (size_t)(first_off[k + 1] - first_off[k]), hipMemcpyDeviceToHost, copy.get()));
-                SBX_HIP(hipMemcpyAsync(h_acc.p + b * kSamAccWords, d_acc.p, kSamAccWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, copy.get()));
-                SBX_HIP(hipEventRecord(ev_copy[b].get(), copy.get()));
-            }
-            if (n_pieces) finish(n_pieces - 1);
-        } catch (...) {                                 // (the pinned buffers die with this scope: nothing may still be copying into them)
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamSynchronize(copy.get());
-            throw;
-        }
+        sam.emit(e, s, f);
+        st.ms_gather += sam.ms;
+        const uint32_t n_pieces = sam.n_pieces;
+        const uint64_t budget = sam.budget;
         f.finish(false);
         out_file.disarm();
-        st.stream_bytes = n ? first_off[n_pieces] : 0;
+        st.stream_bytes = sam.text_bytes;
         st.ms_total_wall = (wall_now() - w0) * 1e3;
         print_timing(st, "sam");
         if (getenv("SBX_TIMING"))
@@ -634,8 +857,9 @@ sbx_view_request request_of(int sink, const char* in_path, const char* out_path,
 
 extern "C" {
 
-int sbx_view_run_indexed(const sbx_view_request* request, int index_mode, uint64_t* count, sbx_view_stats* stats, sbx_view_index_stats* ix,
-                         char* err, size_t errlen) {
+int sbx_view_run_streamed(const sbx_view_request* request, int index_mode, uint64_t* count, sbx_view_stats* stats, sbx_view_index_stats* ix,
+                          sbx_stream_stats* stream_stats, char* err, size_t errlen) {
+    if (stream_stats) *stream_stats = sbx_stream_stats{};
     sbx_view_request q{};
     const int rc = run_entry(err, errlen, [&] {
         if (!request) throw Error(SBX_EINVAL, "null argument");
@@ -651,9 +875,14 @@ int sbx_view_run_indexed(const sbx_view_request* request, int index_mode, uint64
                           errlen);
     if (q.sink == SBX_VIEW_SINK_BAM)
         return view_bam(q.in_path, q.out_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.pg_command_line, q.level, q.with_index,
-                        q.device, q.valid_only, index_mode, ix, stats, err, errlen);
+                        q.device, q.valid_only, index_mode, ix, stats, stream_stats, err, errlen);
     return view_sam(q.in_path, q.out_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.pg_command_line, q.with_header, q.device,
-                    q.valid_only, index_mode, ix, stats, err, errlen);
+                    q.valid_only, index_mode, ix, stats, stream_stats, err, errlen);
+}
+
+int sbx_view_run_indexed(const sbx_view_request* request, int index_mode, uint64_t* count, sbx_view_stats* stats, sbx_view_index_stats* ix,
+                         char* err, size_t errlen) {
+    return sbx_view_run_streamed(request, index_mode, count, stats, ix, nullptr, err, errlen);
 }
 
 int sbx_view_run(const sbx_view_request* request, uint64_t* count, sbx_view_stats* stats, char* err, size_t errlen) {
