@@ -220,6 +220,19 @@ extern (C) nothrow @nogc {
     int sbx_fixbins(const(char)* in_path, const(char)* out_path, int level, int device, sbx_fixbins_stats* stats, char* err, size_t errlen);
     int sbx_fixbins_run(const(char)* in_path, const(char)* out_path, int level, int device, sbx_fixbins_stats* stats,
                         sbx_stream_stats* stream_stats, char* err, size_t errlen);
+    /* `sambamba subsample --type fasthash --max-cov N [-r]`, which subsample.d leaves unfinished: the coverage of the whole file, the
+       larger of that at a read's first and last position, and a hash of the read name decide (see sbx_depth.h).  remove == 0 marks
+       the dropped reads with flag 0x200; level is an addition (the reference hard-codes 9). */
+    struct sbx_subsample_stats {
+        ulong n_records; ulong n_counted; ulong n_over; ulong n_dropped; ulong n_written;
+        ulong max_cov_seen; ulong cov_array_bytes;
+        ulong inflated_bytes; ulong stream_bytes; ulong compressed_bytes;
+        uint n_batches; uint reserved;
+        double ms_inflate; double ms_index; double ms_mark; double ms_scan; double ms_verdict; double ms_deflate; double ms_total_wall;
+    }
+    int sbx_subsample(const(char)* in_path, const(char)* out_path, int max_cov, int remove, int level, int with_index,
+                      const(char)* pg_command_line, int device, sbx_subsample_stats* stats, sbx_stream_stats* stream_stats, char* err,
+                      size_t errlen);
     struct sbx_fasta_stats {
         ulong n_sequences; ulong n_lines; ulong n_bytes;
         uint n_chunks; uint reserved;

@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_markdup_stream_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats", "sbx_stream_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_markdup_stream_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats", "sbx_stream_stats", "sbx_subsample_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -600,6 +600,41 @@ int sbx_fixbins(const char* in_path, const char* out_path, int level, int device
  * record into the window: the patched record never exists in a store.  ms_gather is 0 there (the copy is ms_pack). */
 int sbx_fixbins_run(const char* in_path, const char* out_path, int level, int device, sbx_fixbins_stats* stats,
                     sbx_stream_stats* stream_stats, char* err, size_t errlen);
+
+/* ---- subsample: cap the coverage by dropping reads (`sambamba subsample --type fasthash --max-cov N [-r]`, subsample.d) ----
+ * The reference's command is unfinished (it prints debug text, never drops a read and ends in "Pileup buffer is full"); its header
+ * comment and usage text are the specification, and this is the definition:
+ * A record is COUNTED when its flag has none of 0x4, 0x200, 0x400, 0 <= ref_id < n_ref and 0 <= pos < LN[ref_id].  Its span is
+ * [pos, e), e = min(pos + max(basesCovered, 1), LN) (basesCovered: the M D N = X lengths added up in 32 bits; a sum past 2^31 is
+ * clipped by LN).  c_r(p) is the number of counted records of reference r with pos <= p < e, over the WHOLE file -- so the result
+ * does not depend on the order of the records, the input need not be sorted and no .bai is needed.  A counted record has
+ * cov = max(c(pos), c(e - 1)) >= 1 and h = the low 32 bits of the 64-bit FNV-1a hash `view -s` uses, over its name without the NUL
+ * and a seed of 0; it is KEPT iff cov <= max_cov or (uint64)h * cov < (uint64)max_cov << 32 (exact integer arithmetic).  Mates share
+ * h but not cov, so their verdicts may differ (as in VariantBam).  Records that are not counted are always kept.
+ * The output is in file order; its header is the input's with the "@PG ID:sambamba CL:<pg_command_line>" line of
+ * sbx_markdup_header_text (SO kept; NULL: no @PG line).  remove != 0: dropped records are left out.  remove == 0: every record is
+ * written and a dropped one gets flag bit 0x200 (the reference's "mark as bad quality"; depth's default filter and a second
+ * subsample then ignore it).  Nothing else changes, bins included.  level as sbx_bgzf_compress (the reference hard-codes 9);
+ * with_index != 0: out_path + ".bai" too, a pass of its own.
+ * The file is read twice in batches (K22a marks span ends in a coverage array of one uint32 per reference position plus one per
+ * reference, K22b scans it, K22c judges) and always written through the streamed writer (sbx_stream_stats above;
+ * SBX_INDEX_BATCH_BYTES, SBX_STREAM_WINDOW_BYTES and SBX_BGZF_PIECE_BLOCKS apply and change no byte).  SBX_EINVAL: max_cov <= 0, a
+ * bad level, out_path is the input.  SBX_EUNSUPPORTED: more than 2^32 records.  SBX_EFORMAT: a record whose name and CIGAR run
+ * past its block_size.  SBX_ENOMEM: the coverage array next to one minimal read batch, the encoder and a window of one piece does
+ * not fit; the message states the bytes needed and free and the coverage array's share.  On failure no output file is left.
+ * n_over: counted records with cov > max_cov; n_dropped: those of them the hash drops; n_written: records in the output;
+ * max_cov_seen: the largest cov; cov_array_bytes: bytes of the coverage array; n_batches and the inflate / index milliseconds are
+ * those of both read passes.  Milliseconds are device time (mark = K22a, scan = K22b, verdict = K22c), ms_total_wall the wall clock. */
+typedef struct {
+    uint64_t n_records, n_counted, n_over, n_dropped, n_written;
+    uint64_t max_cov_seen, cov_array_bytes;
+    uint64_t inflated_bytes, stream_bytes, compressed_bytes;
+    uint32_t n_batches, reserved;
+    double ms_inflate, ms_index, ms_mark, ms_scan, ms_verdict, ms_deflate, ms_total_wall;
+} sbx_subsample_stats;
+int sbx_subsample(const char* in_path, const char* out_path, int max_cov, int remove, int level, int with_index,
+                  const char* pg_command_line, int device, sbx_subsample_stats* stats, sbx_stream_stats* stream_stats, char* err,
+                  size_t errlen);
 /* `sambamba index -F` (buildFai, BioD bio/std/file/fai.d:78-101): the .fai of a FASTA file, its lines found and added up on the
  * device (K17).  The line terminator is "\r\n" when the first line ends in it, "\n" otherwise, for the whole file; the text is split
  * at it only (a last line without terminator is a line; with "\n" a '\r' is a byte of its line).  A line starting with '>' opens a

@@ -1,5 +1,5 @@
 """sambamba_amd -- Python harness around libsbx_depth.so, the MI355X (gfx950) engine behind
-`sambamba depth base|region|window`, `sambamba flagstat`, `sambamba sort`, `sambamba markdup`, `sambamba merge`, `sambamba view` (SAM input included), `sambamba slice`, `sambamba index` (BAM and FASTA) `sambamba fixbins` and `sambamba view -v` / `sbx-validate`.
+`sambamba depth base|region|window`, `sambamba flagstat`, `sambamba sort`, `sambamba markdup`, `sambamba merge`, `sambamba view` (SAM input included), `sambamba slice`, `sambamba index` (BAM and FASTA) `sambamba fixbins`, `sambamba subsample` and `sambamba view -v` / `sbx-validate`.
 
 The product is the C-ABI library (include/sbx_depth.h) plus the `sbx-depth` CLI, both built
 from sambamba_amd/csrc/ by sambamba_amd.build.  This package only binds the C ABI with ctypes
@@ -14,5 +14,6 @@ from ._lib import (SbxError, Depth, lib, lib_path, inflate_blocks, compile_filte
                    slice_bam, slice_cli_path,
                    import_sam, import_cli_path,
                    fixbins, index_fasta, index_cli_path, fixbins_cli_path,
+                   subsample, subsample_cli_path,
                    validate, format_validate_report, validate_cli_path, VALIDATE_CLASSES,
                    SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW)

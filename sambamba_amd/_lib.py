@@ -20,6 +20,7 @@ _IMPORT_CLI_PATH = os.path.join(HERE, "csrc", "sbx-import")
 _INDEX_CLI_PATH = os.path.join(HERE, "csrc", "sbx-index")
 _FIXBINS_CLI_PATH = os.path.join(HERE, "csrc", "sbx-fixbins")
 _VALIDATE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-validate")
+_SUBSAMPLE_CLI_PATH = os.path.join(HERE, "csrc", "sbx-subsample")
 
 SBX_MODE_BASE, SBX_MODE_REGION, SBX_MODE_WINDOW = 0, 1, 2
 SBX_FILTER_MAX_OPS = 64
@@ -175,6 +176,12 @@ class StreamStats(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("window_bytes", "n_pack_launches")] + [(k, C.c_uint32) for k in ("n_windows", "reserved")] +
                 [("ms_pack", C.c_double)])
 
+class SubsampleStats(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_records", "n_counted", "n_over", "n_dropped", "n_written", "max_cov_seen", "cov_array_bytes",
+                                           "inflated_bytes", "stream_bytes", "compressed_bytes")] +
+                [(k, C.c_uint32) for k in ("n_batches", "reserved")] +
+                [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_mark", "ms_scan", "ms_verdict", "ms_deflate", "ms_total_wall")])
+
 STREAM_KEYS = ("n_windows", "window_bytes", "n_pack_launches", "ms_pack")
 
 VIEW_INDEX_MODES = {False: 0, True: 1, "auto": 2}       # SBX_VIEW_INDEX_OFF / _REQUIRED / _AUTO
@@ -195,6 +202,7 @@ EXPORTS = [
     "sbx_slice_bam",
     "sbx_import_sam",
     "sbx_index_bam", "sbx_fixbins", "sbx_fixbins_run", "sbx_index_fasta",
+    "sbx_subsample",
 ]
 
 _lib = None
@@ -258,6 +266,10 @@ def fixbins_cli_path():
 
 def validate_cli_path():
     return _VALIDATE_CLI_PATH
+
+
+def subsample_cli_path():
+    return _SUBSAMPLE_CLI_PATH
 
 
 def lib():
@@ -348,6 +360,8 @@ def lib():
     L.sbx_index_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.sbx_fixbins.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(FixbinsStats), C.c_char_p, C.c_size_t]
     L.sbx_fixbins_run.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(FixbinsStats), C.POINTER(StreamStats), C.c_char_p, C.c_size_t]
+    L.sbx_subsample.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int, C.POINTER(SubsampleStats),
+                                C.POINTER(StreamStats), C.c_char_p, C.c_size_t]
     L.sbx_index_fasta.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(FastaStats), C.c_char_p, C.c_size_t]
     L.sbx_prefetch_interval.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
     L.sbx_run_interval_owned.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -369,7 +383,8 @@ def lib():
                      ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats),
                      ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats), ("sbx_slice_stats", SliceStats),
                      ("sbx_view_request", ViewRequest), ("sbx_validate_report", ValidateReport), ("sbx_validate_stats", ValidateStats),
-                     ("sbx_view_index_stats", ViewIndexStats), ("sbx_stream_stats", StreamStats)):
+                     ("sbx_view_index_stats", ViewIndexStats), ("sbx_stream_stats", StreamStats),
+                     ("sbx_subsample_stats", SubsampleStats)):
         if L.sbx_abi_sizeof(name.encode()) != C.sizeof(ty):
             raise ImportError("ctypes layout of %s (%d bytes) differs from libsbx_depth.so (%d bytes)" % (
                 name, C.sizeof(ty), L.sbx_abi_sizeof(name.encode())))
@@ -446,6 +461,28 @@ def fixbins(in_path, out_path, level=-1, device=-1):
     if rc != 0:
         raise SbxError(rc, err.value.decode())
     out = {k: getattr(st, k) for k, _ in FixbinsStats._fields_ if k != "reserved"}
+    out.update({k: getattr(ss, k) for k in STREAM_KEYS})
+    return out
+
+
+def subsample(in_path, out_path, max_cov, *, remove=False, level=-1, index=False, command_line=None, device=-1):
+    """sbx_subsample (`sambamba subsample --type fasthash --max-cov N [-r]`): in_path written to out_path in file order with the
+    coverage capped at about max_cov.  The coverage is counted over the whole file from the records that are mapped, pass QC and are
+    no duplicates; such a record whose coverage (the larger of that at its first and at its last position) exceeds max_cov is kept
+    with probability max_cov / coverage, decided by a hash of its name -- so mates share the hash, not necessarily the verdict.
+    remove=True leaves the dropped records out; otherwise they are written with flag bit 0x200 set.  command_line: the CL of the @PG
+    line (None: no @PG line); index=True also writes out_path + ".bai".  Returns the fields of sbx_subsample_stats as a dict, plus
+    n_windows, window_bytes, n_pack_launches and ms_pack of sbx_stream_stats (the output is always streamed)."""
+    L = lib()
+    st = SubsampleStats()
+    ss = StreamStats()
+    err = C.create_string_buffer(1024)
+    cl = command_line.encode() if command_line is not None else None
+    rc = L.sbx_subsample(in_path.encode(), out_path.encode(), int(max_cov), int(bool(remove)), int(level), int(bool(index)), cl, device,
+                         C.byref(st), C.byref(ss), err, 1024)
+    if rc != 0:
+        raise SbxError(rc, err.value.decode())
+    out = {k: getattr(st, k) for k, _ in SubsampleStats._fields_ if k != "reserved"}
     out.update({k: getattr(ss, k) for k in STREAM_KEYS})
     return out
 

@@ -1,4 +1,4 @@
-"""Build libsbx_depth.so (HIP kernels + C ABI) and the sbx-depth / sbx-flagstat / sbx-sort / sbx-markdup / sbx-merge / sbx-view / sbx-sam / sbx-iview / sbx-nsort / sbx-import / sbx-index / sbx-fixbins / sbx-slice / sbx-validate CLIs for gfx950 with hipcc.
+"""Build libsbx_depth.so (HIP kernels + C ABI) and the sbx-depth / sbx-flagstat / sbx-sort / sbx-markdup / sbx-merge / sbx-view / sbx-sam / sbx-iview / sbx-nsort / sbx-import / sbx-index / sbx-fixbins / sbx-slice / sbx-validate / sbx-subsample CLIs for gfx950 with hipcc.
 
 Usage: python -m sambamba_amd.build   (or sambamba_amd.build.build())
 Outputs are written in-tree (sambamba_amd/csrc/) so they travel with gpurun snapshots.
@@ -24,8 +24,9 @@ INDEX_CLI = os.path.join(CSRC, "sbx-index")
 FIXBINS_CLI = os.path.join(CSRC, "sbx-fixbins")
 SLICE_CLI = os.path.join(CSRC, "sbx-slice")
 VALIDATE_CLI = os.path.join(CSRC, "sbx-validate")
-SOURCES = ["inflate.hip", "index.hip", "scan.hip", "lines.hip", "depth.hip", "reduce.hip", "mates.hip", "format.hip", "deflate.hip", "flagstat.hip", "sort.hip", "markdup.hip", "merge.hip", "view.hip", "sam.hip", "namesort.hip", "samparse.hip", "bins.hip", "fasta.hip", "slice.hip", "valid.hip", "stream.hip", "engine.cpp",
-           "engine_worklist.cpp", "engine_run.cpp", "engine_stats.cpp", "engine_text.cpp", "engine_writer.cpp", "engine_sort.cpp", "engine_markdup.cpp", "engine_merge.cpp", "engine_view.cpp", "engine_import.cpp", "engine_fixbins.cpp", "engine_fasta.cpp", "engine_slice.cpp", "engine_valid.cpp"]
+SUBSAMPLE_CLI = os.path.join(CSRC, "sbx-subsample")
+SOURCES = ["inflate.hip", "index.hip", "scan.hip", "lines.hip", "depth.hip", "reduce.hip", "mates.hip", "format.hip", "deflate.hip", "flagstat.hip", "sort.hip", "markdup.hip", "merge.hip", "view.hip", "sam.hip", "namesort.hip", "samparse.hip", "bins.hip", "fasta.hip", "slice.hip", "valid.hip", "stream.hip", "subsample.hip", "engine.cpp",
+           "engine_worklist.cpp", "engine_run.cpp", "engine_stats.cpp", "engine_text.cpp", "engine_writer.cpp", "engine_sort.cpp", "engine_markdup.cpp", "engine_merge.cpp", "engine_view.cpp", "engine_import.cpp", "engine_fixbins.cpp", "engine_fasta.cpp", "engine_slice.cpp", "engine_valid.cpp", "engine_subsample.cpp"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "sbx_depth.h")]
 
 
@@ -72,7 +73,7 @@ def build(force=False, verbose=False):
                            (MARKDUP_CLI, "markdup_cli.cpp", []), (MERGE_CLI, "merge_cli.cpp", []), (VIEW_CLI, "view_cli.cpp", []),
                            (SAM_CLI, "view_cli.cpp", ["-DSBX_VIEW_SAM=1"]), (IVIEW_CLI, "view_cli.cpp", ["-DSBX_VIEW_INDEXED=1"]), (NSORT_CLI, "sort_cli.cpp", ["-DSBX_SORT_BY_NAME=1"]),
                            (IMPORT_CLI, "import_cli.cpp", []), (INDEX_CLI, "index_cli.cpp", []), (FIXBINS_CLI, "fixbins_cli.cpp", []), (SLICE_CLI, "slice_cli.cpp", []),
-                           (VALIDATE_CLI, "validate_cli.cpp", [])):
+                           (VALIDATE_CLI, "validate_cli.cpp", []), (SUBSAMPLE_CLI, "subsample_cli.cpp", [])):
         cli_src = os.path.join(CSRC, src)
         if os.path.exists(cli_src) and (force or _stale(cli, [cli_src, LIB] + deps)):
             cmd = [_hipcc(), "-O2", "-std=c++17"] + defs + ["-o", cli, cli_src, "-L" + CSRC, "-lsbx_depth",

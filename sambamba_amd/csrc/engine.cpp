@@ -70,6 +70,7 @@ size_t sbx_abi_sizeof(const char* name) {
     if (n == "sbx_validate_stats") return sizeof(sbx_validate_stats);
     if (n == "sbx_view_index_stats") return sizeof(sbx_view_index_stats);
     if (n == "sbx_stream_stats") return sizeof(sbx_stream_stats);
+    if (n == "sbx_subsample_stats") return sizeof(sbx_subsample_stats);
     return 0;
 }
 

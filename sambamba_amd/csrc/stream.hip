@@ -20,7 +20,8 @@
 // disjoint stretches clipped each on its own -- and lane 0 of the record's sixteen writes the two bytes, each only if it lies in
 // [w0, w1).  So no byte of the window has two writers and the patch cannot race the copy, without the copy loop having to compare
 // addresses per byte; the price is a second, 14-byte call of copy_span16 for the records that change, and none for those that do not
-// (their bin is streamc::kNoPatch: one stretch).
+// (their bin is streamc::kNoPatch: one stretch).  PackArgs::patch_off moves the patched pair: 14 for the bin, 18 for the flag
+// (subsample marks a dropped record there); the two stretches are then [0, patch_off) and [patch_off + 2, len).
 //
 // Bytes moved (a batch of n records, s of them selected, b selected bytes, written through k windows): K21a reads 32 n (descriptor)
 // + 4 n (verdict) + 4 s scattered words of U and writes 4 n + 8 n / 256; K21b reads 4 n and writes 8 n; K21c reads, per window the
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_records(PackArgs a) {
         if (len && d < a.w1 && d + len > a.w0) {
             const uint8_t* rec = a.U + a.desc[i].rec_off;       // (K21a: the whole frame lies inside the batch)
             streamc::PackPlan p;
-            streamc::plan_record(d, len, a.w0, a.w1, a.bin ? a.bin[i] : streamc::kNoPatch, &p);
+            streamc::plan_record(d, len, a.w0, a.w1, a.bin ? a.bin[i] : streamc::kNoPatch, &p, a.patch_off);
             for (uint32_t k = 0; k < p.n_spans; ++k) copy_span16(a.window + p.span[k].dst, rec + p.span[k].src, p.span[k].len, l);
             if (l == 0) {
                 for (uint32_t k = 0; k < p.n_bytes; ++k) a.window[p.byte_dst[k]] = p.byte_val[k];

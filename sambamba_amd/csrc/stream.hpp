@@ -16,7 +16,8 @@ struct PackArgs {
     uint64_t n;                     // records of the batch
     uint64_t u_end;                 // no record of the batch ends behind this offset of U
     const uint32_t* count;          // [n] K12a's verdict (ViewSelectArgs::count; 0: not selected); null: every record is selected
-    const uint32_t* bin;            // [n] streamc::kNoPatch or the value of the record's bin field; null: no record is patched
+    const uint32_t* bin;            // [n] streamc::kNoPatch or the value of the record's 16-bit field at patch_off; null: no record is patched
+    uint32_t patch_off = streamc::kBinOffset;      // byte offset of that field in the record: the bin (14), or streamc::kFlagOffset
     uint64_t stream_base;           // where the batch's first selected record starts in the output stream
     uint64_t* group_sum;            // [pack_groups(n) + 1] scratch of launch_pack_offsets
     uint64_t* dest;                 // [n + 1] launch_pack_offsets -> launch_pack_records: start of the record in the output stream

@@ -6,6 +6,7 @@
 // [w0, w1) in at most one stretch (sortc::clip_to_piece).  With a bin patch the record's bytes 14 and 15 are NOT part of any copy:
 // the record is copied as two stretches, [0, 14) and [16, len), each clipped on its own, and the two bytes are written one by one,
 // each only when its place in the stream lies inside the window -- so no byte of the window is written twice, whatever the clip.
+// The patch is 16 bits at a byte offset the caller names: 14, the bin (fixbins), or 18, the flag (subsample); the same holds there.
 #pragma once
 #include "sort_core.hpp"
 
@@ -14,6 +15,7 @@ namespace streamc {
 
 constexpr uint32_t kNoPatch = 0xFFFFFFFFu;      // PackArgs::bin of a record whose bin stays as it is
 constexpr uint32_t kBinOffset = 14;             // the bin field: bytes 14 and 15 of a record, block_size field included
+constexpr uint32_t kFlagOffset = 18;            // the flag field: bytes 18 and 19
 
 struct PackPlan {
     uint32_t n_spans;               // 0 .. 2
@@ -28,9 +30,9 @@ struct PackPlan {
     }
 };
 
-// What the window [w0, w1) receives of a record of len bytes (>= 16) that starts at byte dest of the stream; bin: kNoPatch, or the
-// value bytes 14 .. 15 take (little endian).
-SBX_SORT_HD void plan_record(uint64_t dest, uint64_t len, uint64_t w0, uint64_t w1, uint32_t bin, PackPlan* p) {
+// What the window [w0, w1) receives of a record of len bytes (>= patch_off + 2) that starts at byte dest of the stream; bin: kNoPatch,
+// or the value bytes patch_off .. patch_off + 1 take (little endian).
+SBX_SORT_HD void plan_record(uint64_t dest, uint64_t len, uint64_t w0, uint64_t w1, uint32_t bin, PackPlan* p, uint32_t patch_off = kBinOffset) {
     p->n_spans = 0;
     p->n_bytes = 0;
     if (bin == kNoPatch) {
@@ -38,13 +40,13 @@ SBX_SORT_HD void plan_record(uint64_t dest, uint64_t len, uint64_t w0, uint64_t 
         return;
     }
     sortc::PieceClip c;
-    if (sortc::clip_to_piece(dest, dest + kBinOffset, w0, w1, &c)) p->span[p->n_spans++] = c;
-    if (sortc::clip_to_piece(dest + kBinOffset + 2, dest + len, w0, w1, &c)) {
-        c.src += kBinOffset + 2;
+    if (sortc::clip_to_piece(dest, dest + patch_off, w0, w1, &c)) p->span[p->n_spans++] = c;
+    if (sortc::clip_to_piece(dest + patch_off + 2, dest + len, w0, w1, &c)) {
+        c.src += patch_off + 2;
         p->span[p->n_spans++] = c;
     }
     for (uint32_t k = 0; k < 2; ++k) {
-        const uint64_t at = dest + kBinOffset + k;
+        const uint64_t at = dest + patch_off + k;
         if (at >= w0 && at < w1) {
             p->byte_dst[p->n_bytes] = at - w0;
             p->byte_val[p->n_bytes] = (uint8_t)(bin >> (8 * k));
