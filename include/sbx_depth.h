@@ -133,7 +133,8 @@ typedef struct {
 /* ---- codec seam -------------------------------------------------------------
  * Batched replacement of decompressBgzfBlock (block.d:127-216): raw-deflate (RFC 1951,
  * zlib windowBits = -15) payloads comp[comp_off[i] .. +comp_len[i]) are inflated on the
- * device into out[out_off[i] .. +isize[i]).  All pointers are host memory.  As in the
+ * device into out[out_off[i] .. +isize[i]); bytes of out[0, max end) outside these ranges
+ * are kept (they pass through device memory with the blocks).  All pointers are host memory.  As in the
  * reference's release build the CRC32 is not verified (block.d:187).  Returns
  * SBX_EFORMAT if any payload is not a valid deflate stream of exactly isize[i] bytes. */
 int sbx_inflate_blocks(const uint8_t* comp, const uint64_t* comp_off, const uint32_t* comp_len,

@@ -91,6 +91,9 @@ int sbx_inflate_blocks(const uint8_t* comp, const uint64_t* comp_off, const uint
         DevBuf<uint32_t> d_clen(n_blocks), d_isz(n_blocks), d_st(n_blocks);
         SBX_HIP(hipMemset(d_in.p + in_end, 0, 64));
         SBX_HIP(hipMemcpy(d_in.p, comp, in_end, hipMemcpyHostToDevice));
+        // (the caller's bytes between and around the blocks make the round trip through the device buffer: a kernel that wrote outside a
+        // block's range would show in them -- tests/test_gpu_inflate_writeout.py)
+        SBX_HIP(hipMemcpy(d_out.p, out, out_end, hipMemcpyHostToDevice));
         SBX_HIP(hipMemcpy(d_coff.p, comp_off, n_blocks * 8ull, hipMemcpyHostToDevice));
         SBX_HIP(hipMemcpy(d_ooff.p, out_off, n_blocks * 8ull, hipMemcpyHostToDevice));
         SBX_HIP(hipMemcpy(d_clen.p, comp_len, n_blocks * 4ull, hipMemcpyHostToDevice));
@@ -101,9 +104,8 @@ int sbx_inflate_blocks(const uint8_t* comp, const uint64_t* comp_off, const uint
         SBX_HIP(hipMemcpy(st.data(), d_st.p, n_blocks * 4ull, hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < n_blocks; ++i)
             if (st[i]) throw Error(SBX_EFORMAT, "block " + std::to_string(i) + ": " + inflate_status_string(st[i]));
-        // copy out exactly the produced ranges (blocks may be sparse in `out`)
-        for (uint32_t i = 0; i < n_blocks; ++i)
-            if (isize[i]) SBX_HIP(hipMemcpy(out + out_off[i], d_out.p + out_off[i], isize[i], hipMemcpyDeviceToHost));
+        // (blocks may be sparse in `out`: what lies between them comes back as it went in)
+        SBX_HIP(hipMemcpy(out, d_out.p, out_end, hipMemcpyDeviceToHost));
         return SBX_OK;
     } catch (const Error& e) {
         set_err(err, errlen, e.what());

@@ -950,7 +950,9 @@ __device__ __forceinline__ void wave_copy(uint8_t* d, const uint8_t* s, uint32_t
 // (kAblate: tools/k1_lab compiles parts of the batch loop out to time them; 0 in the product)
 // (kTail16: the second 16 bytes of a 17 .. 32-byte own-lane copy as ONE 16-byte word at offset n - 16 -- it overlaps what the first step
 // copied -- instead of a second Short16 step: 3.16 -> 3.05 ms at 40 Mbp, profiles/round6/call_j_k1b_tail16_40Mbp.jsonl; false: the A/B partner)
-template <uint32_t kHist, uint32_t kSpanMax, bool kOwn32, bool kExact, uint32_t kAblate = 0, bool kTail16 = true>
+// (kCarry: phase C writes aligned 16-byte groups and carries the < 16 bytes behind the last one into the next batch -- round 7,
+// profiles/round7/README.md; false: the write-out of rounds 1-6, the A/B partner and what kAblate 128 / 256 take apart)
+template <uint32_t kHist, uint32_t kSpanMax, bool kOwn32, bool kExact, uint32_t kAblate = 0, bool kTail16 = true, bool kCarry = true>
 __device__ __forceinline__ void lz77_resolve_body(
     const uint8_t* __restrict__ lit_stream, const uint32_t* __restrict__ ent_stream, const uint32_t* __restrict__ n_entries,
     const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ isize, uint32_t n_blocks, uint32_t block0,
@@ -1153,16 +1155,32 @@ __device__ __forceinline__ void lz77_resolve_body(
                 }
             }
         }
-        // ---- phase C: the finished span goes to HBM, contiguous ------------------------------------------------
-        {
+        // ---- phase C: what is finished goes to HBM, contiguous, in 16-byte groups at aligned addresses -------------
+        // (lz::plan_writeout: everything up to the last aligned address; the < 16 bytes behind it stay in the window -- it keeps kHist
+        // bytes behind opos, and the slide's nb = (opos - kHist) & ~15 lies below wpos > opos - 16 -- and leave with the next batch.
+        // Single bytes only in front of the block's first aligned address and behind its last one, a lane each.)
+        const uint32_t a16 = (uint32_t)(uintptr_t)o & 15u;
+        if (kCarry) {
+            // (wpos, the position up to which the block is in HBM, is not carried in a register: between batches it is opos rounded down
+            // to an aligned address, 0 in front of the first one -- what plan_writeout's `next` was, tests/cpp/lz77_writeout_host.cpp)
+            // (the plan is wave-uniform arithmetic: on the scalar unit, it costs the batch loop no vector register)
+            const uint32_t ua = __builtin_amdgcn_readfirstlane(a16), uo = __builtin_amdgcn_readfirstlane(opos);
+            const uint32_t al = (ua + uo) & ~15u, wpos = al > ua ? al - ua : 0u;
+            const lz::WritePlan wp = lz::plan_writeout(ua, wpos, uo, __builtin_amdgcn_readfirstlane(span),
+                                                       __builtin_amdgcn_readfirstlane(e0) >= __builtin_amdgcn_readfirstlane(ne));
+            if (!(kAblate & 8u)) lz::writeout_lane(wp, lane, buf, base, o);
+        } else {
+            // (until round 7: the batch's own span at whatever alignment o + opos has, a serial byte tail per batch; kAblate 128: without
+            // the tail, 256: from the 16-byte group o + opos lies in -- wrong bytes, the traffic of aligned stores)
             const uint8_t* sp = buf + (opos - base);
             uint8_t* dp = o + opos;
+            if (kAblate & 256u) dp -= (a16 + opos) & 15u;
             for (uint32_t i = 16 * lane; !(kAblate & 8u) && i < span; i += 1024) {
                 if (i + 16 <= span) {
                     u32x4 v;
                     __builtin_memcpy(&v, sp + i, 16);
                     __builtin_memcpy(dp + i, &v, 16);
-                } else {
+                } else if (!(kAblate & 128u)) {
                     for (uint32_t k = i; k < span; ++k) dp[k] = sp[k];
                 }
             }

@@ -96,5 +96,44 @@ SBX_LZ_HD void periodic16(uint32_t x0, uint32_t x1, uint32_t len, uint32_t s0, u
     }
 }
 
+// The write-out of K1b (phase C of a batch): which bytes of the block go from the LDS window to HBM now, and how.  Positions are
+// block-relative; `a` is the byte address of the block's first output byte mod 16, `wpos` the position up to which the block is in HBM,
+// [opos, opos + span) what the batch just finished.  Everything up to the last position at which the ABSOLUTE address is a multiple of 16
+// is written, as 16-byte groups at aligned addresses [g_lo, g_hi); what is left over (< 16 bytes) is carried: it stays in the window
+// -- the window keeps kHist bytes behind opos -- and leaves with the next batch.  Two places are ragged, once per block each: the bytes
+// in front of the block's first aligned address ([h_lo, g_lo), with the first groups) and, with the last batch, the bytes behind the
+// last one ([g_hi, t_hi)); both are < 16 single bytes and lie inside the block, so the group a block shares with its neighbour is
+// written by each for its own bytes only.  `next` is the new wpos.
+struct WritePlan { uint32_t h_lo, g_lo, g_hi, t_hi, next; };
+SBX_LZ_HD WritePlan plan_writeout(uint32_t a, uint32_t wpos, uint32_t opos, uint32_t span, bool last) {
+    const uint32_t end = opos + span;
+    const uint32_t up = ((a + wpos + 15u) & ~15u) - a;            // first aligned position at or behind wpos (== wpos but at the head)
+    WritePlan p;
+    p.h_lo = wpos;
+    if (up > end) {                                                // not one aligned address in [wpos, end]: all single bytes, or all carried
+        p.g_lo = p.g_hi = p.t_hi = p.next = last ? end : wpos;
+        return p;
+    }
+    p.g_lo = up;
+    p.g_hi = ((a + end) & ~15u) - a;                               // >= up: (a + up) is a multiple of 16 and <= a + end
+    p.t_hi = last ? end : p.g_hi;
+    p.next = p.t_hi;
+    return p;
+}
+// What lane `lane` of the 64 stores of a plan: groups in rows of 1024 bytes, one per lane; the single bytes of the head by lanes 0 .. 15,
+// those of the tail by lanes 16 .. 31.  `win` holds position `base` at offset 0 (the wave's window), `o` is the block's first output byte.
+struct W4 { uint32_t x, y, z, w; };
+SBX_LZ_HD void writeout_lane(const WritePlan& wp, uint32_t lane, const uint8_t* win, uint32_t base, uint8_t* o) {
+    for (uint32_t p = wp.g_lo + 16u * lane; p < wp.g_hi; p += 1024u) {
+        W4 v;
+        __builtin_memcpy(&v, win + (p - base), 16);
+        __builtin_memcpy(__builtin_assume_aligned(o + p, 16), &v, 16);
+    }
+    if (wp.g_lo != wp.h_lo || wp.t_hi != wp.g_hi) {
+        const uint32_t p = lane < 16u ? wp.h_lo + lane : wp.g_hi + (lane - 16u);
+        if (lane < 16u ? p < wp.g_lo : p < wp.t_hi) o[p] = win[p - base];
+    }
+}
+
 }  // namespace lz
 }  // namespace sbx

@@ -30,6 +30,13 @@ __global__ __launch_bounds__(kResThreads) __attribute__((amdgpu_waves_per_eu(8, 
     lz77_resolve_body<kHistDefault, kSpanDefault, true, true, kAblate, false>(SBX_LZ77_PASS);
 }
 
+// the write-out of rounds 1-6 (kCarry = false: the batch's span at its own byte alignment, a serial byte tail per batch) -- the A/B partner
+// of the carried, aligned write-out, and what kAblate 128 (no byte tail) and 256 (stores rounded down to 16 bytes) take apart
+template <uint32_t kAblate>
+__global__ __launch_bounds__(kResThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_lab_k1b_r6(SBX_LZ77_ARGS) {
+    lz77_resolve_body<kHistDefault, kSpanDefault, true, true, kAblate, true, false>(SBX_LZ77_PASS);
+}
+
 // window geometry variants of the product body
 template <uint32_t kHist, uint32_t kSpan>
 __global__ __launch_bounds__(kResThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_lab_k1b_geo(SBX_LZ77_ARGS) {
@@ -79,6 +86,18 @@ struct Lab {
             hipLaunchKernelGGL((k_lab_k1b_t16<0>), grid, block, lds, stream, a.lit, a.ent, a.nent, a.out_off, a.isize, a.n_blocks, a.block0, a.out, a.status);
         });
         printf("{\"kernel\": \"k1b\", \"variant\": \"two Short16 steps\", \"ms_best\": %.4f, \"ms_mean\": %.4f}\n", ms, last_mean);
+        if (verify) check();
+        fflush(stdout);
+    }
+    template <uint32_t kAblate>
+    void k1b_r6(const char* what, bool verify = false) {
+        const uint32_t per = kResThreads / 64;
+        dim3 grid((a.n_blocks + per - 1) / per), block(kResThreads);
+        const size_t lds = (size_t)per * (kHistDefault + 1024u + kSpanDefault + 16u) + 128 + (size_t)per * 256;
+        const double ms = time([&] {
+            hipLaunchKernelGGL((k_lab_k1b_r6<kAblate>), grid, block, lds, stream, a.lit, a.ent, a.nent, a.out_off, a.isize, a.n_blocks, a.block0, a.out, a.status);
+        });
+        printf("{\"kernel\": \"k1b\", \"writeout\": \"round 6\", \"ablate\": %u, \"what\": \"%s\", \"ms_best\": %.4f, \"ms_mean\": %.4f}\n", kAblate, what, ms, last_mean);
         if (verify) check();
         fflush(stdout);
     }
@@ -164,6 +183,17 @@ int main(int argc, char** argv) {
             lab.k1b_geo<2048, 2048>(true);
             lab.k1b_geo<3072, 1536>();
             lab.k1b_geo<4096, 1536>();
+        }
+        if (argc > 3 && std::string(argv[3]) == "writeout") {
+            // round 7: what the per-batch byte tail and the misaligned stores of the old write-out cost, and the carried write-out next to it
+            lab.k1b_r6<0>("round 6's write-out", true);
+            lab.k1b_r6<128>("... no byte tail");
+            lab.k1b_r6<256>("... stores rounded down to 16 bytes");
+            lab.k1b_r6<128 | 256>("... no byte tail, stores rounded down");
+            lab.k1b_r6<8>("... no phase C");
+            lab.k1b<8>("the product body, no phase C");
+            lab.k1b_r6<0>("round 6's write-out, again");
+            lab.k1b<0>("the product body, a third time", true);
         }
         if (argc > 3 && std::string(argv[3]) == "ablate") {
             lab.k1b<1>("no literal copies (own + coop)");
