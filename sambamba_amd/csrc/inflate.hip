@@ -277,12 +277,14 @@ struct DistSyms {
 };
 
 // Build one canonical code from `n` code lengths in lens[] (global scratch, 1 byte each): symbol
-// permutation to LDS, limits/deltas to registers.  Returns false on an over-subscribed code.
-// (Incomplete codes are accepted, as zlib accepts the single-code distance tree; an unused code
-// decodes as "invalid symbol".)
+// permutation to LDS, limits/deltas to registers.  Returns false on a code zlib's inflate_table refuses:
+// an over-subscribed one, and an incomplete one unless it is a single code of one bit or -- the distance
+// code of a block of literals -- has no codes at all (`fixed`: the fixed code's 30 distance codes of 5
+// bits are RFC 1951's own).  An unused code decodes as "invalid symbol" / "invalid distance" in the
+// symbol loop.
 // *complete_within = the code is complete using lengths <= kWithin only (limit[kWithin] == 2^15).
 template <bool kIsLit, int kWithin>
-__device__ __forceinline__ bool build_code(const uint8_t* lens, int n, uint8_t* lds, DistSyms& DS, Code& C, bool* complete_within) {
+__device__ __forceinline__ bool build_code(const uint8_t* lens, int n, bool fixed, uint8_t* lds, DistSyms& DS, Code& C, bool* complete_within) {
     Pack16 tmp;
     tmp.clear();
     for (int s = 0; s < n; ++s) tmp.add(lens[s] & 15u, 1u);
@@ -296,7 +298,7 @@ __device__ __forceinline__ bool build_code(const uint8_t* lens, int n, uint8_t* 
     uint32_t lim[17], D[18];
 #pragma unroll
     for (int l = 1; l <= 15; ++l) {
-        left = (left << 1) - (int32_t)cnt[l];
+        left = left * 2 - (int32_t)cnt[l];
         if (left < 0) ok = false;
         lim[l] = (first + cnt[l]) << (15 - l);
         D[l] = offs - first;                   // delta of length l (mod 2^16 is all that matters)
@@ -316,6 +318,7 @@ __device__ __forceinline__ bool build_code(const uint8_t* lens, int n, uint8_t* 
     C.d1 = D[1] & 0x1FFu;
     *complete_within = lim[kWithin] == 32768u;
     if (!ok) return false;
+    if (left != 0 && !fixed && !(offs == 1u && cnt[1] == 1u) && !(!kIsLit && offs == 0u)) return false;
     if (kIsLit) {
         for (int i = 0; i < kLitSymBytes / 4; ++i) ((uint32_t*)(lds + kLitSymOff))[i] = 0;
     }
@@ -619,8 +622,8 @@ __global__ __launch_bounds__(kInfThreads) void k_huffman_decode(
             int32_t left = 1;
             bool ok = true;
 #pragma unroll
-            for (int l = 1; l <= 7; ++l) { left = (left << 1) - (int32_t)ccnt[l]; if (left < 0) ok = false; }
-            if (!ok) { err = INF_BAD_CODELENS; active = false; dyn = false; }
+            for (int l = 1; l <= 7; ++l) { left = left * 2 - (int32_t)ccnt[l]; if (left < 0) ok = false; }
+            if (!ok || left != 0) { err = INF_BAD_CODELENS; active = false; dyn = false; }      // (incomplete: refused as in zlib)
         }
         {
             int i = 0;
@@ -673,8 +676,8 @@ __global__ __launch_bounds__(kInfThreads) void k_huffman_decode(
         bool sym_loop = huff && active;
         bool lit_in_14 = true, dist_in_12 = true;
         if (sym_loop) {
-            if (!build_code<true, 14>(lens, nlit, lds, DS, CL, &lit_in_14)) { err = INF_BAD_CODELENS; active = false; sym_loop = false; }
-            else if (!build_code<false, 12>(lens + nlit, ndist, lds, DS, CD, &dist_in_12)) { err = INF_BAD_CODELENS; active = false; sym_loop = false; }
+            if (!build_code<true, 14>(lens, nlit, btype == 1, lds, DS, CL, &lit_in_14)) { err = INF_BAD_CODELENS; active = false; sym_loop = false; }
+            else if (!build_code<false, 12>(lens + nlit, ndist, btype == 1, lds, DS, CD, &dist_in_12)) { err = INF_BAD_CODELENS; active = false; sym_loop = false; }
         }
         // wave-uniform: every decoding lane's code is complete within 14 / 12 bits (decode_len)
         // (in scalar registers: a flag the compiler keeps as a lane mask costs two vector instructions per test)

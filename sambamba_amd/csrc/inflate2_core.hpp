@@ -178,6 +178,9 @@ struct Lane {
     uint32_t lit_flushed, ent_flushed;      // 16-byte groups written to the streams
     uint8_t* lit;
     uint32_t* ent;
+#if !defined(__HIP_DEVICE_COMPILE__)
+    uint32_t general_loops;         // CPU harness only: deflate blocks decoded with the general form of the symbol loop
+#endif
 
     SBX_HD uint32_t& dw(int off, uint32_t j) const { return *(uint32_t*)(W + off + 256u * j + l4); }
     SBX_HD uint16_t& h16(int off, uint32_t e) const { return *(uint16_t*)(W + off + 128u * e + l2); }
@@ -396,6 +399,9 @@ struct Lane {
         ent = io.ent;
         hi = lo = 0;
         n_lit = n_ent = lit_mark = opos = lit_flushed = ent_flushed = 0;
+#if !defined(__HIP_DEVICE_COMPILE__)
+        general_loops = 0;
+#endif
         init_input(io.in);
         const uint32_t lead_bits = bitpos;
         uint32_t* const lens32 = (uint32_t*)(io.scratch + kScratchLens);
@@ -475,8 +481,9 @@ struct Lane {
                         }
                 int32_t left = 1;
                 bool ok = true;
-                for (uint32_t l = 1; l <= 7; ++l) { left = (left << 1) - (int32_t)((ccnt >> (5u * l)) & 31u); if (left < 0) ok = false; }
-                if (!ok) { err = 1; active = false; dyn = false; }
+                for (uint32_t l = 1; l <= 7; ++l) { left = left * 2 - (int32_t)((ccnt >> (5u * l)) & 31u); if (left < 0) ok = false; }
+                // (zlib's inflate_table refuses an incomplete code-length code as it refuses an over-subscribed one)
+                if (!ok || left != 0) { err = 1; active = false; dyn = false; }
             }
             {
                 uint32_t i = 0, prev = 0, nib = 0;          // nib: the dword of eight lengths being filled
@@ -536,7 +543,7 @@ struct Lane {
             // ---- distance code: limits / deltas, insert positions, symbols in canonical order -------------------------------
             bool dist_in12 = true, dist_no12 = true, lit_in14 = true, lit_no12 = true;
             if (huff) {
-                uint32_t first = 0, offs = 0, lim_prev = 0, D_prev = 0, lim_a = 0, dd_a = 0;
+                uint32_t first = 0, offs = 0, lim_prev = 0, D_prev = 0, lim_a = 0, dd_a = 0, c1 = 0;
                 int32_t left = 1;
                 bool ok = true;
 #pragma unroll
@@ -544,7 +551,8 @@ struct Lane {
                     uint32_t lim, D;
                     if (l <= 15) {
                         const uint32_t c = b8(kOffLenSym, l);
-                        left = (left << 1) - (int32_t)c;
+                        if (l == 1) c1 = c;
+                        left = left * 2 - (int32_t)c;
                         if (left < 0) ok = false;
                         lim = (first + c) << (15u - l);
                         D = offs - first;
@@ -569,6 +577,10 @@ struct Lane {
                 CD.lim1[7] = lim_a | 32767u << 16;
                 CD.dd[7] = dd_a | 0x2000u << 16;
                 CD.d1_lo = CD.d1 + (CD.dd[0] & 0xFFFFu) + (CD.dd[0] >> 16);
+                // an incomplete distance code is valid in two forms only, as in zlib's inflate_table: no codes at all (a block of literals)
+                // and a single code of one bit (the fixed code's 30 distance codes of 5 bits are RFC 1951's own).  The symbol loop finds a
+                // code that has no symbol (dm1 == 15, didx beyond the list)
+                if (btype == 2u && left != 0 && offs != 0u && !(offs == 1u && c1 == 1u)) ok = false;
                 if (!ok) { err = 1; active = false; huff = false; }
             }
             if (huff) {
@@ -599,7 +611,7 @@ struct Lane {
                     if (l <= 15) {
                         const uint32_t cc = h16(kOffAux, l);
                         const uint32_t c_lit = cc & 0x1FFu, c_non = cc >> 9, c = c_lit + c_non;
-                        left = (left << 1) - (int32_t)c;
+                        left = left * 2 - (int32_t)c;
                         if (left < 0) ok = false;
                         lim = (first + c) << (15u - l);
                         D = offs - first;
@@ -662,6 +674,9 @@ struct Lane {
 #endif
             if (plain) symbol_loop<true>(CL, CD, io, huff, err, active);
             else symbol_loop<false>(CL, CD, io, huff, err, active);
+#if !defined(__HIP_DEVICE_COMPILE__)
+            general_loops += huff && !plain ? 1u : 0u;
+#endif
             if (active && bitpos - lead_bits > io.in_bits) { err = 1; active = false; }
             if (active && last) active = false;
         }

@@ -3,11 +3,16 @@
 // compares the result with zlib's inflate of the same block (the library the reference calls, block.d:158-185).
 // Test infrastructure (tests/test_inflate2_cpu.py), not part of the product.
 //   usage: inflate2_host FILE [lane]      exit 0 = every block identical;  prints "<blocks> <fast> <general> <bad>"
+//          inflate2_host --cases FILE [lane]      the case table of tests/k1_cases.py (its case_file): every case states whether the lane
+//                                                 decodes it, hands it over or -- an invalid stream -- must not accept it, and how many of
+//                                                 its deflate blocks take the general form of the symbol loop;
+//                                                 prints "<cases> <fast> <general> <rejected> <bad>", a line on stderr per failing case
 #include <zlib.h>
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../sambamba_amd/csrc/inflate2_core.hpp"
@@ -176,7 +181,133 @@ static bool resolve_exact(const uint32_t* ent, uint32_t n_ent, const uint8_t* li
     return opos == isize;
 }
 
+// One block through the lane program, the literal translation and a plain LZ77 resolve.
+struct LaneRun {
+    uint32_t status = 0, n_ent = 0, n_lit = 0, general_loops = 0;
+    bool consistent = false;            // status 0: the token streams resolve to exactly ISIZE bytes
+    std::vector<uint8_t> got;
+    // The token streams, 64-byte aligned and of exactly the capacity a block has on the device (inflate.hip: isize + 49 literal bytes,
+    // isize / 3 + isize / 255 + 11 entries): a sanitizer build of this program traps the first byte beyond either.
+    uint32_t* ent = nullptr;
+    uint8_t* lit_al = nullptr;          // translated literals
+    LaneRun() = default;
+    LaneRun(const LaneRun&) = delete;
+    LaneRun& operator=(const LaneRun&) = delete;
+    ~LaneRun() { free(ent); free(lit_al); }
+};
+
+static void* alloc64(size_t bytes, int fill) {
+    void* p = nullptr;
+    if (posix_memalign(&p, 64, bytes ? bytes : 1) != 0) { fprintf(stderr, "out of memory\n"); exit(2); }
+    memset(p, fill, bytes);
+    return p;
+}
+
+// `in` must be readable from the 4-byte aligned address below it to 128 KiB + 64 bytes beyond the payload (inflate2_core.hpp: service)
+static void run_lane(const uint8_t* in, uint32_t clen, uint32_t isize, uint32_t lane, uint8_t* lds, const uint16_t* len_tab,
+                     const uint32_t* dist_tab, LaneRun* r) {
+    free(r->ent); free(r->lit_al);
+    r->lit_al = (uint8_t*)alloc64((size_t)isize + 49, 0xEE);
+    r->ent = (uint32_t*)alloc64(4 * ((size_t)isize / 3 + isize / 255 + 11), 0xEE);
+    uint8_t* const lit_al = r->lit_al;
+    std::vector<uint8_t> scratch(kScratchBytes + 64, 0xCC);
+    uint8_t* scr_al = scratch.data() + ((16 - ((uintptr_t)scratch.data() & 15)) & 15);
+    LaneIo io;
+    io.in = in; io.in_bits = clen * 8u; io.osize = isize; io.lit = lit_al; io.ent = r->ent; io.scratch = scr_al; io.live = true;
+    Lane L;
+    const LaneResult R = L.run(io, lds, lane, len_tab, dist_tab);
+    r->status = R.status; r->n_ent = R.n_ent; r->n_lit = R.n_lit; r->general_loops = L.general_loops;
+    r->consistent = false;
+    r->got.clear();
+    if (R.status != 0) return;
+    const uint32_t* info = (const uint32_t*)(scr_al + kScratchInfo);
+    const uint32_t n_seg = info[0], n_lit = info[1];
+    bool ok = n_lit == R.n_lit;
+    // translation
+    for (uint32_t s = 0; s < n_seg && ok; ++s) {
+        const uint32_t a = info[2 + s], b = s + 1 < n_seg ? info[2 + s + 1] : n_lit;
+        const uint8_t* tab = scr_al + kScratchTabs + 256 * s;
+        for (uint32_t i = a; i < b; ++i) lit_al[i] = tab[lit_al[i]];
+    }
+    // resolve
+    std::vector<uint8_t>& got = r->got;
+    got.reserve(isize + 600);
+    uint32_t lp = 0;
+    for (uint32_t k = 0; k < R.n_ent && ok; ++k) {
+        const uint32_t e = r->ent[k], lr = e >> 24, len = e & 511u, dist = ((e >> 9) & 0x7FFFu) + 1u;
+        for (uint32_t i = 0; i < lr; ++i) got.push_back(lit_al[lp++]);
+        if (len) {
+            if (dist > got.size()) { ok = false; break; }
+            const size_t src = got.size() - dist;
+            for (uint32_t i = 0; i < len; ++i) got.push_back(got[src + i]);
+        }
+        if (got.size() > isize) ok = false;
+    }
+    r->consistent = ok && lp == n_lit && got.size() == isize;
+}
+
+static uint32_t rd32(const std::vector<uint8_t>& f, size_t* pos) {
+    if (*pos + 4 > f.size()) { fprintf(stderr, "case file cut short\n"); exit(2); }
+    uint32_t v;
+    memcpy(&v, f.data() + *pos, 4);
+    *pos += 4;
+    return v;
+}
+
+// The case table.  A stream is laid out at every address mod 16 in turn (a short one at all sixteen) with 128 KiB + 64 readable bytes
+// behind it -- the bound the lane program documents for its prefetch; a sanitizer build of this program holds it to that.
+static int run_cases(const char* path, uint32_t lane, uint8_t* lds, const uint16_t* len_tab, const uint32_t* dist_tab) {
+    const std::vector<uint8_t> f = read_file(path);
+    size_t pos = 0;
+    long n_cases = 0, n_fast = 0, n_general = 0, n_reject = 0, n_bad = 0;
+    constexpr size_t kReadable = 128 * 1024 + 64;
+    while (pos < f.size()) {
+        const uint32_t nl = rd32(f, &pos);
+        const std::string name((const char*)f.data() + pos, nl);
+        pos += nl;
+        const uint32_t expect = rd32(f, &pos), loops = rd32(f, &pos), isize = rd32(f, &pos), clen = rd32(f, &pos);
+        const uint8_t* stream = f.data() + pos;
+        pos += clen;
+        const uint8_t* want = f.data() + pos;
+        if (expect != 2u) pos += isize;
+        if (pos > f.size()) { fprintf(stderr, "case file cut short\n"); return 2; }
+        const uint32_t a0 = clen <= 256u ? 0u : (uint32_t)(n_cases & 15), a1 = clen <= 256u ? 16u : a0 + 1u;
+        const char* why = nullptr;
+        for (uint32_t al = a0; al < a1 && !why; ++al) {
+            // exactly the documented bound behind the payload and nothing more: a sanitizer build traps the first byte beyond it
+            std::vector<uint8_t> buf(al + clen + kReadable, 0x5A);
+            if ((uintptr_t)buf.data() & 15) { fprintf(stderr, "allocation not 16-byte aligned\n"); return 2; }
+            uint8_t* p = buf.data() + al;
+            memcpy(p, stream, clen);
+            LaneRun r;
+            run_lane(p, clen, isize, lane, lds, len_tab, dist_tab, &r);
+            if (expect == 0u) {
+                if (r.status != 0) why = "handed to the general kernel, expected fast";
+                else if (!r.consistent) why = "token streams do not resolve to ISIZE bytes";
+                else if (memcmp(r.got.data(), want, isize) != 0) why = "output differs from zlib's";
+                else if (r.general_loops != loops) why = "plain / general form of the symbol loop not as expected";
+            } else if (r.status != kNeedsGeneral) {
+                why = expect == 1u ? "expected to be handed to the general kernel" : "invalid stream accepted";
+            }
+        }
+        ++n_cases;
+        if (why) { ++n_bad; fprintf(stderr, "FAIL %s: %s\n", name.c_str(), why); }
+        else if (expect == 0u) ++n_fast;
+        else if (expect == 1u) ++n_general;
+        else ++n_reject;
+    }
+    printf("%ld %ld %ld %ld %ld\n", n_cases, n_fast, n_general, n_reject, n_bad);
+    return n_bad == 0 ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 3 && !strcmp(argv[1], "--cases")) {
+        std::vector<uint8_t> lds(kWaveLds + kLenTabBytes + kDistTabBytes, 0xA5);
+        uint16_t* len_tab = (uint16_t*)(lds.data() + kWaveLds);
+        uint32_t* dist_tab = (uint32_t*)(lds.data() + kWaveLds + kLenTabBytes);
+        for (uint32_t i = 0; i < 32; ++i) rfc_tables_entry(i, &len_tab[i], &dist_tab[i]);
+        return run_cases(argv[2], argc > 3 ? (uint32_t)atoi(argv[3]) : 0u, lds.data(), len_tab, dist_tab);
+    }
     if (argc < 2) { fprintf(stderr, "usage: %s FILE [lane] [--exact]\n", argv[0]); return 2; }
     const uint32_t lane = argc > 2 ? (uint32_t)atoi(argv[2]) : 0u;
     const bool exact = argc > 3 && !strcmp(argv[3], "--exact");
@@ -215,51 +346,21 @@ int main(int argc, char** argv) {
         std::vector<uint8_t> in(clen + 128 + 8, 0x5A);
         uint8_t* in_al = in.data() + ((8 - ((uintptr_t)in.data() & 7)) & 7) + lead;
         memcpy(in_al, h + hdr, clen);
-        std::vector<uint8_t> lit(isize + 128 + 64, 0xEE);
-        std::vector<uint32_t> ent(isize / 3 + isize / 255 + 64, 0xEEEEEEEEu);
-        std::vector<uint8_t> scratch(kScratchBytes + 64, 0xCC);
-        uint8_t* lit_al = lit.data() + ((64 - ((uintptr_t)lit.data() & 63)) & 63);
-        uint8_t* scr_al = scratch.data() + ((16 - ((uintptr_t)scratch.data() & 15)) & 15);
-        LaneIo io;
-        io.in = in_al; io.in_bits = clen * 8u; io.osize = isize; io.lit = lit_al; io.ent = ent.data(); io.scratch = scr_al; io.live = true;
-        Lane L;
-        const LaneResult R = L.run(io, lds.data(), lane, len_tab, dist_tab);
+        LaneRun r;
+        run_lane(in_al, clen, isize, lane, lds.data(), len_tab, dist_tab, &r);
         ++n_blocks;
-        if (R.status != 0) {
+        if (r.status != 0) {
             ++n_general;
         } else {
             ++n_fast;
-            const uint32_t* info = (const uint32_t*)(scr_al + kScratchInfo);
-            const uint32_t n_seg = info[0], n_lit = info[1];
-            bool ok = n_lit == R.n_lit;
-            // translation
-            for (uint32_t s = 0; s < n_seg && ok; ++s) {
-                const uint32_t a = info[2 + s], b = s + 1 < n_seg ? info[2 + s + 1] : n_lit;
-                const uint8_t* tab = scr_al + kScratchTabs + 256 * s;
-                for (uint32_t i = a; i < b; ++i) lit_al[i] = tab[lit_al[i]];
-            }
-            // resolve
-            std::vector<uint8_t> got;
-            got.reserve(isize + 600);
-            uint32_t lp = 0;
-            for (uint32_t k = 0; k < R.n_ent && ok; ++k) {
-                const uint32_t e = ent[k], lr = e >> 24, len = e & 511u, dist = ((e >> 9) & 0x7FFFu) + 1u;
-                for (uint32_t i = 0; i < lr; ++i) got.push_back(lit_al[lp++]);
-                if (len) {
-                    if (dist > got.size()) { ok = false; break; }
-                    const size_t src = got.size() - dist;
-                    for (uint32_t i = 0; i < len; ++i) got.push_back(got[src + i]);
-                }
-                if (got.size() > isize) ok = false;
-            }
-            ok = ok && lp == n_lit && got.size() == isize && memcmp(got.data(), want.data(), isize) == 0;
+            bool ok = r.consistent && memcmp(r.got.data(), want.data(), isize) == 0;
             if (ok && exact) {
                 std::vector<uint8_t> got2;
-                ok = resolve_exact(ent.data(), R.n_ent, lit_al, isize, got2, &n_batches, &n_rounds) && memcmp(got2.data(), want.data(), isize) == 0;
+                ok = resolve_exact(r.ent, r.n_ent, r.lit_al, isize, got2, &n_batches, &n_rounds) && memcmp(got2.data(), want.data(), isize) == 0;
             }
             if (!ok) {
                 ++n_bad;
-                if (n_bad < 5) fprintf(stderr, "MISMATCH block %ld at file offset %zu (isize %u, n_lit %u, n_ent %u, got %zu bytes)\n", n_blocks - 1, pos, isize, n_lit, R.n_ent, got.size());
+                if (n_bad < 5) fprintf(stderr, "MISMATCH block %ld at file offset %zu (isize %u, n_lit %u, n_ent %u, got %zu bytes)\n", n_blocks - 1, pos, isize, r.n_lit, r.n_ent, r.got.size());
             }
         }
         pos += bsize;
