@@ -1,7 +1,11 @@
 """`depth region` and `depth window` through the device path (K5 range_reduce / count_reads) and the
 sbx-depth CLI: byte-identical text against the CPU oracle (the literal restatement of
 sambamba/depth.d:609-1077).  The reference ships no golden for these modes without -m
-("parity unpinned by goldens"), so the oracle is the pin."""
+("parity unpinned by goldens"), so the oracle is the pin.
+
+The inputs here are the reference's fixtures and random reads.  The kernels' own limits -- the runs of add_runs, the second
+window and the long-read loop, range lengths on the lane stride, the tile and the chunk, inactive tiles, thresholds on a depth,
+the region search -- are in tests/test_gpu_k5_edges.py, on the hand-placed cases of tests/k5_cases.py."""
 import os
 
 import pytest
