@@ -209,6 +209,8 @@ extern (C) nothrow @nogc {
     // `sambamba view -S -f bam`: in_path "-" is stdin, out_path null or "-" stdout
     int sbx_import_sam(const(char)* in_path, const(char)* out_path, const(char)* pg_command_line, int level, int with_index, int device,
                        sbx_import_stats* stats, char* err, size_t errlen);
+    int sbx_import_sam_run(const(char)* in_path, const(char)* out_path, const(char)* pg_command_line, int level, int with_index, int device,
+                           sbx_import_stats* stats, sbx_stream_stats* stream_stats, char* err, size_t errlen);
     // `sambamba index [-c]`: check_bins == 0 is sbx_build_index
     int sbx_index_bam(const(char)* bam_path, const(char)* bai_path, int check_bins, int device, char* err, size_t errlen);
     struct sbx_fixbins_stats {

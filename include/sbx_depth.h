@@ -209,9 +209,9 @@ int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, si
  *             not the one its key was taken with -- the call fails with SBX_EIO ("the input changed while it was being sorted") and
  *             the output file is removed.  SBX_ENOMEM only when not even the keys, one minimal read batch and a window of one piece
  *             fit.
- * sbx_sort_bam_by_name, sbx_merge_bam, sbx_import_sam and view with two or more listed regions have
+ * sbx_sort_bam_by_name, sbx_merge_bam and view with two or more listed regions have
  * the resident path only and refuse what does not fit with SBX_ENOMEM (a name order needs the names next to the keys: not built);
- * sbx_fixbins and both sinks of view in file order stream such a file (sbx_stream_stats).
+ * sbx_fixbins, sbx_import_sam and both sinks of view in file order stream such a file (sbx_stream_stats).
  * Milliseconds are device time of the kernels (inflate = K1, index = K2, keys = K9a + the copy into the record store, sort = K9b,
  * gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index.
  * On the windowed path inflate and index are those of the key pass alone (SBX_TIMING=1 reports the replays in a `[sbx] sort-windows:`
@@ -562,8 +562,16 @@ int sbx_view_reference_info(sbx_ctx*, char* out, size_t cap, size_t* out_len);
  * reference name the header lacks, a '\r', an empty line included -- fails the call with SBX_EFORMAT, the message carrying the
  * number of such lines and the 1-based number of the first, and no output file is left.  Two texts sbx_view_sam writes and the
  * grammar lacks are read: "B:<type>," (an array without elements) and "-nan" (0xFFC00000).
- * The records are resident on the device as for sbx_sort_bam: SBX_ENOMEM, naming the bytes needed and the bytes free, when the store
- * cannot grow; more than 2^32 records are SBX_EUNSUPPORTED; an out_path that is the input is SBX_EINVAL.  The text is uploaded in
+ * The records stay resident on the device while they fit, in a store that grows chunk by chunk.  When it cannot grow -- the grown store
+ * does not fit next to the old one, or would leave no room for the streamed path -- the call switches: the header and the records kept
+ * so far go through one staging window of the output stream into the file, the store is freed, and from then on K15d writes every
+ * chunk's records into the window directly (sbx_stream_stats, sbx_import_sam_run below).  Nothing is written before the switch; the file
+ * is the resident path's byte for byte.  A bad line met behind the switch is the same SBX_EFORMAT with the same message; an output file
+ * is removed, an output on stdout has received bytes by then.  SBX_STREAM_WINDOW_BYTES takes the streamed path from the first chunk
+ * (as for view and fixbins), SBX_IMPORT_STORE_BYTES=<n> switches at the chunk whose records would bring the store past n bytes (both for
+ * tests; anything but a positive decimal counts as unset).  SBX_ENOMEM, naming the bytes needed part by part and the bytes free, only
+ * when not even a window of one piece, the encoder, two text chunks and the arrays of one chunk fit; more than 2^32 records are
+ * SBX_EUNSUPPORTED; an out_path that is the input is SBX_EINVAL.  The text is uploaded in
  * chunks cut at line ends (64 MiB, not tuned; SBX_IMPORT_CHUNK_BYTES overrides it for tests); the output does not depend on the size.
  * n_lines: lines behind the header; text_bytes: their bytes.  Milliseconds are device time (index = K15a, measure = K15b + scan,
  * emit = K15c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index. */
@@ -574,6 +582,11 @@ typedef struct {
 } sbx_import_stats;
 int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_command_line, int level, int with_index, int device,
                    sbx_import_stats* stats, char* err, size_t errlen);
+/* sbx_import_sam with the figures of the streamed path (sbx_stream_stats above; n_pack_launches counts the launches of K15d, ms_pack
+ * their time, which is ms_emit too): stream_stats may be NULL, and sbx_import_sam is this call with NULL.  All zero when the records
+ * stayed resident. */
+int sbx_import_sam_run(const char* in_path, const char* out_path, const char* pg_command_line, int level, int with_index, int device,
+                       sbx_import_stats* stats, sbx_stream_stats* stream_stats, char* err, size_t errlen);
 
 /* ---- index, fixbins (`sambamba index [-c] [-F]`, index.d; `sambamba fixbins`, fixbins.d) ----
  * sbx_index_bam with check_bins == 0 is sbx_build_index: the same file, the same errors.  With check_bins != 0 (`index -c`) the same

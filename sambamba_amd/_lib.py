@@ -200,7 +200,7 @@ EXPORTS = [
     "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_run", "sbx_view_run_indexed", "sbx_view_run_streamed", "sbx_view_num_filter", "sbx_view_reference_info",
     "sbx_validate_bam", "sbx_format_validate_report",
     "sbx_slice_bam",
-    "sbx_import_sam",
+    "sbx_import_sam", "sbx_import_sam_run",
     "sbx_index_bam", "sbx_fixbins", "sbx_fixbins_run", "sbx_index_fasta",
     "sbx_subsample",
 ]
@@ -357,6 +357,8 @@ def lib():
     L.sbx_slice_bam.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_int, C.POINTER(SliceStats), C.c_char_p,
                                 C.c_size_t]
     L.sbx_import_sam.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(ImportStats), C.c_char_p, C.c_size_t]
+    L.sbx_import_sam_run.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(ImportStats), C.POINTER(StreamStats),
+                                     C.c_char_p, C.c_size_t]
     L.sbx_index_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
     L.sbx_fixbins.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(FixbinsStats), C.c_char_p, C.c_size_t]
     L.sbx_fixbins_run.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(FixbinsStats), C.POINTER(StreamStats), C.c_char_p, C.c_size_t]
@@ -993,15 +995,20 @@ def import_sam(in_path, out_path, level=-1, index=False, command_line=None, devi
     """sbx_import_sam (`sambamba view -S -f bam`): the SAM text at in_path ("-": stdin) parsed on the device and written to out_path
     ("-": stdout) as a BAM -- index=True also writes out_path + ".bai", command_line is the CL field of the @PG line that is added
     (None: no @PG).  A line outside the grammar raises SbxError(-3) naming how many there are and the first.  Returns the fields
-    of sbx_import_stats as a dict."""
+    of sbx_import_stats as a dict, plus n_windows, window_bytes, n_pack_launches and ms_pack of sbx_stream_stats (sbx_import_sam_run):
+    zeros when the records stayed on the device, the figures of the streamed path when they did not fit (or SBX_STREAM_WINDOW_BYTES
+    or SBX_IMPORT_STORE_BYTES made it so)."""
     L = lib()
     st = ImportStats()
+    ss = StreamStats()
     err = C.create_string_buffer(512)
     cl = command_line.encode() if command_line is not None else None
-    rc = L.sbx_import_sam(in_path.encode(), out_path.encode(), cl, int(level), int(index), device, C.byref(st), err, 512)
+    rc = L.sbx_import_sam_run(in_path.encode(), out_path.encode(), cl, int(level), int(index), device, C.byref(st), C.byref(ss), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
-    return {k: getattr(st, k) for k, _ in ImportStats._fields_ if k != "reserved"}
+    out = {k: getattr(st, k) for k, _ in ImportStats._fields_ if k != "reserved"}
+    out.update({k: getattr(ss, k) for k in STREAM_KEYS})
+    return out
 
 
 def view_reference_info(path, device=-1):

@@ -7,8 +7,20 @@
 // scan, K15c (records into the resident store of engine_store.hpp, which grows with grow_keeping).  Every chunk is measured even after
 // a bad line was met, so that the refusal names how many there are; nothing is emitted from then on.  The output tail is the one of
 // the other resident-store commands: the identity permutation through write_store_output, then index_written_bam.
+//
+// Records that do not fit the device -- on a pipe nobody knows in advance -- leave as a stream (StreamedOutput, engine_streamout.hpp):
+// before the store grows, the grown store must fit next to the old one and must leave room for what the streamed path allocates
+// (stream_floor below).  If not, the writer is created, the header and the store's records go through its window, the store and
+// the per-file arrays are freed, and from this chunk on K15d writes every chunk's records straight into the window, one launch per
+// window the chunk touches; d_len and d_off then hold one chunk.  Nothing was written before the switch, so an input that fits
+// still fails on a bad line before a byte is out; behind the switch a bad line is met after windows were written: the remaining
+// chunks are measured as ever, the refusal is the same, an output file is removed and a pipe has received bytes.
+// SBX_STREAM_WINDOW_BYTES takes the streamed path from the first chunk, SBX_IMPORT_STORE_BYTES forces the switch (tests).
+#include <memory>
+
 #include "engine_chunks.hpp"
 #include "engine_store.hpp"
+#include "engine_streamout.hpp"
 #include "markdup_core.hpp"
 #include "samparse.hpp"
 
@@ -111,6 +123,31 @@ std::vector<RefSeq> header_references(const std::string& text) {
     return refs;
 }
 
+// SBX_IMPORT_STORE_BYTES (tests): the record store may hold no more than this many record bytes; the chunk whose records would
+// pass it starts the streamed path.  Anything that is not a positive decimal counts as unset (0: no limit but the device's).
+uint64_t import_store_limit() { return env_size("SBX_IMPORT_STORE_BYTES", 0); }
+
+// What the streamed path holds on the device, in bytes: a window of one piece, the encoder's buffers (as StreamBudget reserves
+// them), two text chunks, and the arrays of a chunk -- line start, length and offset, 20 bytes per line, and no line of the grammar
+// has fewer than 22 bytes.
+struct StreamFloor {
+    uint64_t piece_blocks, piece_bytes;
+    uint64_t window, encoder, text, arrays;
+    uint64_t total() const { return window + encoder + text + arrays; }
+    // ... of which text_held bytes of text buffers exist already
+    uint64_t to_allocate(uint64_t text_held) const { return total() - std::min(text, text_held); }
+};
+StreamFloor stream_floor(uint64_t chunk_bytes) {
+    StreamFloor f{};
+    f.piece_blocks = bgzf_piece_blocks();
+    f.piece_bytes = f.piece_blocks * (uint64_t)kBgzfPayload;
+    f.window = f.piece_bytes + 64;
+    f.encoder = f.piece_bytes * 3 + (8ull << 20);
+    f.text = 2 * (chunk_bytes + 64);
+    f.arrays = (chunk_bytes / 22 + 4096) * 20;
+    return f;
+}
+
 void print_timing(const sbx_import_stats& st, uint64_t chunk_bytes) {
     if (!getenv("SBX_TIMING")) return;
     fprintf(stderr, "[sbx] import: n_lines=%llu n_records=%llu text_bytes=%llu stream_bytes=%llu compressed_bytes=%llu n_chunks=%u chunk_bytes=%llu "
@@ -124,8 +161,8 @@ void print_timing(const sbx_import_stats& st, uint64_t chunk_bytes) {
 
 extern "C" {
 
-int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_command_line, int level, int with_index, int device,
-                   sbx_import_stats* stats, char* err, size_t errlen) {
+int sbx_import_sam_run(const char* in_path, const char* out_path, const char* pg_command_line, int level, int with_index, int device,
+                       sbx_import_stats* stats, sbx_stream_stats* stream_stats, char* err, size_t errlen) {
     const bool to_stdout = !out_path || !strcmp(out_path, "-");
     const char* const path = to_stdout ? "/dev/stdout" : out_path;
     const int rc = run_entry(err, errlen, [&] {
@@ -134,6 +171,7 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
         if (to_stdout && with_index) throw Error(SBX_EINVAL, "an output on stdout cannot be indexed");
         const bool from_stdin = !strcmp(in_path, "-");
         if (!to_stdout && !from_stdin) refuse_overwrite(in_path, path);
+        if (stream_stats) *stream_stats = sbx_stream_stats{};
         const double w0 = wall_now();
         require_device(device);
         int dev = 0;
@@ -172,13 +210,56 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
         }
 
         // ---- the chunks: the reader thread fills the slots, this thread parses them ----
-        const uint64_t budget = import_chunk_bytes();
+        const uint64_t budget = import_chunk_bytes(), window_hook = stream_window_hook(), store_limit = import_store_limit();
         sbx_import_stats st{};
         DevBuf<uint8_t> d_store(64), d_text[2];
         DevBuf<uint64_t> d_off(2), d_tile, d_line_start, d_group;
         DevBuf<uint32_t> d_len(2);
         uint64_t store_used = 0, n_rec = 0;
+        std::unique_ptr<StreamedOutput> out;            // the streamed path, from the chunk on that did not fit the store (or the first)
         unsigned long long acc[kImportAccWords] = {0, kImportNoBadLine, 0, 0};
+
+        // Room for `more` further record bytes in the store?  Grows it when it has to and may; false: the records go on as a stream.
+        auto store_takes = [&](uint64_t more) {
+            if (window_hook || (store_limit && store_used + more > store_limit)) return false;
+            const uint64_t need = store_used + more + 64;
+            if (need <= d_store.n) return true;
+            const uint64_t cap = need + need / 2 + 1024;            // (what grow_keeping allocates, next to the store as it is)
+            size_t free_b = 0, total_b = 0;
+            SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+            // behind the growth the switch must still be possible: what the streamed path allocates, next to the grown store
+            if (cap > free_b || free_b - cap + d_store.n < stream_floor(budget).to_allocate(d_text[0].n + d_text[1].n)) return false;
+            grow_keeping(d_store, (size_t)store_used, (size_t)need, s);
+            return true;
+        };
+        // The switch: the writer, the header, the store's records through the window; the store and the per-file arrays go.  Lines
+        // [0, n_lines) of the current chunk have their lengths at d_len[n_rec ...): they move to the front of arrays of their own.
+        auto start_stream = [&](uint64_t chunk_text_bytes, uint64_t n_lines) {
+            DevBuf<uint32_t> len_now((size_t)n_lines + 2);
+            SBX_HIP(hipMemcpyAsync(len_now.p, d_len.p + n_rec, (size_t)n_lines * 4, hipMemcpyDeviceToDevice, s));
+            SBX_HIP(hipStreamSynchronize(s));
+            d_len = std::move(len_now);
+            d_off.alloc((size_t)n_lines + 2);
+            const StreamFloor f = stream_floor(std::max<uint64_t>(budget, chunk_text_bytes));
+            const uint64_t to_allocate = f.to_allocate(d_text[0].n + d_text[1].n);
+            size_t free_b = 0, total_b = 0;
+            SBX_HIP(hipMemGetInfo(&free_b, &total_b));
+            if (to_allocate > free_b)
+                throw Error(SBX_ENOMEM, "the records do not fit the device: importing them in a stream needs " + std::to_string(f.total()) +
+                                            " bytes of device memory (a window of one piece " + std::to_string(f.window) + ", the encoder " +
+                                            std::to_string(f.encoder) + ", two text chunks " + std::to_string(f.text) + ", the arrays of a chunk " +
+                                            std::to_string(f.arrays) + "), " + std::to_string(to_allocate) + " of them are not allocated yet and " +
+                                            std::to_string(free_b) + " are free next to a record store of " + std::to_string(d_store.n) + " bytes");
+            // The window: the hook's; else the whole pieces that hold four chunks of text, at most half of what is left and at least
+            // the one piece of the floor.  A pipe's stream has no bound to cut the window to, and a chunk's records are fewer bytes
+            // than its text: a wider window would save no launch of K15d worth its memory.
+            const uint64_t spare_pieces = (free_b - to_allocate) / 2 / f.piece_bytes;
+            const uint64_t window = window_hook ? sortc::window_span(f.piece_bytes, window_hook)
+                                                : std::min(sortc::window_span(f.piece_bytes, 4 * budget), (1 + spare_pieces) * f.piece_bytes);
+            out.reset(new StreamedOutput(out_file, header, window, (uint32_t)f.piece_blocks, level, s));
+            out->take_device(d_store.p, store_used);
+            d_store.release();
+        };
         {
             ChunkReader reader(dev, "reading the SAM text failed", [&](PinnedBuf<uint8_t>& text) {
                 size_t bytes = 0;
@@ -203,14 +284,19 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
                 const uint64_t n_newlines = index_lines(t, d_tile, d_line_start, t_index, s, [&] { reader.release(c); });
                 const uint64_t n_lines = n_newlines + (open_end ? 1u : 0u);
                 if (n_rec + n_lines > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-                // K15b and the offsets
-                grow_keeping(d_len, (size_t)n_rec, (size_t)(n_rec + n_lines) + 2, s);
-                grow_keeping(d_off, (size_t)n_rec, (size_t)(n_rec + n_lines) + 2, s);
+                // K15b and the offsets; the arrays are the file's while the store is kept and the chunk's on the streamed path
+                if (out) {
+                    d_len.ensure((size_t)n_lines + 2);
+                    d_off.ensure((size_t)n_lines + 2);
+                } else {
+                    grow_keeping(d_len, (size_t)n_rec, (size_t)(n_rec + n_lines) + 2, s);
+                    grow_keeping(d_off, (size_t)n_rec, (size_t)(n_rec + n_lines) + 2, s);
+                }
                 const uint32_t groups = group_count(n_lines);
                 d_group.ensure(groups + 2);
                 const ImportLines lines{t, d_line_start.p, n_newlines, n_lines, n_header_lines + st.n_lines + 1, table};
                 t_measure.start(s);
-                launch_import_measure(lines, d_len.p + n_rec, d_group.p, d_acc.p, s);
+                launch_import_measure(lines, d_len.p + (out ? 0 : n_rec), d_group.p, d_acc.p, s);
                 launch_scan64(d_group.p, groups, 0, s);
                 t_measure.stop(s);
                 uint64_t chunk_record_bytes = 0;
@@ -223,26 +309,27 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
                 st.text_bytes += size;
                 ++st.n_chunks;
                 if (acc[kImportAccBad]) continue;               // (the remaining chunks are still measured, for the count)
-                // K15c into the store
-                const uint64_t need = store_used + chunk_record_bytes + 64;
-                if (need > d_store.n) {
-                    const uint64_t cap = need + need / 2 + 1024;        // (what grow_keeping allocates, next to the store as it is)
-                    size_t free_b = 0, total_b = 0;
-                    SBX_HIP(hipMemGetInfo(&free_b, &total_b));
-                    if (cap > free_b)
-                        throw Error(SBX_ENOMEM, "the records do not fit the device: growing the record store needs " + std::to_string(cap) +
-                                                    " bytes of device memory, " + std::to_string(free_b) + " are free");
-                    grow_keeping(d_store, (size_t)store_used, (size_t)need, s);
+                if (!out && !store_takes(chunk_record_bytes)) start_stream(size, n_lines);
+                if (out) {
+                    // K15d: the chunk's records are the next bytes of the stream, one launch per window they touch
+                    launch_group_offsets(d_len.p, d_group.p, n_lines, out->stream_bytes(), d_off.p, s);
+                    const double ms_before = out->stats().ms_pack;
+                    out->take(chunk_record_bytes, [&](uint8_t* window, uint64_t w_from, uint64_t w_to, unsigned long long* counter) {
+                        launch_import_emit_window(lines, d_len.p, d_off.p, window, w_from, w_to, d_acc.p, counter, s);
+                    });
+                    st.ms_emit += out->stats().ms_pack - ms_before;
+                } else {
+                    // K15c into the store
+                    t_emit.start(s);
+                    launch_group_offsets(d_len.p + n_rec, d_group.p, n_lines, store_used, d_off.p + n_rec, s);
+                    launch_import_emit(lines, d_len.p + n_rec, d_off.p + n_rec, d_store.p, d_acc.p, s);
+                    t_emit.stop(s);
                 }
-                t_emit.start(s);
-                launch_group_offsets(d_len.p + n_rec, d_group.p, n_lines, store_used, d_off.p + n_rec, s);
-                launch_import_emit(lines, d_len.p + n_rec, d_off.p + n_rec, d_store.p, d_acc.p, s);
-                t_emit.stop(s);
                 SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
                 SBX_HIP(hipStreamSynchronize(s));
-                st.ms_emit += t_emit.ms();
+                if (!out) st.ms_emit += t_emit.ms();
                 if (acc[kImportAccOverrun]) throw Error(SBX_EFORMAT, "internal error: a record did not have the length it was measured with");
-                store_used += chunk_record_bytes;
+                if (!out) store_used += chunk_record_bytes;
                 n_rec += n_lines;
             }
         }
@@ -253,25 +340,39 @@ int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_com
         d_text[0].release(); d_text[1].release();
         d_tile.release(); d_line_start.release(); d_group.release();
 
-        // ---- the output: the records of the store in their order ----
         const uint64_t n = n_rec;
-        DevBuf<uint32_t> d_perm((size_t)n + 2);
-        launch_iota(d_perm.p, n, s);
-        DevBuf<uint64_t> d_out_off((size_t)n + 2);
-        double ms_gather = 0;
-        const unsigned long long record_bytes = store_used;
-        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, d_perm.p, n, d_out_off.p, level, &record_bytes,
-                                                "imported records", s, &ms_gather);
-        out_file.disarm();
         st.n_records = n;
-        st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
-        st.ms_deflate = w.ms_deflate;
+        if (out) {
+            // ---- the streamed path: the last window, short ----
+            out->finish();
+            out_file.disarm();
+            st.stream_bytes = out->stream_bytes(); st.compressed_bytes = out->compressed_bytes();
+            st.ms_deflate = out->ms_deflate();
+            if (stream_stats) *stream_stats = out->stats();
+        } else {
+            // ---- the output: the records of the store in their order ----
+            DevBuf<uint32_t> d_perm((size_t)n + 2);
+            launch_iota(d_perm.p, n, s);
+            DevBuf<uint64_t> d_out_off((size_t)n + 2);
+            double ms_gather = 0;
+            const unsigned long long record_bytes = store_used;
+            const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, d_perm.p, n, d_out_off.p, level, &record_bytes,
+                                                    "imported records", s, &ms_gather);
+            out_file.disarm();
+            st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
+            st.ms_deflate = w.ms_deflate;
+        }
         st.ms_total_wall = (wall_now() - w0) * 1e3;
         print_timing(st, budget);
         if (stats) *stats = st;
     });
     // (the index is a pass of its own and not part of the figures)
     return rc != SBX_OK ? rc : index_written_bam(path, with_index, device, err, errlen);
+}
+
+int sbx_import_sam(const char* in_path, const char* out_path, const char* pg_command_line, int level, int with_index, int device,
+                   sbx_import_stats* stats, char* err, size_t errlen) {
+    return sbx_import_sam_run(in_path, out_path, pg_command_line, level, with_index, device, stats, nullptr, err, errlen);
 }
 
 }  // extern "C"

@@ -18,8 +18,8 @@
 // into the window, which goes through the same encoder to the file.  No temporary file and no merge; the file is the resident
 // path's byte for byte.  The budget of device memory, the spans, the choice of the window and the loop over windows and batches are
 // engine_windows.hpp, shared with sbx_markdup (whose output is in input order); what is here is the key pass, the order and the
-// callback that launches K9d-3.  The name orders, sbx_merge_bam and sbx_import_sam stay resident and refuse with
-// SBX_ENOMEM what does not fit; sbx_fixbins and view in file order, BAM and SAM sink, stream it (engine_streamout.hpp).
+// callback that launches K9d-3.  The name orders and sbx_merge_bam stay resident and refuse with
+// SBX_ENOMEM what does not fit; sbx_fixbins, sbx_import_sam and view in file order, BAM and SAM sink, stream it (engine_streamout.hpp).
 //
 // sbx_sort_bam_by_name (`sambamba sort -n / -N`, with or without -M) is the same call with another order: next to K9a, K14a
 // (namesort.hip) builds the key of every kept record's name in a key store of 64-bit words, and the order is an LSD sort over those

@@ -4,7 +4,9 @@
 // a full window goes through the encoder of engine_stream.hpp into the file, the window moves on and K21 runs again on the same
 // batch until the batch is consumed.  The window is a whole number of compression pieces and BGZF blocks are cut every kBgzfPayload
 // bytes of the stream, so the file is the resident path's byte for byte.  The encoder runs between two launches of K21; overlapping
-// them through a second window is a follow-up.  sbx_import_sam would use the same writer with another filler.
+// them through a second window is a follow-up.  sbx_import_sam (engine_import.cpp) uses the same writer with
+// fillers of its own and no known bound of the stream: take() with K15d (samparse.hip) for the records of a text chunk, take_device()
+// for the records it had kept in a store before it found that they do not fit.
 // The SAM sink of view streams too, but needs none of this: its text goes piece by piece through the buffers of the resident sink
 // (engine_view.cpp, view_sam_streamed); of this file it uses StreamBudget's second form and the hook.
 #pragma once
@@ -118,10 +120,13 @@ class StreamedOutput {
 public:
     // `out` is armed as soon as the file exists and stays armed; the header is the first part of the stream.  stream_max: as for the budget.
     StreamedOutput(OutputGuard& out, const std::vector<uint8_t>& header, uint64_t stream_max, const StreamBudget& b, int level, hipStream_t s)
-        : s_(s), hlen_(header.size()), span_(std::min<uint64_t>(b.window_bytes, sortc::window_span(b.piece_bytes, stream_max))),
-          d_win_((size_t)span_ + 64), d_wacc_(1),       // (a window is never larger than the stream in whole pieces)
-          comp_((uint32_t)std::min<uint64_t>(b.piece_blocks, std::max<uint64_t>(1, (stream_max + kBgzfPayload - 1) / kBgzfPayload)), level, true),
-          f_(out) {
+        // (a window is never larger than the stream in whole pieces)
+        : StreamedOutput(out, header, std::min<uint64_t>(b.window_bytes, sortc::window_span(b.piece_bytes, stream_max)),
+                         (uint32_t)std::min<uint64_t>(b.piece_blocks, std::max<uint64_t>(1, (stream_max + kBgzfPayload - 1) / kBgzfPayload)), level, s) {}
+    // The same for a stream without a known bound (a pipe): a window of window_bytes (whole pieces, the caller's budget or the hook)
+    // and an encoder for whole pieces of piece_blocks payloads.
+    StreamedOutput(OutputGuard& out, const std::vector<uint8_t>& header, uint64_t window_bytes, uint32_t piece_blocks, int level, hipStream_t s)
+        : s_(s), hlen_(header.size()), span_(window_bytes), d_win_((size_t)span_ + 64), d_wacc_(1), comp_(piece_blocks, level, true), f_(out) {
         st_.window_bytes = span_;
         SBX_HIP(hipMemsetAsync(d_wacc_.p, 0, sizeof(unsigned long long), s_));
         advance(hlen_, [&](uint64_t w0, uint64_t w1) {
@@ -154,6 +159,36 @@ public:
         });
         SBX_HIP(hipStreamSynchronize(s_));
         st_.ms_pack += ms;
+    }
+    // nb more bytes of the stream from a filler of the caller's: fill(window, w0, w1, counter) is called once for every window
+    // [w0, w1) they touch, puts those of them that lie inside at window + (place - w0), in order on the stream, and adds their number
+    // to *counter (device memory) -- the check of flush() holds for them as for K21's.  Returns when the last call of fill has.
+    template <class Fill>
+    void take(uint64_t nb, Fill&& fill) {
+        double ms = 0;
+        advance(nb, [&](uint64_t w0, uint64_t w1) {
+            t_pack_.start(s_);
+            fill(d_win_.p, w0, w1, d_wacc_.p);
+            t_pack_.stop(s_);
+            ms += t_pack_.ms();
+            ++st_.n_pack_launches;
+        });
+        st_.ms_pack += ms;
+    }
+    // nb more bytes of the stream that lie in device memory at d_src: copies clipped to each window, counted like record bytes
+    void take_device(const uint8_t* d_src, uint64_t nb) {
+        const uint64_t from = at_;
+        advance(nb, [&](uint64_t w0, uint64_t w1) {
+            sortc::PieceClip c;
+            if (!sortc::clip_to_piece(from, from + nb, w0, w1, &c)) return;
+            unsigned long long count = 0;
+            SBX_HIP(hipMemcpyAsync(d_win_.p + c.dst, d_src + c.src, c.len, hipMemcpyDeviceToDevice, s_));
+            SBX_HIP(hipMemcpyAsync(&count, d_wacc_.p, sizeof count, hipMemcpyDeviceToHost, s_));
+            SBX_HIP(hipStreamSynchronize(s_));
+            count += c.len;
+            SBX_HIP(hipMemcpyAsync(d_wacc_.p, &count, sizeof count, hipMemcpyHostToDevice, s_));
+            SBX_HIP(hipStreamSynchronize(s_));
+        });
     }
     // the last window, short; the EOF block
     void finish() {

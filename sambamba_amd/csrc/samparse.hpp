@@ -26,5 +26,10 @@ void launch_import_measure(const ImportLines& l, uint32_t* d_rec_len, uint64_t* 
 // counts in acc[kImportAccOverrun] (and writes nothing outside its own bytes).
 void launch_import_emit(const ImportLines& l, const uint32_t* d_rec_len, const uint64_t* d_rec_off, uint8_t* d_store, unsigned long long* d_acc,
                         hipStream_t stream);
+// K15d: rec_off[i] is the place of record i in the output stream; the bytes of the records that lie in [w0, w1) of the stream are
+// written at d_window + (place - w0) and nothing else is (d_window holds w1 - w0 bytes).  *d_wrote grows by the number of bytes
+// written; a record whose emission disagrees with its measured length counts in acc[kImportAccOverrun].
+void launch_import_emit_window(const ImportLines& l, const uint32_t* d_rec_len, const uint64_t* d_rec_off, uint8_t* d_window, uint64_t w0, uint64_t w1,
+                               unsigned long long* d_acc, unsigned long long* d_wrote, hipStream_t stream);
 
 }  // namespace sbx

@@ -2,15 +2,17 @@
 // opposite direction of sam_core.hpp and `__host__ __device__` like it: the statements of K15 (samparse.hip) run on the CPU too
 // (tests/native/samin_host.cpp: records against tests/samin_ref.py, floats against glibc's strtof).
 //
-// ONE walker, walk_line, goes through the fields of a line and hands every piece of the record to a sink.  Two sinks exist:
-// MeasureSink adds the bytes up (sam_record_length, K15b) and RecordSink writes them (sam_record_emit, K15c), so the length and the
-// bytes come from the same field sequence.
+// ONE walker, walk_line, goes through the fields of a line and hands every piece of the record to a sink.  Three sinks exist:
+// MeasureSink adds the bytes up (sam_record_length, K15b), RecordSink writes them (sam_record_emit, K15c) and WindowSink writes those
+// of them that lie inside one window of the output stream (sam_record_emit_window, K15d), so the length and the bytes come from the
+// same field sequence.
 //   * reads: the walker never reads a byte at or behind line + n.  The eleven mandatory fields are located first (ten tabs), every
 //     field is checked against its rule of the grammar before a byte of it is used, and a line outside the grammar is kParseBad:
 //     nothing of the reference's silent recovery (skip to the next tab, drop the tag, fill the qualities) is reproduced.
 //   * writes: RecordSink is a fmt::RowSink (format_core.hpp: eight bytes per store, every store holds only bytes of its own record)
 //     behind a count -- a put that would pass the length the record was measured with is dropped, with everything after it, and
-//     the record is kParseOverrun.  So no byte outside [out, out + length) is written whatever the line holds.
+//     the record is kParseOverrun.  So no byte outside [out, out + length) is written whatever the line holds.  WindowSink keeps the
+//     same count and stores single bytes, each only after its place in the stream was found inside the window and the record.
 //   * what the record needs before its variable part -- block_size, bin, n_cigar_op, l_seq -- is known before the first byte is
 //     put: block_size is the measured length, the CIGAR is walked once for its count and its reference span and once more for
 //     its words, l_seq is the width of the SEQ field.
@@ -263,7 +265,7 @@ SBX_FMT_HD uint32_t base_code(uint32_t c) {
     return (uint32_t)((k < 14u ? lo >> (4u * k) : hi >> (4u * (k - 14u))) & 15ull);
 }
 
-// ---- the two sinks -------------------------------------------------------------------------------------------------------------------
+// ---- the three sinks -----------------------------------------------------------------------------------------------------------------
 // bytes(x, k): the low k bytes of x (1 <= k <= 8, the bytes above them zero); raw: bytes of the line as they are; seq: l bases packed two
 // per byte; qual: l bytes minus 33; fill: the same byte l times.
 struct MeasureSink {
@@ -335,6 +337,67 @@ struct RecordSink {
         uint64_t i = 0;
         for (; i + 8u <= l; i += 8u) row.put(x, 8u);
         if (i < l) row.put(x >> (8u * (8u - (uint32_t)(l - i))), (uint32_t)(l - i));
+    }
+};
+
+// The record at [off, off + length) of the output stream, of which only the bytes inside the window [w0, w1) are written: stream
+// byte p goes to win[p - w0].  A put is clipped to the window before a byte of it is produced, so a long SEQ or QUAL costs what lies
+// inside; the stores are single bytes (at most two records of a launch take this path, K15d).  `over` as in RecordSink: a put past
+// the measured length is dropped with everything after it.  wrote: the bytes stored.
+struct WindowSink {
+    uint8_t* win;
+    uint64_t off, w0;
+    uint64_t lo, hi;            // bytes [lo, hi) of the record lie inside the window (lo >= hi: none)
+    uint64_t cap, used, wrote;
+    uint32_t over;
+    SBX_FMT_HD void init(uint8_t* window, uint64_t window_from, uint64_t window_to, uint64_t at, uint64_t length) {
+        win = window; off = at; w0 = window_from; cap = length; used = 0; wrote = 0; over = 0;
+        const uint64_t a = at > window_from ? at : window_from, b = at + length < window_to ? at + length : window_to;
+        lo = a < b ? a - at : 0;
+        hi = a < b ? b - at : 0;
+    }
+    // A put of k bytes: its bytes [*a, *b) lie inside, byte *a goes to *dst.  false: none does, or the put did not fit.
+    SBX_FMT_HD bool clip(uint64_t k, uint64_t* a, uint64_t* b, uint8_t** dst) {
+        if (over || k > cap - used) { over = 1; return false; }
+        const uint64_t at = used;
+        used += k;
+        const uint64_t s = at > lo ? at : lo, e = at + k < hi ? at + k : hi;
+        if (s >= e) return false;
+        *a = s - at;
+        *b = e - at;
+        *dst = win + (off + s - w0);                            // (s >= lo: off + s >= w0)
+        wrote += e - s;
+        return true;
+    }
+    SBX_FMT_HD void bytes(uint64_t x, uint32_t k) {
+        uint64_t a, b;
+        uint8_t* d;
+        if (clip(k, &a, &b, &d)) for (uint64_t j = a; j < b; ++j) d[j - a] = (uint8_t)(x >> (8u * j));
+    }
+    SBX_FMT_HD void raw(const uint8_t* s, uint64_t len) {
+        uint64_t a, b;
+        uint8_t* d;
+        if (clip(len, &a, &b, &d)) for (uint64_t j = a; j < b; ++j) d[j - a] = s[j];
+    }
+    SBX_FMT_HD void seq(const uint8_t* s, uint64_t l) {
+        uint64_t a, b;
+        uint8_t* d;
+        if (clip((l + 1u) / 2u, &a, &b, &d))
+            for (uint64_t j = a; j < b; ++j) {
+                uint32_t v = base_code(s[2u * j]) << 4;
+                if (2u * j + 1u < l) v |= base_code(s[2u * j + 1u]);
+                d[j - a] = (uint8_t)v;
+            }
+    }
+    SBX_FMT_HD void qual(const uint8_t* s, uint64_t l) {
+        uint64_t a, b;
+        uint8_t* d;
+        if (clip(l, &a, &b, &d)) for (uint64_t j = a; j < b; ++j) d[j - a] = (uint8_t)(s[j] - 33u);
+    }
+    SBX_FMT_HD void fill(uint32_t v, uint64_t l) {
+        uint64_t a, b;
+        uint8_t* d;
+        if (clip(l, &a, &b, &d)) for (uint64_t j = a; j < b; ++j) d[j - a] = (uint8_t)v;
     }
 };
 
@@ -592,6 +655,19 @@ SBX_FMT_HD uint32_t sam_record_emit(const uint8_t* line, uint64_t n, const RefTa
     s.init(out, length);
     const uint32_t st = walk_line(line, n, refs, (uint32_t)(length - 4u), s);
     s.row.finish();
+    if (st != kParseOk) return st;
+    return s.over || s.used != length ? kParseOverrun : kParseOk;
+}
+
+// The same record as a part of the output stream: it lies at [off, off + length) there and only its bytes inside [w0, w1) are
+// written, stream byte p to window[p - w0]; *wrote receives their number ((min(off + length, w1) - max(off, w0)) for a record
+// that is as long as it was measured).  The status is sam_record_emit's, whatever the window.
+SBX_FMT_HD uint32_t sam_record_emit_window(const uint8_t* line, uint64_t n, const RefTable& refs, uint64_t off, uint64_t length, uint8_t* window,
+                                           uint64_t w0, uint64_t w1, uint64_t* wrote) {
+    WindowSink s;
+    s.init(window, w0, w1, off, length);
+    const uint32_t st = walk_line(line, n, refs, (uint32_t)(length - 4u), s);
+    *wrote = s.wrote;
     if (st != kParseOk) return st;
     return s.over || s.used != length ? kParseOverrun : kParseOk;
 }
