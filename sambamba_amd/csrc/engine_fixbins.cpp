@@ -1,13 +1,13 @@
 // engine_fixbins.cpp -- sbx_fixbins: `sambamba fixbins` (sambamba/fixbins.d) on the device.
 //
-// The shape is sbx_markdup's: the read pass of engine_store.hpp copies every batch of records into the resident record store; per
-// batch K16b (bins.hip) notes offset and length of every record and stores reg2bin(pos, pos + basesCovered()) into the bin field of
-// those that carry another value; the file is written in input order by the writer sort uses.  The header -- text and reference list
-// -- is written as it was read: the reference adds no @PG line here.
+// The shape is sbx_markdup's.  BinPass::step is the one batch step around K16b (bins.hip), called by both paths.  Resident: the batch
+// is copied into the record store of engine_store.hpp, K16b notes offset and length of every record and stores
+// reg2bin(pos, pos + basesCovered()) into the bin field of those that carry another value; the file is written in input order by the
+// writer sort uses.  The header -- text and reference list -- is written as it was read: the reference adds no @PG line here.
 //
-// A file whose records do not fit the store (or SBX_STREAM_WINDOW_BYTES) takes the streamed path (fixbins_streamed): no store; per
-// batch K16b computes the bins from the records in U and K21 (stream.hip) writes them while it copies the records into the staging
-// window of engine_streamout.hpp.  The file is the same byte for byte.
+// A file whose records do not fit the store (try_plan_record_store says so; or SBX_STREAM_WINDOW_BYTES) takes the streamed path
+// (fixbins_streamed): no store; the same step computes the bins from the records in U and K21 (stream.hip) writes them while it
+// copies the records into the staging window of engine_streamout.hpp.  The file is the same byte for byte.
 #include "bins.hpp"
 #include "engine_streamout.hpp"
 
@@ -23,6 +23,61 @@ void print_timing(const sbx_fixbins_stats& st, const char* tail) {
             st.ms_bins, st.ms_gather, st.ms_deflate, st.ms_total_wall, tail);
 }
 
+// The read pass of both paths: the one batch step around K16b and what it keeps.
+struct BinPass {
+    sbx_ctx* c;
+    hipStream_t s;
+    PassBooks<kBinFixWords> books;
+    DevBuf<uint64_t> d_off;         // resident: offset and length of every record in the store
+    DevBuf<uint32_t> d_len, d_bin;  // streamed: the bins of one batch
+    EventTimer t_k;
+    double ms_bins = 0;
+    uint64_t cur;                   // inflated offset of the file behind the batches so far
+
+    BinPass(sbx_ctx* c_, uint64_t u_first, hipStream_t s_) : c(c_), s(s_), cur(u_first) { books.init(s); }
+    // K16b over a batch of for_each_record_batch.  d_store: the resident record store -- the batch's bytes are copied behind those of
+    // the batches before, inside the timed interval, the bins are stored there and off[] / len[] written -- or null: the bins go
+    // to d_bin and nothing is stored into U (the streamed path).
+    void step(uint64_t nrec, uint64_t base, uint64_t next, uint8_t* d_store, uint64_t u_first) {
+        if (d_store) {
+            const size_t want = (size_t)(books.n + nrec + 2);
+            grow_keeping(d_off, (size_t)books.n, want, s);
+            grow_keeping(d_len, (size_t)books.n, want, s);
+        } else {
+            d_bin.ensure((size_t)nrec + 2);
+        }
+        BinFixArgs a{};
+        a.desc = c->d_desc.p; a.n = nrec; a.acc = books.d_acc.p;
+        if (d_store) {
+            a.store = d_store;
+            a.store_delta = (int64_t)base - (int64_t)u_first;
+            a.store_end = next - u_first;
+            a.out_base = books.n;
+            a.off = d_off.p; a.len = d_len.p;
+        } else {
+            a.store = const_cast<uint8_t*>(c->U());     // (with bin_out nothing is stored into it)
+            a.store_end = next - base;
+            a.bin_out = d_bin.p;
+        }
+        t_k.start(s);
+        if (d_store) copy_batch_to_store(c, d_store, u_first, cur, base, next, s);
+        launch_fix_bins(a, s);
+        t_k.stop(s);
+        // (the next batch's K1 / K2 overwrite U and the descriptors: K16b and the copy end first)
+        books.read_back(c, nrec, s);
+        ms_bins += t_k.ms();
+        cur = next;
+    }
+    bool bad() const { return books.acc[kBinFixBad] != 0; }
+    // after the pass: the refusals, then what the pass gives the stats
+    void finish(const char* in_path, sbx_fixbins_stats* st) const {
+        books.refuse_too_many();
+        if (bad()) throw Error(SBX_EFORMAT, malformed_records_message(books.acc[kBinFixBad], in_path));
+        st->n_records = books.n; st->n_bins_changed = books.acc[kBinFixChanged];
+        st->ms_inflate = books.ms_inflate; st->ms_index = books.ms_index; st->ms_bins = ms_bins;
+    }
+};
+
 void fixbins_streamed(Standalone& c, OutputGuard& out_file, const char* in_path, const std::vector<uint8_t>& header, uint64_t hook, int level,
                       double w0, sbx_fixbins_stats* stats, sbx_stream_stats* stream_stats) {
     const uint64_t u_total = c->blocks.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
@@ -30,46 +85,25 @@ void fixbins_streamed(Standalone& c, OutputGuard& out_file, const char* in_path,
     const StreamBudget budget(stream_max, hook, 20, "fixing the bins of", "20 bytes per record of it", "");
     hipStream_t s = c->stream.get();
     StreamedOutput out(out_file, header, stream_max, budget, level, s);
-    DevBuf<uint32_t> d_bin;
-    DevBuf<unsigned long long> d_acc(kBinFixWords);
-    SBX_HIP(hipMemsetAsync(d_acc.p, 0, kBinFixWords * sizeof(unsigned long long), s));
-    SBX_HIP(hipStreamSynchronize(s));
+    BinPass bins(c.get(), u_first, s);
+    const unsigned long long* acc = bins.books.acc;
     sbx_fixbins_stats st{};
-    EventTimer t_k;
-    uint64_t n = 0;
     uint32_t n_batches = 0;
-    bool too_many = false;
-    unsigned long long acc[kBinFixWords] = {0};
     for_each_record_batch(c.get(), budget.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-        if (n + nrec > 0xFFFFFFF0ull) { too_many = true; return false; }
-        d_bin.ensure((size_t)nrec + 2);
+        if (!bins.books.admit(nrec)) return false;
         const unsigned long long bytes_before = acc[kBinFixBytes];
-        t_k.start(s);
-        BinFixArgs a{};
-        a.store = const_cast<uint8_t*>(c->U()); a.desc = c->d_desc.p; a.n = nrec;      // (with bin_out nothing is stored into it)
-        a.store_delta = 0;
-        a.store_end = next - base;
-        a.acc = d_acc.p;
-        a.bin_out = d_bin.p;
-        launch_fix_bins(a, s);
-        t_k.stop(s);
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_bins += t_k.ms();
-        n += nrec;
-        if (acc[kBinFixBad]) return false;
+        bins.step(nrec, base, next, nullptr, 0);
+        if (bins.bad()) return false;
         PackArgs p{};
         p.U = c->U(); p.desc = c->d_desc.p; p.n = nrec; p.u_end = next - base;
-        p.bin = d_bin.p;
+        p.bin = bins.d_bin.p;
         // (the next batch's K1 / K2 overwrite U and the descriptors: add_batch returns when K21 has read them)
         out.add_batch(p, acc[kBinFixBytes] - bytes_before);
         return true;
     });
-    if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-    if (acc[kBinFixBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kBinFixBad], in_path));
+    bins.finish(in_path, &st);
     out.finish();
     out_file.disarm();
-    st.n_records = n; st.n_bins_changed = acc[kBinFixChanged];
     st.inflated_bytes = u_total; st.stream_bytes = out.stream_bytes(); st.compressed_bytes = out.compressed_bytes();
     st.n_batches = n_batches;
     st.ms_deflate = out.ms_deflate();
@@ -96,55 +130,25 @@ int sbx_fixbins_run(const char* in_path, const char* out_path, int level, int de
         const std::vector<uint8_t> header = bam_header_bytes(c->hdr.text, c->hdr.refs);
         // the resident store, unless it does not fit or the hook asks for the stream
         const uint64_t hook = stream_window_hook();
-        StorePlan plan{};
-        bool streamed = hook != 0;
-        if (!streamed) {
-            try { plan = plan_record_store(c.get(), header.size(), 12, "fixing the bins of"); }
-            catch (const Error& e) { if (e.code != SBX_ENOMEM) throw; streamed = true; }
-        }
-        if (streamed) { fixbins_streamed(c, out_file, in_path, header, hook, level, w0, stats, stream_stats); return; }
+        const std::optional<StorePlan> fits = hook ? std::nullopt : try_plan_record_store(c.get(), header.size(), 12, "fixing the bins of");
+        if (!fits) { fixbins_streamed(c, out_file, in_path, header, hook, level, w0, stats, stream_stats); return; }
+        const StorePlan& plan = *fits;
         const uint64_t u_first = plan.u_first;
         hipStream_t s = c->stream.get();
         DevBuf<uint8_t> d_store((size_t)plan.store_bytes + 64);
-        DevBuf<uint64_t> d_off;
-        DevBuf<uint32_t> d_len;
-        DevBuf<unsigned long long> d_acc(kBinFixWords);
-        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kBinFixWords * sizeof(unsigned long long), s));
-        SBX_HIP(hipStreamSynchronize(s));
+        BinPass bins(c.get(), u_first, s);
         const double w1 = wall_now();
 
         // ---- the read pass ----
         sbx_fixbins_stats st{};
-        EventTimer t_k;
-        uint64_t n = 0, cur = u_first;
         uint32_t n_batches = 0;
-        bool too_many = false;
-        unsigned long long acc[kBinFixWords] = {0};
         for_each_record_batch(c.get(), plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-            if (n + nrec > 0xFFFFFFF0ull) { too_many = true; return false; }
-            const size_t want = (size_t)(n + nrec + 2);
-            grow_keeping(d_off, (size_t)n, want, s);
-            grow_keeping(d_len, (size_t)n, want, s);
-            t_k.start(s);
-            copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
-            BinFixArgs a{};
-            a.store = d_store.p; a.desc = c->d_desc.p; a.n = nrec;
-            a.store_delta = (int64_t)base - (int64_t)u_first;
-            a.store_end = next - u_first;
-            a.out_base = n;
-            a.off = d_off.p; a.len = d_len.p; a.acc = d_acc.p;
-            launch_fix_bins(a, s);
-            t_k.stop(s);
-            // (the next batch's K1 / K2 overwrite U and the descriptors: K16b and the copy end first)
-            SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipStreamSynchronize(s));
-            st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_bins += t_k.ms();
-            n += nrec;
-            cur = next;
-            return acc[kBinFixBad] == 0;
+            if (!bins.books.admit(nrec)) return false;
+            bins.step(nrec, base, next, d_store.p, u_first);
+            return !bins.bad();
         });
-        if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-        if (acc[kBinFixBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kBinFixBad], in_path));
+        bins.finish(in_path, &st);
+        const uint64_t n = bins.books.n;
         const uint64_t u_total = plan.u_total;
         c.reset();                                       // the batch buffers make room for the output pieces
         const double w2 = wall_now();
@@ -156,11 +160,10 @@ int sbx_fixbins_run(const char* in_path, const char* out_path, int level, int de
         DevBuf<uint32_t> d_perm((size_t)n + 2);
         launch_iota(d_perm.p, n, s);
         DevBuf<uint64_t> d_out_off((size_t)n + 2);
-        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, d_perm.p, n, d_out_off.p, level, &acc[kBinFixBytes],
+        const WrittenBam w = write_store_output(out_file, header, d_store.p, bins.d_off.p, bins.d_len, d_perm.p, n, d_out_off.p, level, &bins.books.acc[kBinFixBytes],
                                                 "records", s, &st.ms_gather);
         out_file.disarm();
         const double w3 = wall_now();
-        st.n_records = n; st.n_bins_changed = acc[kBinFixChanged];
         st.inflated_bytes = u_total; st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
         st.n_batches = n_batches;
         st.ms_deflate = w.ms_deflate;

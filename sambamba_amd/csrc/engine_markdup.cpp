@@ -1,5 +1,9 @@
 // engine_markdup.cpp -- sbx_markdup: `sambamba markdup` (sambamba/markdup.d) on the device.
 //
+// Both paths below share their steps: EndsPass::step is the one batch step around K10a, pair_and_mark runs K10b and K10c with the
+// pairing kernel as its one varying part, fill_counts fills the counters of the stats.  What a path adds is its own: where the
+// records stay, and the output tail.
+//
 // The read pass is that of sbx_sort_bam (engine_store.hpp: every batch of records is copied into the resident record store); per
 // batch K10a (markdup.hip) describes every record -- class, position key, score, name + RG hash.  Then, over the whole file: the
 // pairable records are sorted by hash and paired inside the runs (K10b); the pairs are sorted by their three key words, the single
@@ -157,6 +161,112 @@ constexpr uint64_t kStreamedPerRecord = 98;
 // one, and the store grows by half whenever a batch does not fit (the old and the new buffer exist side by side for that moment).
 constexpr uint64_t kStreamedKeyBytes = 48;
 
+// The read pass of both paths: the per-record arrays K10a fills while the batches arrive, and the one batch step around it.
+struct EndsPass {
+    sbx_ctx* c;
+    const MdJob& job;
+    hipStream_t s;
+    PassBooks<kMdAccWords> books;
+    DevBuf<uint64_t> d_off, d_pos_key, d_hash;
+    DevBuf<uint32_t> d_len, d_score, d_rg_at;
+    DevBuf<uint8_t> d_cls;
+    EventTimer t_k;
+    double ms_ends = 0;
+    uint64_t cur;                   // inflated offset of the file behind the batches so far
+
+    EndsPass(sbx_ctx* c_, const MdJob& job_, uint64_t u_first, hipStream_t s_) : c(c_), job(job_), s(s_), cur(u_first) { books.init(s); }
+    MdRecords records() const { return MdRecords{d_off.p, d_len.p, d_cls.p, d_pos_key.p, d_score.p, d_hash.p, d_rg_at.p}; }
+    // K10a over a batch of for_each_record_batch (books.admit(nrec) has said yes).  d_store: the resident record store -- the batch's
+    // bytes are copied behind those of the batches before, inside the timed interval, and off[] holds store offsets -- or null
+    // (the streamed path: K10e overwrites off[] of the pairable records).  behind(): what the path queues behind K10a and in front
+    // of the read-back that ends the step.
+    template <class Behind>
+    void step(uint64_t nrec, uint64_t base, uint64_t next, uint8_t* d_store, uint64_t u_first, Behind&& behind) {
+        const uint64_t n = books.n;
+        const size_t want = (size_t)(n + nrec + 2);
+        grow_keeping(d_off, (size_t)n, want, s);
+        grow_keeping(d_pos_key, (size_t)n, want, s);
+        grow_keeping(d_hash, (size_t)n, want, s);
+        grow_keeping(d_len, (size_t)n, want, s);
+        grow_keeping(d_score, (size_t)n, want, s);
+        grow_keeping(d_rg_at, (size_t)n, want, s);
+        grow_keeping(d_cls, (size_t)n, want, s);
+        MdEndsArgs a{};
+        a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base;
+        a.n_ref = job.n_ref; a.ref_bits = job.ref_bits; a.hash_mask = job.hash_mask;
+        a.store_delta = d_store ? (int64_t)base - (int64_t)u_first : 0;
+        a.out_base = n;
+        a.lib = job.table();
+        a.r = records();
+        a.acc = books.d_acc.p;
+        t_k.start(s);
+        if (d_store) copy_batch_to_store(c, d_store, u_first, cur, base, next, s);
+        launch_md_ends(a, s);
+        t_k.stop(s);
+        behind();
+        // (the next batch's K1 / K2 overwrite U and the descriptors: K10a and the copy end first)
+        books.read_back(c, nrec, s);
+        ms_ends += t_k.ms();
+        cur = next;
+    }
+    bool bad() const { return books.acc[kMdAccBad] != 0; }
+    // after the pass
+    void refuse() const {
+        books.refuse_too_many();
+        if (bad()) throw Error(SBX_EFORMAT, malformed_records_message(books.acc[kMdAccBad]));
+    }
+};
+
+// the buffers of K10b and K10c (the caller lets go of them: when, sets the peak of its path), and what the two count
+struct MarkWork {
+    DevBuf<uint32_t> d_mate, d_cnt;
+    DevBuf<uint64_t> d_base;
+    WordSorter sorter;
+    GroupBuffers groups;
+    explicit MarkWork(uint64_t n) : d_mate((size_t)n + 2), d_cnt(md_groups(n) + 4), d_base(md_groups(n) + 4) {}
+};
+struct MarkCounts { uint64_t n_pairable = 0, n_pairs = 0, n_single = 0; };
+
+// K10b, then K10c, over the n records of the pass: d_dup[record] = 1 for every duplicate.  What varies between the paths:
+// pair_runs(sorted hashes, their records, n_pairable, d_mate) is the pairing kernel -- it compares names in the record store or in
+// the key store --; between() lets go of what the path needs no more once the pairs are made; behind() queues what the path counts
+// into ms_groups behind K10c.  Ends with the accumulators read back and the stream idle; ms_pairing, ms_groups and n_sort_passes of
+// *st are set.
+template <class PairRuns, class Between, class Behind>
+MarkCounts pair_and_mark(const MdRecords& r, uint64_t n, uint32_t ref_bits, MarkWork& w, PassBooks<kMdAccWords>& books, uint8_t* d_dup, hipStream_t s,
+                   sbx_markdup_stats* st, PairRuns&& pair_runs, Between&& between, Behind&& behind) {
+    MarkCounts k;
+    EventTimer t_pair, t_groups;
+    t_pair.start(s);
+    launch_fill32(w.d_mate.p, kMdNone, n, s);
+    SBX_HIP(hipMemsetAsync(d_dup, 0, (size_t)n + 2, s));
+    k.n_pairable = compact(kMdPredPairable, r.cls, w.d_mate.p, n, w.d_cnt, w.d_base, w.sorter.idx(), s);
+    w.sorter.sort_by(r.hash, k.n_pairable, books.d_acc.p, s);
+    pair_runs(w.sorter.keys(), w.sorter.idx(), k.n_pairable, w.d_mate.p);
+    t_pair.stop(s);
+    SBX_HIP(hipStreamSynchronize(s));
+    st->ms_pairing = t_pair.ms();
+    between();
+    t_groups.start(s);
+    mark_groups(r, n, k.n_pairable, w.d_mate.p, ref_bits, w.sorter, w.d_cnt, w.d_base, books.d_acc.p, d_dup, s, w.groups, &k.n_pairs, &k.n_single);
+    behind();
+    t_groups.stop(s);
+    SBX_HIP(hipMemcpyAsync(books.acc, books.d_acc.p, sizeof books.acc, hipMemcpyDeviceToHost, s));
+    SBX_HIP(hipStreamSynchronize(s));
+    st->ms_groups = t_groups.ms();
+    st->n_sort_passes = w.sorter.passes;
+    return k;
+}
+
+// the counters of the stats, and the times of the read pass (books.acc: as read back behind the last kernel that counts)
+void fill_counts(const EndsPass& pass, const MarkCounts& k, uint64_t n_out, uint32_t n_batches, sbx_markdup_stats* st) {
+    const unsigned long long* acc = pass.books.acc;
+    st->n_records_in = pass.books.n; st->n_records_out = n_out;
+    st->n_end_pairs = k.n_pairs; st->n_single_ends = k.n_single; st->n_unmatched_pairs = acc[kMdAccUnmatched]; st->n_duplicates = acc[kMdAccDup];
+    st->n_batches = n_batches;
+    st->ms_inflate = pass.books.ms_inflate; st->ms_index = pass.books.ms_index; st->ms_ends = pass.ms_ends;
+}
+
 // The streamed path (see the head of this file).  hook: SBX_MARKDUP_WINDOW_BYTES or 0.
 void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool remove, int level, uint64_t hook, double w0,
                       sbx_markdup_stats* stats, sbx_markdup_stream_stats* stream_stats) {
@@ -170,66 +280,44 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
                    " for the encoder and " + std::to_string(budget.cap_bytes) + " for a window of one piece");
     hipStream_t s = c->stream.get();
     job.upload(s);
-    DevBuf<uint64_t> d_off, d_pos_key, d_hash, d_key_off, d_tile_sum;
-    DevBuf<uint32_t> d_len, d_score, d_rg_at, d_key_len;
-    DevBuf<uint8_t> d_cls, d_keys;
+    EndsPass pass(c.get(), job, budget.u_first, s);
+    DevBuf<uint64_t> d_key_off, d_tile_sum;
+    DevBuf<uint32_t> d_key_len;
+    DevBuf<uint8_t> d_keys;
     DevBuf<uint16_t> d_flag;
-    DevBuf<unsigned long long> d_acc(kMdAccWords);
-    SBX_HIP(hipMemsetAsync(d_acc.p, 0, kMdAccWords * sizeof(unsigned long long), s));
-    SBX_HIP(hipStreamSynchronize(s));
+    unsigned long long* acc = pass.books.acc;
     const double w1 = wall_now();
 
     // ---- the key pass: K10a + K10e, nothing copied; the batches are saved ----
     sbx_markdup_stats st{};
     sbx_markdup_stream_stats ss{};
-    EventTimer t_k, t_m, t_e;
+    EventTimer t_m, t_e;
     std::vector<SavedBatch> saved;
-    uint64_t n = 0, key_bytes = 0;
+    uint64_t key_bytes = 0;
     uint32_t n_batches = 0;
-    bool too_many = false;
-    unsigned long long acc[kMdAccWords] = {0};
     for_each_record_batch(c.get(), budget.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-        if (n + nrec > 0xFFFFFFF0ull) { too_many = true; return false; }
-        const size_t want = (size_t)(n + nrec + 2);
-        grow_keeping(d_off, (size_t)n, want, s);
-        grow_keeping(d_pos_key, (size_t)n, want, s);
-        grow_keeping(d_hash, (size_t)n, want, s);
-        grow_keeping(d_len, (size_t)n, want, s);
-        grow_keeping(d_score, (size_t)n, want, s);
-        grow_keeping(d_rg_at, (size_t)n, want, s);
-        grow_keeping(d_cls, (size_t)n, want, s);
-        grow_keeping(d_flag, (size_t)n, want, s);
+        if (!pass.books.admit(nrec)) return false;
+        const uint64_t first = pass.books.n;
+        grow_keeping(d_flag, (size_t)first, (size_t)(first + nrec + 2), s);
         d_key_len.ensure((size_t)nrec + 2);
         d_key_off.ensure((size_t)nrec + 2);
         d_tile_sum.ensure(len_tiles(nrec) + 2);
-        MdEndsArgs a{};
-        a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base;
-        a.n_ref = job.n_ref; a.ref_bits = job.ref_bits; a.hash_mask = job.hash_mask;
-        a.store_delta = 0;                               // (no store: K10e overwrites off[] of the pairable records)
-        a.out_base = n;
-        a.lib = job.table();
-        a.r = MdRecords{d_off.p, d_len.p, d_cls.p, d_pos_key.p, d_score.p, d_hash.p, d_rg_at.p};
-        a.acc = d_acc.p;
         MdKeyArgs k{};
-        k.U = a.U; k.desc = a.desc; k.n = nrec; k.out_base = n; k.r = a.r;
+        k.U = c->U(); k.desc = c->d_desc.p; k.n = nrec; k.out_base = first;
         k.flag = d_flag.p; k.key_len = d_key_len.p; k.key_off = d_key_off.p;
-        t_k.start(s);
-        launch_md_ends(a, s);
-        t_k.stop(s);
-        t_m.start(s);
-        launch_md_key_measure(k, s);
-        launch_sorted_offsets(d_key_len.p, nullptr, nrec, key_bytes, d_tile_sum.p, d_key_off.p, s);
-        t_m.stop(s);
         uint64_t key_end = key_bytes;
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        if (nrec) SBX_HIP(hipMemcpyAsync(&key_end, d_key_off.p + nrec, 8, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_ends += t_k.ms() + t_m.ms();
+        pass.step(nrec, base, next, nullptr, 0, [&] {
+            k.r = pass.records();
+            t_m.start(s);
+            launch_md_key_measure(k, s);
+            launch_sorted_offsets(d_key_len.p, nullptr, nrec, key_bytes, d_tile_sum.p, d_key_off.p, s);
+            t_m.stop(s);
+            if (nrec) SBX_HIP(hipMemcpyAsync(&key_end, d_key_off.p + nrec, 8, hipMemcpyDeviceToHost, s));
+        });
         ss.ms_keys += t_m.ms();
-        saved.back().first_kept = n;
+        saved.back().first_kept = first;
         saved.back().n_kept = nrec;
-        n += nrec;
-        if (acc[kMdAccBad]) return false;
+        if (pass.bad()) return false;
         grow_keeping(d_keys, (size_t)key_bytes, (size_t)key_end + 64, s);       // (SBX_ENOMEM when the keys do not fit)
         k.key_store = d_keys.p;
         t_e.start(s);
@@ -237,50 +325,29 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
         t_e.stop(s);
         // (the next batch's K1 / K2 overwrite U and the descriptors: K10e ends first)
         SBX_HIP(hipStreamSynchronize(s));
-        st.ms_ends += t_e.ms();
         ss.ms_keys += t_e.ms();
         key_bytes = key_end;
         return true;
     }, &saved);
-    if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-    if (acc[kMdAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kMdAccBad]));
+    pass.refuse();
+    const uint64_t n = pass.books.n;
     const double w2 = wall_now();
 
-    // ---- K10b over the key store ----
-    const MdRecords r{d_off.p, d_len.p, d_cls.p, d_pos_key.p, d_score.p, d_hash.p, d_rg_at.p};
+    // ---- K10b over the key store, K10c ----
+    const MdRecords r = pass.records();
     DevBuf<uint8_t> d_dup((size_t)n + 2);
-    uint64_t n_pairable = 0, n_pairs = 0, n_single = 0;
-    uint32_t n_passes = 0;
+    MarkCounts marked;
     {
-        DevBuf<uint32_t> d_mate((size_t)n + 2), d_cnt(md_groups(n) + 4);
-        DevBuf<uint64_t> d_base(md_groups(n) + 4);
-        WordSorter sorter;
-        sorter.reserve(n);
-        EventTimer t_pair, t_groups;
-        t_pair.start(s);
-        launch_fill32(d_mate.p, kMdNone, n, s);
-        SBX_HIP(hipMemsetAsync(d_dup.p, 0, (size_t)n + 2, s));
-        n_pairable = compact(kMdPredPairable, d_cls.p, d_mate.p, n, d_cnt, d_base, sorter.idx(), s);
-        sorter.sort_by(d_hash.p, n_pairable, d_acc.p, s);
-        launch_md_pair_runs_keys(sorter.keys(), sorter.idx(), n_pairable, d_keys.p, r, d_mate.p, s);
-        t_pair.stop(s);
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_pairing = t_pair.ms();
-        d_hash.release();
-        d_keys.release();
-        d_off.release();
-        d_rg_at.release();
-
-        // ---- K10c ----
-        GroupBuffers groups;
-        t_groups.start(s);
-        mark_groups(r, n, n_pairable, d_mate.p, job.ref_bits, sorter, d_cnt, d_base, d_acc.p, d_dup.p, s, groups, &n_pairs, &n_single);
-        t_groups.stop(s);
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_groups = t_groups.ms();
-        n_passes = sorter.passes;
+        MarkWork w(n);
+        w.sorter.reserve(n);
+        marked = pair_and_mark(
+            r, n, job.ref_bits, w, pass.books, d_dup.p, s, &st,
+            [&](const uint64_t* hashes, const uint32_t* idx, uint64_t n_pairable, uint32_t* d_mate) {
+                launch_md_pair_runs_keys(hashes, idx, n_pairable, d_keys.p, r, d_mate, s);
+            },
+            [&] { pass.d_hash.release(); d_keys.release(); pass.d_off.release(); pass.d_rg_at.release(); }, [] {});
     }
-    d_pos_key.release(); d_score.release(); d_cls.release();
+    pass.d_pos_key.release(); pass.d_score.release(); pass.d_cls.release();
 
     // ---- the output plan: lengths in the output, destinations, the span of every batch ----
     DevBuf<uint8_t> d_hi((size_t)n + 2);
@@ -293,12 +360,12 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
         d_tile_sum.ensure(len_tiles(n) + 2);
         EventTimer t;
         t.start(s);
-        launch_md_out_plan(d_flag.p, d_dup.p, d_len.p, n, remove ? 1u : 0u, d_hi.p, d_out_len.p, d_acc.p, s);
+        launch_md_out_plan(d_flag.p, d_dup.p, pass.d_len.p, n, remove ? 1u : 0u, d_hi.p, d_out_len.p, pass.books.d_acc.p, s);
         launch_sorted_offsets(d_out_len.p, nullptr, n, hlen, d_tile_sum.p, d_dest.p, s);
         spans.launch(d_dest.p, d_out_len.p, s);
         t.stop(s);
         if (n) SBX_HIP(hipMemcpyAsync(&total, d_dest.p + n, 8, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipMemcpyAsync(acc, pass.books.d_acc.p, sizeof pass.books.acc, hipMemcpyDeviceToHost, s));
         spans.read_back(s);
         ss.ms_plan = t.ms();
     }
@@ -311,7 +378,7 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
                                            const sortc::Window& win, uint8_t* d_win, unsigned long long* d_wacc, hipStream_t ws) {
         MdScatterArgs a{};
         a.U = c->U(); a.desc = c->d_desc.p; a.n = rb.nrec; a.u_end = rb.next - rb.base; a.first = sb.first_kept;
-        a.dest = d_dest.p; a.len = d_len.p; a.out_len = d_out_len.p; a.hi = d_hi.p;
+        a.dest = d_dest.p; a.len = pass.d_len.p; a.out_len = d_out_len.p; a.hi = d_hi.p;
         a.w0 = win.w0; a.w1 = win.w1; a.window = d_win; a.acc = d_wacc;
         launch_md_window_scatter(a, ws);
     });
@@ -321,13 +388,12 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
     ss.ms_scatter = w.ms_scatter; ss.ms_inflate_replay = w.ms_inflate_replay; ss.ms_index_replay = w.ms_index_replay;
     ss.n_windows = w.n_windows; ss.n_batch_runs = (uint32_t)w.n_batch_runs; ss.n_batches_skipped = (uint32_t)w.n_batches_skipped;
     st.ms_gather = ss.ms_plan + ss.ms_scatter;
-    st.n_records_in = n; st.n_records_out = n_out;
-    st.n_end_pairs = n_pairs; st.n_single_ends = n_single; st.n_unmatched_pairs = acc[kMdAccUnmatched]; st.n_duplicates = acc[kMdAccDup];
+    fill_counts(pass, marked, n_out, n_batches, &st);
+    st.ms_ends += ss.ms_keys;                            // (K10e counts as part of the ends)
     st.inflated_bytes = budget.u_total; st.stream_bytes = total; st.compressed_bytes = w.compressed_bytes;
-    st.n_sort_passes = n_passes; st.n_batches = n_batches;
     st.ms_deflate = w.ms_deflate;
     st.ms_total_wall = (w4 - w0) * 1e3;
-    ss.window_bytes = w.span; ss.key_store_bytes = key_bytes; ss.n_key_records = n_pairable;
+    ss.window_bytes = w.span; ss.key_store_bytes = key_bytes; ss.n_key_records = marked.n_pairable;
     if (getenv("SBX_TIMING")) {
         fprintf(stderr, "[sbx] markdup-stream: n_windows=%u window_bytes=%llu n_batch_runs=%u n_batches_skipped=%u key_store_bytes=%llu "
                         "n_key_records=%llu ms_keys=%.2f ms_plan=%.2f ms_scatter=%.2f ms_inflate_replay=%.2f ms_index_replay=%.2f\n",
@@ -383,138 +449,76 @@ int sbx_markdup_run(const char* in_path, const char* out_path, int remove_duplic
         const int32_t n_lib = mdc::read_group_libraries(ph, &job.library_of);
         if (!mdc::key_fits(n_lib, n_ref))
             throw Error(SBX_EUNSUPPORTED, std::to_string(n_lib) + " libraries and " + std::to_string(n_ref) + " references do not fit the 64-bit position key");
-        const uint32_t ref_bits = job.ref_bits = mdc::ref_bits_of(n_ref);
+        job.ref_bits = mdc::ref_bits_of(n_ref);
         for (const sortc::HeaderLine& l : ph.rg) { job.rg_off.push_back((uint32_t)job.rg_ids.size()); job.rg_ids += l.id; job.rg_ids.push_back('\0'); }
         if (const char* e = getenv("SBX_MARKDUP_HASH_BITS")) {
             const unsigned long b = strtoul(e, nullptr, 10);
             if (b < 64) job.hash_mask = (1ull << b) - 1ull;
         }
-        const uint64_t hash_mask = job.hash_mask;
 
         // The records stay on the device when they fit; otherwise (or when the hook says so) the file is streamed.
         const uint64_t hook = markdup_window_hook();
-        StorePlan plan{};
-        bool streamed = hook != 0;
-        if (!streamed) {
-            try {
-                plan = plan_record_store(c.get(), hlen, 96, "marking the duplicates of");
-            } catch (const Error& e) {
-                if (e.code != SBX_ENOMEM) throw;
-                streamed = true;
-            }
-        }
-        if (streamed) {
+        const std::optional<StorePlan> fits = hook ? std::nullopt : try_plan_record_store(c.get(), hlen, 96, "marking the duplicates of");
+        if (!fits) {
             markdup_streamed(c, out_file, job, remove_duplicates != 0, level, hook, w0, stats, stream_stats);
             return;
         }
-        const uint64_t u_first = plan.u_first;
+        const StorePlan& plan = *fits;
+        const uint64_t u_first = plan.u_first, u_total = plan.u_total;
         hipStream_t s = c->stream.get();
         DevBuf<uint8_t> d_store((size_t)plan.store_bytes + 64);
         job.upload(s);
-        DevBuf<uint64_t> d_off, d_pos_key, d_hash;
-        DevBuf<uint32_t> d_len, d_score, d_rg_at;
-        DevBuf<uint8_t> d_cls;
-        DevBuf<unsigned long long> d_acc(kMdAccWords);
-        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kMdAccWords * sizeof(unsigned long long), s));
-        SBX_HIP(hipStreamSynchronize(s));
+        EndsPass pass(c.get(), job, u_first, s);
         const double w1 = wall_now();
 
         // ---- the read pass ----
         sbx_markdup_stats st{};
-        EventTimer t_k;
-        uint64_t n = 0, cur = u_first;
         uint32_t n_batches = 0;
-        bool too_many = false;
-        unsigned long long acc[kMdAccWords] = {0};
         for_each_record_batch(c.get(), plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-            if (n + nrec > 0xFFFFFFF0ull) { too_many = true; return false; }
-            const size_t want = (size_t)(n + nrec + 2);
-            grow_keeping(d_off, (size_t)n, want, s);
-            grow_keeping(d_pos_key, (size_t)n, want, s);
-            grow_keeping(d_hash, (size_t)n, want, s);
-            grow_keeping(d_len, (size_t)n, want, s);
-            grow_keeping(d_score, (size_t)n, want, s);
-            grow_keeping(d_rg_at, (size_t)n, want, s);
-            grow_keeping(d_cls, (size_t)n, want, s);
-            t_k.start(s);
-            copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
-            MdEndsArgs a{};
-            a.U = c->U(); a.desc = c->d_desc.p; a.n = nrec; a.u_end = next - base;
-            a.n_ref = n_ref; a.ref_bits = ref_bits; a.hash_mask = hash_mask;
-            a.store_delta = (int64_t)base - (int64_t)u_first;
-            a.out_base = n;
-            a.lib = job.table();
-            a.r = MdRecords{d_off.p, d_len.p, d_cls.p, d_pos_key.p, d_score.p, d_hash.p, d_rg_at.p};
-            a.acc = d_acc.p;
-            launch_md_ends(a, s);
-            t_k.stop(s);
-            // (the next batch's K1 / K2 overwrite U and the descriptors: K10a and the copy end first)
-            SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-            SBX_HIP(hipStreamSynchronize(s));
-            st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_ends += t_k.ms();
-            n += nrec;
-            cur = next;
-            return acc[kMdAccBad] == 0;
+            if (!pass.books.admit(nrec)) return false;
+            pass.step(nrec, base, next, d_store.p, u_first, [] {});
+            return !pass.bad();
         });
-        if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-        if (acc[kMdAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kMdAccBad]));
-        const uint64_t u_total = plan.u_total;
+        pass.refuse();
+        const uint64_t n = pass.books.n;
         c.reset();                                       // the batch buffers make room for the sorts and the output pieces
         const double w2 = wall_now();
 
-        // ---- K10b: pairing ----
+        // ---- K10b: pairing; K10c: pair groups, fragment groups; K10d ----
         Stream stream;
         stream.create();
         s = stream.get();
-        const MdRecords r{d_off.p, d_len.p, d_cls.p, d_pos_key.p, d_score.p, d_hash.p, d_rg_at.p};
-        DevBuf<uint32_t> d_mate((size_t)n + 2), d_cnt(md_groups(n) + 4);
-        DevBuf<uint64_t> d_base(md_groups(n) + 4);
+        const MdRecords r = pass.records();
+        MarkWork work(n);
         DevBuf<uint8_t> d_dup((size_t)n + 2), d_keep((size_t)n + 2);
-        WordSorter sorter;
-        sorter.reserve(n);
-        EventTimer t_pair, t_groups;
-        t_pair.start(s);
-        launch_fill32(d_mate.p, kMdNone, n, s);
-        SBX_HIP(hipMemsetAsync(d_dup.p, 0, (size_t)n + 2, s));
-        const uint64_t n_pairable = compact(kMdPredPairable, d_cls.p, d_mate.p, n, d_cnt, d_base, sorter.idx(), s);
-        sorter.sort_by(d_hash.p, n_pairable, d_acc.p, s);
-        launch_md_pair_runs(sorter.keys(), sorter.idx(), n_pairable, d_store.p, r, d_mate.p, s);
-        t_pair.stop(s);
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_pairing = t_pair.ms();
-        d_hash.release();
-
-        // ---- K10c: pair groups, fragment groups; K10d ----
-        t_groups.start(s);
-        uint64_t n_pairs = 0, n_single = 0;
-        GroupBuffers groups;
-        mark_groups(r, n, n_pairable, d_mate.p, ref_bits, sorter, d_cnt, d_base, d_acc.p, d_dup.p, s, groups, &n_pairs, &n_single);
-        launch_md_patch_flags(d_store.p, d_off.p, d_dup.p, n, remove_duplicates ? 1u : 0u, d_keep.p, d_acc.p, s);
-        // the records that are written, in file order
-        DevBuf<uint32_t> d_perm((size_t)n + 2);
+        work.sorter.reserve(n);
+        DevBuf<uint32_t> d_perm;            // the records that are written, in file order
         uint64_t n_out = n;
-        if (remove_duplicates) n_out = compact(kMdPredKeep, d_keep.p, nullptr, n, d_cnt, d_base, d_perm.p, s);
-        else launch_iota(d_perm.p, n, s);
-        t_groups.stop(s);
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_groups = t_groups.ms();
-        const uint32_t n_passes = sorter.passes;
-        sorter = WordSorter();
-        groups = GroupBuffers();
-        d_mate.release(); d_dup.release(); d_keep.release();
-        d_pos_key.release(); d_score.release(); d_rg_at.release(); d_cls.release();
+        const MarkCounts marked = pair_and_mark(
+            r, n, job.ref_bits, work, pass.books, d_dup.p, s, &st,
+            [&](const uint64_t* hashes, const uint32_t* idx, uint64_t n_pairable, uint32_t* d_mate) {
+                launch_md_pair_runs(hashes, idx, n_pairable, d_store.p, r, d_mate, s);
+            },
+            [&] { pass.d_hash.release(); },
+            [&] {
+                launch_md_patch_flags(d_store.p, r.off, d_dup.p, n, remove_duplicates ? 1u : 0u, d_keep.p, pass.books.d_acc.p, s);
+                d_perm.alloc((size_t)n + 2);
+                if (remove_duplicates) n_out = compact(kMdPredKeep, d_keep.p, nullptr, n, work.d_cnt, work.d_base, d_perm.p, s);
+                else launch_iota(d_perm.p, n, s);
+            });
+        work.sorter = WordSorter();
+        work.groups = GroupBuffers();
+        work.d_mate.release(); d_dup.release(); d_keep.release();
+        pass.d_pos_key.release(); pass.d_score.release(); pass.d_rg_at.release(); pass.d_cls.release();
 
         // ---- the output ----
         DevBuf<uint64_t> d_out_off((size_t)n_out + 2);
-        const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, d_perm.p, n_out, d_out_off.p, level,
-                                                remove_duplicates ? nullptr : &acc[kMdAccBytes], "records", s, &st.ms_gather);
+        const WrittenBam w = write_store_output(out_file, header, d_store.p, pass.d_off.p, pass.d_len, d_perm.p, n_out, d_out_off.p, level,
+                                                remove_duplicates ? nullptr : &pass.books.acc[kMdAccBytes], "records", s, &st.ms_gather);
         out_file.disarm();
         const double w3 = w.w_planned, w4 = wall_now();
-        st.n_records_in = n; st.n_records_out = n_out;
-        st.n_end_pairs = n_pairs; st.n_single_ends = n_single; st.n_unmatched_pairs = acc[kMdAccUnmatched]; st.n_duplicates = acc[kMdAccDup];
+        fill_counts(pass, marked, n_out, n_batches, &st);
         st.inflated_bytes = u_total; st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
-        st.n_sort_passes = n_passes; st.n_batches = n_batches;
         st.ms_deflate = w.ms_deflate;
         st.ms_total_wall = (w4 - w0) * 1e3;
         if (getenv("SBX_TIMING")) print_markdup_line(st, (w1 - w0) * 1e3, (w2 - w1) * 1e3, (w3 - w2) * 1e3, (w4 - w3) * 1e3);

@@ -8,7 +8,7 @@
 // deflate kernels (bgzf_compress_pieces) and, through pinned memory, to the file.  The sorted stream never exists as a whole.
 //
 // The scaffold of the entry point, the plan of the store, the copy into it and the output tail are engine_store.hpp, shared with
-// sbx_markdup, sbx_merge_bam and sbx_view_bam.
+// sbx_markdup, sbx_merge_bam and sbx_view_bam.  KeyPass::step is the one batch step around K9a: both paths below call it.
 //
 // A file whose records do not fit the device next to one batch of the read pass takes the WINDOWED path (sort_file_windowed; also
 // forced by SBX_SORT_WINDOW_BYTES): no record store.  The key pass runs K9a alone and saves its batches (for_each_record_batch with
@@ -140,6 +140,65 @@ uint64_t window_bytes_hook() { return env_u64("SBX_SORT_WINDOW_BYTES").value_or(
 
 constexpr uint64_t kWindowedPerRecord = 36;     // bytes per record while the keys are sorted: key, key2, len, val, val2, dest / out_off
 
+// The read pass of both paths: the keys, lengths and -- with a store -- offsets of the records that take part while the batches arrive,
+// and the one batch step around K9a.
+struct KeyPass {
+    sbx_ctx* c;
+    bool use_filter;
+    hipStream_t s;
+    PassBooks<kSortAccWords> books;
+    DevBuf<uint64_t> d_key, d_off, d_group_base;
+    DevBuf<uint32_t> d_len, d_group_count;
+    EventTimer t_k;
+    double ms_keys = 0;
+    uint64_t n_kept = 0;            // records that received a key in the batches so far
+    uint64_t cur;                   // inflated offset of the file behind the batches so far
+
+    KeyPass(sbx_ctx* c_, bool use_filter_, uint64_t u_first, hipStream_t s_) : c(c_), use_filter(use_filter_), s(s_), cur(u_first) {
+        books.acc[kSortAccAnd] = ~0ull;
+        books.init(s);
+    }
+    // K9a over a batch of for_each_record_batch; returns how many of its records received a key (they are [n_kept - that, n_kept)).
+    // d_store: the resident record store -- the batch's bytes are copied behind those of the batches before, inside the timed
+    // interval, and off[] is written -- or null: nothing is copied and no offset kept (the windowed path).
+    uint64_t step(uint64_t nrec, uint64_t base, uint64_t next, uint8_t* d_store, uint64_t u_first) {
+        const int32_t n_ref = (int32_t)c->hdr.refs.size();
+        const size_t want = (size_t)(n_kept + nrec + 2);
+        grow_keeping(d_key, (size_t)n_kept, want, s);
+        if (d_store) grow_keeping(d_off, (size_t)n_kept, want, s);
+        grow_keeping(d_len, (size_t)n_kept, want, s);
+        if (use_filter) { d_group_count.ensure(sort_keys_groups(nrec) + 4); d_group_base.ensure(sort_keys_groups(nrec) + 4); }
+        SortKeysArgs a{};
+        a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
+        a.n_ref = n_ref; a.key_n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
+        a.store_delta = d_store ? (int64_t)base - (int64_t)u_first : 0;
+        a.out_base = n_kept;
+        a.key = d_key.p; a.off = d_store ? d_off.p : nullptr; a.len = d_len.p; a.acc = books.d_acc.p;
+        t_k.start(s);
+        if (d_store) copy_batch_to_store(c, d_store, u_first, cur, base, next, s);
+        launch_sort_keys(a, d_group_count.p, d_group_base.p, s);
+        t_k.stop(s);
+        // (the next batch's K1 / K2 overwrite U and the descriptors: K9a and the copy end first)
+        books.read_back(c, nrec, s);
+        ms_keys += t_k.ms();
+        const uint64_t kept = books.acc[kSortAccKept] - n_kept;
+        n_kept = books.acc[kSortAccKept];
+        cur = next;
+        return kept;
+    }
+    bool bad() const { return books.acc[kSortAccBad] != 0; }
+    // after the pass
+    void refuse_bad() const {
+        if (bad()) throw Error(SBX_EFORMAT, malformed_records_message(books.acc[kSortAccBad]));
+    }
+    void check_counts() const {
+        if (!use_filter && n_kept != books.n)
+            throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(books.n) + " records received a key");
+        books.refuse_too_many(n_kept);
+    }
+    void times(sbx_sort_stats* st) const { st->ms_inflate = books.ms_inflate; st->ms_index = books.ms_index; st->ms_keys += ms_keys; }
+};
+
 // The coordinate sort of a file whose records do not stay on the device (or SBX_SORT_WINDOW_BYTES): the keys of the whole file are
 // sorted as in sort_file, the order becomes one destination per record (K9d-1), and the sorted stream is written window by window
 // (write_windows): the batches of the key pass whose destinations meet the window (K9d-2) are run again and K9d-3 puts their records
@@ -147,52 +206,28 @@ constexpr uint64_t kWindowedPerRecord = 36;     // bytes per record while the ke
 void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<uint8_t>& header, bool use_filter, int level, uint64_t hook,
                         double w0, sbx_sort_stats* stats) {
     const uint64_t hlen = header.size();
-    const int32_t n_ref = (int32_t)c->hdr.refs.size();
     WindowBudget budget(c.get(), hlen, sortc::kSortWindowWords, hook);
     budget.fit(budget.est_records * kWindowedPerRecord, "the keys of its records, one read batch, the encoder and a window of one piece");
     hipStream_t s = c->stream.get();
-    DevBuf<uint64_t> d_key;
-    DevBuf<uint32_t> d_len, d_group_count, d_rank;
-    DevBuf<uint64_t> d_group_base;
-    DevBuf<unsigned long long> d_acc(kSortAccWords);
-    unsigned long long acc[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
-    SBX_HIP(hipMemcpyAsync(d_acc.p, acc, sizeof acc, hipMemcpyHostToDevice, s));
-    SBX_HIP(hipStreamSynchronize(s));
+    KeyPass keys(c.get(), use_filter, budget.u_first, s);
+    DevBuf<uint32_t> d_rank;
+    const unsigned long long* acc = keys.books.acc;
     const double w1 = wall_now();
 
     // ---- the key pass: K9a, nothing copied; the batches are saved ----
     sbx_sort_stats st{};
-    EventTimer t_k;
     std::vector<SavedBatch> saved;
-    uint64_t n_in = 0, n_kept = 0;
     uint32_t n_batches = 0;
     for_each_record_batch(c.get(), budget.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-        const size_t want = (size_t)(n_kept + nrec + 2);
-        grow_keeping(d_key, (size_t)n_kept, want, s);
-        grow_keeping(d_len, (size_t)n_kept, want, s);
-        if (use_filter) { d_group_count.ensure(sort_keys_groups(nrec) + 4); d_group_base.ensure(sort_keys_groups(nrec) + 4); }
-        SortKeysArgs a{};
-        a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
-        a.n_ref = n_ref; a.key_n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
-        a.out_base = n_kept;
-        a.key = d_key.p; a.off = nullptr; a.len = d_len.p; a.acc = d_acc.p;
-        t_k.start(s);
-        launch_sort_keys(a, d_group_count.p, d_group_base.p, s);
-        t_k.stop(s);
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_keys += t_k.ms();
-        n_in += nrec;
-        saved.back().first_kept = n_kept;
-        saved.back().n_kept = acc[kSortAccKept] - n_kept;
-        n_kept = acc[kSortAccKept];
-        return !acc[kSortAccBad];
+        saved.back().first_kept = keys.n_kept;
+        saved.back().n_kept = keys.step(nrec, base, next, nullptr, 0);
+        return !keys.bad();
     }, &saved);
-    if (acc[kSortAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSortAccBad]));
-    if (!use_filter && n_kept != n_in)
-        throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(n_in) + " records received a key");
-    if (n_kept > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-    const uint64_t n = n_kept;
+    keys.refuse_bad();
+    keys.check_counts();
+    keys.times(&st);
+    const uint64_t n_in = keys.books.n;
+    const uint64_t n = keys.n_kept;
     const double w2 = wall_now();
 
     // ---- K9b, the offsets, K9d-1 and K9d-2 ----
@@ -202,37 +237,37 @@ void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<
     uint64_t total = hlen;
     {
         ResidentOrder order;
-        sort_resident(d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
+        sort_resident(keys.d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
         st.ms_sort = order.ms_sort;
         st.key_bits = order.key_bits; st.n_sort_passes = order.n_passes;
-        const OutputPlan plan = plan_output(d_len.p, order.perm, n, hlen, order.key2.p, s, &st.ms_gather);
+        const OutputPlan plan = plan_output(keys.d_len.p, order.perm, n, hlen, order.key2.p, s, &st.ms_gather);
         total = plan.total;
         if (total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the sorted records do not add up");
         spans.upload(saved, n, s);
         EventTimer t;
         t.start(s);
         launch_window_dest(order.perm, order.key2.p, n, d_dest.p, s);
-        spans.launch(d_dest.p, d_len.p, s);
+        spans.launch(d_dest.p, keys.d_len.p, s);
         t.stop(s);
         spans.read_back(s);
         ms_dest = t.ms();
         // keys, key2, val / val2 and the offsets go before the first window comes (order: end of this scope)
-        d_key.release();
+        keys.d_key.release();
     }
 
     // ---- the windows: K9d-3 for every saved batch that meets one ----
     const WindowedOutput w = write_windows(c.get(), out_file, header, total, budget, spans, level, [&](const SavedBatch& sb, const RecordBatch& rb,
                                            const sortc::Window& win, uint8_t* d_win, unsigned long long* d_wacc, hipStream_t ws) {
         if (use_filter) {
-            d_group_count.ensure(sort_keys_groups(rb.nrec) + 4);
-            d_group_base.ensure(sort_keys_groups(rb.nrec) + 4);
+            keys.d_group_count.ensure(sort_keys_groups(rb.nrec) + 4);
+            keys.d_group_base.ensure(sort_keys_groups(rb.nrec) + 4);
             d_rank.ensure((size_t)rb.nrec + 2);
         }
         WindowScatterArgs a{};
         a.U = c->U(); a.desc = c->d_desc.p; a.n = rb.nrec; a.u_end = rb.next - rb.base; a.use_filter = use_filter ? 1u : 0u;
         a.first_kept = sb.first_kept; a.n_kept = sb.n_kept;
-        a.dest = d_dest.p; a.len = d_len.p; a.w0 = win.w0; a.w1 = win.w1; a.window = d_win; a.acc = d_wacc;
-        launch_window_scatter(a, d_group_count.p, d_group_base.p, d_rank.p, ws);
+        a.dest = d_dest.p; a.len = keys.d_len.p; a.w0 = win.w0; a.w1 = win.w1; a.window = d_win; a.acc = d_wacc;
+        launch_window_scatter(a, keys.d_group_count.p, keys.d_group_base.p, d_rank.p, ws);
     });
     out_file.disarm();
     const double w3 = w.w_planned, w4 = w.w_written;
@@ -262,7 +297,6 @@ void sort_file(const char* in_path, const char* out_path, const sbx_filter* filt
     const bool use_filter = has_ops(filter);
     Standalone c = open_record_pass(in_path, device, filter, use_filter);
     OutputGuard out_file(out_path);
-    const int32_t n_ref = (int32_t)c->hdr.refs.size();
     std::string text, why;
     if (!sortc::sort_header_text(c->hdr.text.data(), c->hdr.text.size(), &text, &why, name_order ? "queryname" : "coordinate"))
         throw Error(SBX_EFORMAT, "SAM header: " + why);
@@ -271,80 +305,42 @@ void sort_file(const char* in_path, const char* out_path, const sbx_filter* filt
 
     // per record: key, offset, length and K9b's second key and two values; a name order adds the key's offset, the -M word and
     // -- an estimate, the key store grows with the batches -- four key words
-    // The coordinate order goes through windows when the records do not fit (or the hook says so); the name orders stay resident.
+    // The coordinate order goes through windows when the records do not fit (or the hook says so); the name orders stay resident:
+    // they plan without the "try", and the refusal of the plan is their answer.
     const uint64_t hook = name_order ? 0 : window_bytes_hook();
-    StorePlan plan{};
-    bool windowed = hook != 0;
-    if (!windowed) {
-        try {
-            plan = plan_record_store(c.get(), hlen, name_order ? 48 + 16 + 32 : 48, "sorting");
-        } catch (const Error& e) {
-            if (name_order || e.code != SBX_ENOMEM) throw;
-            windowed = true;
-        }
-    }
-    if (windowed) {
+    std::optional<StorePlan> fits;
+    if (name_order) fits = plan_record_store(c.get(), hlen, 48 + 16 + 32, "sorting");
+    else if (!hook) fits = try_plan_record_store(c.get(), hlen, 48, "sorting");
+    if (!fits) {
         sort_file_windowed(c, out_file, header, use_filter, level, hook, w0, stats);
         return;
     }
-    const uint64_t u_total = plan.u_total, u_first = plan.u_first, store_bytes = plan.store_bytes, batch_u = plan.batch_u;
+    const StorePlan& plan = *fits;
+    const uint64_t u_total = plan.u_total, u_first = plan.u_first;
     hipStream_t s = c->stream.get();
-    DevBuf<uint8_t> d_store((size_t)store_bytes + 64);
-    DevBuf<uint64_t> d_key, d_off;
-    DevBuf<uint32_t> d_len, d_group_count;
-    DevBuf<uint64_t> d_group_base;
-    DevBuf<unsigned long long> d_acc(kSortAccWords);
-    {
-        const unsigned long long init[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
-        SBX_HIP(hipMemcpyAsync(d_acc.p, init, sizeof init, hipMemcpyHostToDevice, s));
-        SBX_HIP(hipStreamSynchronize(s));
-    }
+    DevBuf<uint8_t> d_store((size_t)plan.store_bytes + 64);
+    KeyPass keys(c.get(), use_filter, u_first, s);
+    const unsigned long long* acc = keys.books.acc;
     NameKeys names;
     if (name_order) names.init(name_order, match_mates, s);
     const double w1 = wall_now();
 
     // ---- the read pass ----
     sbx_sort_stats st{};
-    EventTimer t_k;
-    uint64_t n_in = 0, n_kept = 0, cur = u_first;
     uint32_t n_batches = 0;
     bool names_ok = true;
-    unsigned long long acc[kSortAccWords] = {0ull, ~0ull, 0ull, 0ull, 0ull};
-    for_each_record_batch(c.get(), batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
-        const size_t want = (size_t)(n_kept + nrec + 2);
-        grow_keeping(d_key, (size_t)n_kept, want, s);
-        grow_keeping(d_off, (size_t)n_kept, want, s);
-        grow_keeping(d_len, (size_t)n_kept, want, s);
-        if (use_filter) { d_group_count.ensure(sort_keys_groups(nrec) + 4); d_group_base.ensure(sort_keys_groups(nrec) + 4); }
-        t_k.start(s);
-        copy_batch_to_store(c.get(), d_store.p, u_first, cur, base, next, s);
-        SortKeysArgs a{};
-        a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = next - base;
-        a.n_ref = n_ref; a.key_n_ref = n_ref; a.use_filter = use_filter ? 1u : 0u;
-        a.store_delta = (int64_t)base - (int64_t)u_first;
-        a.out_base = n_kept;
-        a.key = d_key.p; a.off = d_off.p; a.len = d_len.p; a.acc = d_acc.p;
-        launch_sort_keys(a, d_group_count.p, d_group_base.p, s);
-        t_k.stop(s);
-        // (the next batch's K1 / K2 overwrite U and the descriptors: K9a and the copy end first)
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_keys += t_k.ms();
-        n_in += nrec;
-        const uint64_t kept_before = n_kept;
-        n_kept = acc[kSortAccKept];
-        cur = next;
-        if (acc[kSortAccBad]) return false;
+    for_each_record_batch(c.get(), plan.batch_u, &n_batches, [&](uint64_t nrec, uint64_t base, uint64_t next) -> bool {
+        const uint64_t kept = keys.step(nrec, base, next, d_store.p, u_first);
+        if (keys.bad()) return false;
         // K14a: the keys of the names of the records K9a kept, read from the store
-        if (name_order) names_ok = names.add_batch(d_store.p, d_off.p, d_len.p, kept_before, n_kept - kept_before, s, &st.ms_keys);
+        if (name_order) names_ok = names.add_batch(d_store.p, keys.d_off.p, keys.d_len.p, keys.n_kept - kept, kept, s, &st.ms_keys);
         return names_ok;
     });
-    if (acc[kSortAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kSortAccBad]));
+    keys.refuse_bad();
     if (name_order) names.refuse_bad();
-    if (!use_filter && n_kept != n_in)
-        throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_kept) + " of " + std::to_string(n_in) + " records received a key");
-    if (n_kept > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
-    const uint64_t n = n_kept;
+    keys.check_counts();
+    keys.times(&st);
+    const uint64_t n_in = keys.books.n, n = keys.n_kept;
     c.reset();                                       // the batch buffers make room for the sort and the output pieces
     const double w2 = wall_now();
 
@@ -354,20 +350,20 @@ void sort_file(const char* in_path, const char* out_path, const sbx_filter* filt
     s = stream.get();
     ResidentOrder order;
     if (name_order) {
-        names.sort(d_key.p, n, s, &order);
+        names.sort(keys.d_key.p, n, s, &order);
         SBX_HIP(hipStreamSynchronize(s));
         names.release();                             // the key store goes before the output pieces come
         order.hist.release();
         order.hist_base.release();
     } else {
-        sort_resident(d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
+        sort_resident(keys.d_key.p, n, acc[kSortAccOr] ^ acc[kSortAccAnd], s, &order);
     }
     // the keys are done with: one of their buffers holds the output offsets
-    d_key.release();
+    keys.d_key.release();
     st.ms_sort = order.ms_sort;
 
     // ---- offsets, K9c + deflate, piece by piece ----
-    const WrittenBam w = write_store_output(out_file, header, d_store.p, d_off.p, d_len, order.perm, n, order.key2.p, level,
+    const WrittenBam w = write_store_output(out_file, header, d_store.p, keys.d_off.p, keys.d_len, order.perm, n, order.key2.p, level,
                                             &acc[kSortAccBytes], "sorted records", s, &st.ms_gather);
     out_file.disarm();
     const double w3 = w.w_planned, w4 = wall_now();

@@ -1,17 +1,21 @@
-// engine_store.hpp -- what sbx_sort_bam, sbx_markdup, sbx_merge_bam and sbx_view_bam share around their kernels.  Each of them reads as:
-// checks, open (run_entry / open_record_pass / OutputGuard, engine_ctx.hpp), header, plan, its own read-pass lambda with its own
-// kernel, order, output tail, stats line.  Here: the plan of the resident record store (1 x the inflated records of the file next to
-// one batch of the read pass), the copy of a batch into it, K9b over the keys of the resident records (sort and merge), and the output
-// tail (write_store_output) that turns "header + records of the store in the order of a permutation" into a BGZF file piece by piece
-// (offsets, piece bounds, K9c gather, deflate) and hands back the figures every stats struct takes from it.  The permutation is a
-// list of record numbers: it may leave records out (a filter) or name one several times (sbx_view_bam with listed regions).  The
-// stream written never exists as a whole.  What the kernels share is wave_prims.hpp.  A file that does not fit the store goes, for
-// sort and markdup, through engine_windows.hpp instead: the same reading order, a key pass for the plan, the windowed writer for the tail.
+// engine_store.hpp -- what sbx_sort_bam, sbx_markdup, sbx_fixbins, sbx_merge_bam and sbx_view_bam share around their kernels.  Each of
+// them reads as: checks, open (run_entry / open_record_pass / OutputGuard, engine_ctx.hpp), header, the decision between the resident
+// record store and the path that keeps none, ONE batch step with the command's kernel that both paths call, order, output tail,
+// stats line.  Here: the plan of the resident record store (1 x the inflated records of the file next to one batch of the read pass)
+// and whether it fits (plan_if_fits / try_plan_record_store); PassBooks, the bookkeeping of a read pass (accumulators, the read-back
+// that ends every batch step, the record count, the K1 / K2 times); the copy of a batch into the store; K9b over the keys of the
+// resident records (sort and merge); and the output tail (write_store_output) that turns "header + records of the store in the order
+// of a permutation" into a BGZF file piece by piece (offsets, piece bounds, K9c gather, deflate) and hands back the figures every
+// stats struct takes.  The permutation is a list of record numbers: it may leave records out (a filter) or name one several times
+// (sbx_view_bam with listed regions).  The stream written never exists as a whole.  What the kernels share is wave_prims.hpp.  A file
+// that does not fit the store goes, for sort and markdup, through engine_windows.hpp instead (the same reading order, a key pass for
+// the plan, the windowed writer for the tail), for fixbins and view in file order through engine_streamout.hpp.
 #pragma once
 #include "engine_ctx.hpp"
 #include "engine_stream.hpp"
 #include "sort.hpp"
 #include "sort_core.hpp"
+#include <optional>
 
 namespace sbx {
 
@@ -79,6 +83,56 @@ inline StorePlan plan_record_store(sbx_ctx* c, uint64_t hlen, uint64_t per_recor
     p.u_first = u_first;
     return p;
 }
+
+// The resident-or-not decision: the plan, or nothing when the store does not fit the device.  Only SBX_ENOMEM means that; every
+// other error passes through.  A command that has no other path (sort -n / -N / -M, merge) calls plan_* itself and keeps the refusal.
+template <class Plan>
+std::optional<StorePlan> plan_if_fits(Plan&& plan) {
+    try {
+        return plan();
+    } catch (const Error& e) {
+        if (e.code != SBX_ENOMEM) throw;
+        return std::nullopt;
+    }
+}
+inline std::optional<StorePlan> try_plan_record_store(sbx_ctx* c, uint64_t hlen, uint64_t per_record, const char* doing) {
+    return plan_if_fits([&] { return plan_record_store(c, hlen, per_record, doing); });
+}
+
+// ---- what every read pass keeps next to its kernel ----
+// The N accumulator words of the command's kernel on the device and their host mirror, the records of the batches so far with the
+// refusal of more than 0xFFFFFFF0 of them, and the K1 / K2 times of the batches.  A batch step ends with read_back(): when it
+// returns the stream is idle, so the next batch's K1 / K2 may overwrite U and the descriptors.
+template <size_t N>
+struct PassBooks {
+    DevBuf<unsigned long long> d_acc{N};
+    unsigned long long acc[N] = {0};
+    uint64_t n = 0;                 // records of the batches that were read back
+    bool too_many = false;
+    double ms_inflate = 0, ms_index = 0;
+    // acc[] -- all 0, or what the caller has put there (sort's are not all 0) -- goes to the device
+    void init(hipStream_t s) {
+        SBX_HIP(hipMemcpyAsync(d_acc.p, acc, sizeof acc, hipMemcpyHostToDevice, s));
+        SBX_HIP(hipStreamSynchronize(s));
+    }
+    // in front of a batch of nrec records: false when the pass has to stop because there are too many (refuse_too_many() says so)
+    bool admit(uint64_t nrec) {
+        too_many = too_many || n + nrec > 0xFFFFFFF0ull;
+        return !too_many;
+    }
+    // the end of a batch step: the accumulators as the kernels queued on s leave them, the batch's records and K1 / K2 times added
+    void read_back(sbx_ctx* c, uint64_t nrec, hipStream_t s) {
+        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
+        SBX_HIP(hipStreamSynchronize(s));
+        ms_inflate += c->stats.ms_inflate;
+        ms_index += c->stats.ms_index;
+        n += nrec;
+    }
+    // kept: records that take part, for a command that counts those (sort)
+    void refuse_too_many(uint64_t kept = 0) const {
+        if (too_many || kept > 0xFFFFFFF0ull) throw Error(SBX_EUNSUPPORTED, "more than 2^32 records");
+    }
+};
 
 // the records of a batch (for_each_record_batch: inflated offsets [cur, next), U[0] = offset `base`) go behind those of the batches before
 inline void copy_batch_to_store(sbx_ctx* c, uint8_t* d_store, uint64_t u_first, uint64_t cur, uint64_t base, uint64_t next, hipStream_t s) {

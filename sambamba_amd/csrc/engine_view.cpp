@@ -15,8 +15,14 @@
 // a piece overlap the kernel of the next.
 //
 // An output in file order -- no region, one listed region, -L -- whose records do not fit the store (or SBX_STREAM_WINDOW_BYTES) keeps
-// none.  view_bam_streamed hands every batch, while it is in U, to the StreamedOutput of engine_streamout.hpp (K21, stream.hip);
-// view_sam_streamed runs K12b, K13a and K13b per batch with the batch as the store.  StreamedSelect is what the two share.
+// none (ViewJob::plan_store decides).  view_bam_streamed hands every batch, while it is in U, to the StreamedOutput of
+// engine_streamout.hpp (K21, stream.hip); view_sam_streamed runs K12b, K13a and K13b per batch with the batch as the store.
+//
+// The shape of the file: ViewJob is the prologue and the epilogue of every sink -- what it derives from the validated
+// sbx_view_request (threshold, context, regions, the indexed read, header text, the output path), the wall time and the timing line.
+// SelectStep is the one per-batch selection step (K19, K12a, the group scans, the read-back, the checks); the count sink, the
+// resident store (select_resident) and both streamed sinks call it and say what K12a is to leave behind.  view_count, view_bam and
+// view_sam take the request itself.
 //
 // sbx_view_run and the three calls of before it read the whole file whatever the regions say (their stats promise n_records_in =
 // the records of the file, and they need no .bai).  sbx_view_run_indexed reads only the blocks the .bai names for the regions: the
@@ -81,20 +87,6 @@ void check_opts(const sbx_filter* filter, const sbx_view_opts* opts, uint64_t* t
     *threshold = 0;
     if (opts && opts->subsample && !viewc::subsample_threshold(opts->fraction, threshold))
         throw Error(SBX_EINVAL, "the subsampling fraction must be a number that is not negative");
-}
-
-ViewSelectArgs select_args(sbx_ctx* c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& regions, const sbx_region* d_regions,
-                           uint64_t nrec, uint64_t u_end, unsigned long long* d_acc, const uint16_t* d_invalid) {
-    ViewSelectArgs a{};
-    a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = u_end;
-    if (opts) {
-        a.flags_set = opts->flags_set; a.flags_unset = opts->flags_unset;
-        a.subsample = opts->subsample ? 1u : 0u; a.seed = opts->seed; a.threshold = threshold;
-    }
-    a.regions = d_regions; a.n_regions = (uint32_t)regions.list.size(); a.regions_merged = regions.merged ? 1u : 0u;
-    a.acc = d_acc;
-    a.invalid = d_invalid;
-    return a;
 }
 
 // view -v: K19 in front of K12a.  run() leaves the masks of the batch's records and returns them; null when the option is off.
@@ -256,6 +248,141 @@ void read_batches(sbx_ctx* c, const IndexedRead& rd, uint64_t batch_u, uint32_t*
     }
 }
 
+// The output order is the file order when no region orders it: no region, one listed region, or the merged list of a BED file.
+bool in_file_order(const ViewRegions& sel) { return sel.merged || sel.list.size() <= 1; }
+
+// ---- what every sink derives from the request: the prologue and the epilogue of a call ----
+struct ViewJob {
+    const sbx_view_request& q;
+    const bool to_stdout;
+    const char* const path;         // of the output; "/dev/stdout" for none or "-"
+    double w0 = 0;
+    uint64_t threshold = 0;         // of -s
+    Standalone c;
+    OutputGuard out_file;
+    ViewRegions sel;
+    IndexedRead rd;
+    std::string text;               // header text of the output, where the sink has one
+
+    static const char* path_of(const sbx_view_request& q) { return !q.out_path || !strcmp(q.out_path, "-") ? "/dev/stdout" : q.out_path; }
+    explicit ViewJob(const sbx_view_request& request)
+        : q(request), to_stdout(path_of(request) != request.out_path), path(path_of(request)), out_file(path, to_stdout) {}
+    // Behind the sink's own argument checks: the options, the input, the regions, the read through the index and -- with_text -- the
+    // header text.
+    void open(int index_mode, bool with_text, sbx_view_index_stats* ix) {
+        check_opts(q.filter, q.opts, &threshold);
+        w0 = wall_now();
+        c = open_record_pass(q.in_path, q.device, q.filter, true);
+        sel = resolve_regions(c.get(), q.regions, q.n_regions, q.bed_path);
+        rd = plan_indexed_read(c.get(), q.in_path, sel, index_mode, ix);
+        std::string why;
+        if (with_text && !mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), q.pg_command_line, &text, &why))
+            throw Error(SBX_EFORMAT, "SAM header: " + why);
+    }
+    // The resident store of select_resident -- it holds the records of the file, or, indexed, the bytes of the runs -- or nothing: the
+    // sink streams.  In file order that is when the hook asks for it or the store does not fit; two or more listed regions need the
+    // store, and its refusal is theirs.  hlen / per_record: bytes of the sink's header and of the per-record arrays it will add.
+    std::optional<StorePlan> plan_store(uint64_t hlen, uint64_t per_record, uint64_t hook) const {
+        auto plan = [&] {
+            return rd.on ? plan_store_bytes(rd.store_bytes, hlen, per_record, "selecting records of", "the blocks the index names for the regions do")
+                         : plan_record_store(c.get(), hlen, per_record, "selecting records of");
+        };
+        if (!in_file_order(sel)) return plan();
+        if (hook) return std::nullopt;
+        return plan_if_fits(plan);
+    }
+    // the epilogue
+    void finish(sbx_view_stats& st, const char* sink, sbx_view_stats* stats) const {
+        st.ms_total_wall = (wall_now() - w0) * 1e3;
+        print_timing(st, sink);
+        if (stats) *stats = st;
+    }
+};
+
+// ---- the one selection step of all sinks ----
+// Per batch: K19 with -v, K12a, the scans of the group sums, the accumulators read back; the checks on them, raised when the batch
+// that trips them is met; at the end the errors and what the pass gives the stats.  What K12a leaves next to the accumulators is the
+// sink's choice: the count sink wants nothing, the streamed BAM sink lengths checked and the entries of every record (K21 reads
+// them), and K12b -- the resident store, the streamed SAM sink -- the group sums and their scans as well.
+struct SelectWants { bool lengths, counts, groups; };
+struct SelectStep {
+    const ViewJob& job;
+    const SelectWants wants;
+    DevBuf<sbx_region> d_regions;
+    DevBuf<uint32_t> d_count, d_group_entries, d_group_records;
+    DevBuf<uint64_t> d_group_entry_base, d_group_record_base;
+    PassBooks<kViewAccWords> books;
+    ValidPass valid;
+    EventTimer t_a;
+    double ms_select = 0;
+    unsigned long long before[kViewAccWords] = {0};    // books.acc in front of the last batch
+    uint64_t inflated = 0;
+    uint32_t n_batches = 0;
+    bool too_many = false;
+    ViewSelectArgs a{};                                 // K12a's arguments for the last batch
+
+    SelectStep(const ViewJob& j, SelectWants w, hipStream_t s) : job(j), wants(w) {
+        upload_regions(job.sel, &d_regions, s);
+        books.init(s);
+        valid.init(job.q.valid_only != 0, s);
+    }
+    // store_at: where the bytes of the batch a record store keeps go -- queued inside ms_select's interval --, or null.
+    // false: a check tripped (refuse_bad() / refuse_output() say which); a sink with an output stops the pass there.
+    bool run(const ViewBatch& vb, uint8_t* store_at, hipStream_t s) {
+        sbx_ctx* c = job.c.get();
+        const uint64_t nrec = vb.nrec, kept = vb.keep_hi - vb.keep_lo;
+        const uint32_t n_groups = view_groups(nrec);
+        memcpy(before, books.acc, sizeof before);
+        if (wants.counts) d_count.ensure((size_t)nrec + 2);
+        if (wants.groups) {
+            d_group_entries.ensure(n_groups + 4); d_group_records.ensure(n_groups + 4);
+            d_group_entry_base.ensure(n_groups + 4); d_group_record_base.ensure(n_groups + 4);
+        }
+        t_a.start(s);
+        // the batch's records go behind those of the batches before
+        if (store_at && kept) SBX_HIP(hipMemcpyAsync(store_at, c->U() + vb.keep_lo, kept, hipMemcpyDeviceToDevice, s));
+        a = ViewSelectArgs{};
+        a.U = c->U(); a.desc = c->d_desc.p; a.rec_ref = c->d_rec_ref.p; a.n = nrec; a.u_end = vb.u_end;
+        if (const sbx_view_opts* opts = job.q.opts) {
+            a.flags_set = opts->flags_set; a.flags_unset = opts->flags_unset;
+            a.subsample = opts->subsample ? 1u : 0u; a.seed = opts->seed; a.threshold = job.threshold;
+        }
+        a.regions = d_regions.p; a.n_regions = (uint32_t)job.sel.list.size(); a.regions_merged = job.sel.merged ? 1u : 0u;
+        a.acc = books.d_acc.p;
+        a.invalid = valid.run(c, nrec, vb.u_end, s);
+        a.with_lengths = wants.lengths ? 1u : 0u;
+        a.count = wants.counts ? d_count.p : nullptr;
+        if (wants.groups) { a.group_entries = d_group_entries.p; a.group_records = d_group_records.p; }
+        launch_view_select(a, s);
+        if (wants.groups && nrec) {
+            launch_count_scan(d_group_entries.p, n_groups, d_group_entry_base.p, s);
+            launch_count_scan(d_group_records.p, n_groups, d_group_record_base.p, s);
+        }
+        t_a.stop(s);
+        // (the next batch's K1 / K2 overwrite U and the descriptors, and may reallocate them: K12a and the copy end first)
+        books.read_back(c, nrec, s);
+        ms_select += t_a.ms();
+        too_many = too_many || books.acc[kViewAccEntries] > 0xFFFFFFF0ull;
+        return !books.acc[kViewAccBad] && !too_many;
+    }
+    void refuse_bad() const {
+        if (books.acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(books.acc[kViewAccBad]));
+    }
+    // for a sink with an output, behind refuse_bad(); one_entry_per_record: the output is in file order
+    void refuse_output(bool one_entry_per_record) const {
+        const unsigned long long n_ent = books.acc[kViewAccEntries], n_rec = books.acc[kViewAccRecords];
+        if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 output records");
+        if (one_entry_per_record && n_ent != n_rec)
+            throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_ent) + " entries for " + std::to_string(n_rec) + " records");
+    }
+    void fill(sbx_view_stats* st) const {
+        st->n_records_in = books.n; st->n_records_selected = books.acc[kViewAccRecords]; st->n_entries_out = books.acc[kViewAccEntries];
+        st->inflated_bytes = inflated;
+        st->n_regions = job.sel.given(); st->n_batches = n_batches;
+        st->ms_inflate = books.ms_inflate; st->ms_index = books.ms_index; st->ms_select = ms_select;
+    }
+};
+
 // ---- what the BAM and the SAM sink share: the read pass and the order of the entries ----
 // The records of the file in the resident store and the selected entries in output order: entry i is record perm[i], len[perm[i]]
 // bytes at store + off[perm[i]].
@@ -268,68 +395,36 @@ struct SelectedRecords {
     Stream stream;                  // what follows the read pass runs on it (declared last: it is waited for before the buffers go)
 };
 
-// Reads the file (K1, K2, K12a, K12b per batch; the records go to the store), closes the context and orders the entries (K9b over
-// the region index for listed regions).  hlen / per_record: bytes of the sink's header and of the per-record arrays it will add,
-// for the refusal of a file that does not fit.  Fills the counts and the times of the passes into *st.
-void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshold, const ViewRegions& sel, const IndexedRead& rd, bool valid_only,
-                     uint64_t hlen, uint64_t per_record, SelectedRecords* out, sbx_view_stats* st_out) {
+// Reads the file (K1, K2, K12a, K12b per batch; the records go to the store `plan` describes), closes the context and orders the
+// entries (K9b over the region index for listed regions).  Fills the counts and the times of the passes into *st.
+void select_resident(ViewJob& job, const StorePlan& plan, SelectedRecords* out, sbx_view_stats* st_out) {
     sbx_view_stats& st = *st_out;
+    const ViewRegions& sel = job.sel;
     const bool listed = !sel.merged && !sel.list.empty();
     DevBuf<uint8_t>& d_store = out->store;
     DevBuf<uint64_t>& d_off = out->off;
     DevBuf<uint32_t>& d_len = out->len;
     DevBuf<uint32_t>& d_perm = out->perm;
     Stream& stream = out->stream;
-    // the store holds the records of the file, or -- indexed -- the bytes of the runs
-    const StorePlan plan = rd.on ? plan_store_bytes(rd.store_bytes, hlen, per_record, "selecting records of", "the blocks the index names for the regions do")
-                                 : plan_record_store(c.get(), hlen, per_record, "selecting records of");
-    hipStream_t s = c->stream.get();
+    hipStream_t s = job.c->stream.get();
     d_store = DevBuf<uint8_t>((size_t)plan.store_bytes + 64);
-    DevBuf<sbx_region> d_regions;
-    upload_regions(sel, &d_regions, s);
-    DevBuf<uint64_t> d_entry_key, d_group_entry_base, d_group_record_base;
-    DevBuf<uint32_t> d_entry_rec, d_count, d_group_entries, d_group_records;
-    DevBuf<unsigned long long> d_acc(kViewAccWords);
-    SBX_HIP(hipMemsetAsync(d_acc.p, 0, kViewAccWords * sizeof(unsigned long long), s));
-    SBX_HIP(hipStreamSynchronize(s));
-    ValidPass valid;
-    valid.init(valid_only, s);
+    SelectStep pick(job, SelectWants{true, true, true}, s);
+    const unsigned long long* acc = pick.books.acc;
+    DevBuf<uint64_t> d_entry_key;
+    DevBuf<uint32_t> d_entry_rec;
 
     // ---- the read pass ----
-    EventTimer t_a, t_b;
-    uint64_t n_in = 0, n_rec = 0, n_ent = 0, store_at = 0, inflated = 0;
-    uint32_t n_batches = 0;
-    bool too_many = false;
-    unsigned long long acc[kViewAccWords] = {0};
-    read_batches(c.get(), rd, plan.batch_u, &n_batches, &inflated, [&](const ViewBatch& vb) -> bool {
-        const uint64_t nrec = vb.nrec, kept = vb.keep_hi - vb.keep_lo;
-        const uint32_t groups = view_groups(nrec);
+    EventTimer t_b;
+    uint64_t store_at = 0;
+    read_batches(job.c.get(), job.rd, plan.batch_u, &pick.n_batches, &pick.inflated, [&](const ViewBatch& vb) -> bool {
+        const uint64_t kept = vb.keep_hi - vb.keep_lo;
         if (store_at + kept > plan.store_bytes) throw Error(SBX_EFORMAT, "internal error: the batches hold more bytes than the record store was planned for");
-        d_count.ensure((size_t)nrec + 2);
-        d_group_entries.ensure(groups + 4); d_group_records.ensure(groups + 4);
-        d_group_entry_base.ensure(groups + 4); d_group_record_base.ensure(groups + 4);
-        t_a.start(s);
-        // the batch's records go behind those of the batches before
-        if (kept) SBX_HIP(hipMemcpyAsync(d_store.p + store_at, c->U() + vb.keep_lo, kept, hipMemcpyDeviceToDevice, s));
-        const uint16_t* d_invalid = valid.run(c.get(), nrec, vb.u_end, s);
-        ViewSelectArgs a = select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, vb.u_end, d_acc.p, d_invalid);
-        a.with_lengths = 1;
-        a.count = d_count.p; a.group_entries = d_group_entries.p; a.group_records = d_group_records.p;
-        launch_view_select(a, s);
-        if (nrec) {
-            launch_count_scan(d_group_entries.p, groups, d_group_entry_base.p, s);
-            launch_count_scan(d_group_records.p, groups, d_group_record_base.p, s);
-        }
-        t_a.stop(s);
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index; st.ms_select += t_a.ms();
-        n_in += nrec;
+        const bool go_on = pick.run(vb, d_store.p + store_at, s);
         const int64_t store_delta = (int64_t)store_at - (int64_t)vb.keep_lo;
         store_at += kept;
-        if (acc[kViewAccBad]) return false;
-        if (acc[kViewAccEntries] > 0xFFFFFFF0ull) { too_many = true; return false; }
+        if (!go_on) return false;
         // the arrays grow to what the batch selected, then K12b fills them
+        const uint64_t n_rec = pick.before[kViewAccRecords], n_ent = pick.before[kViewAccEntries];
         grow_keeping(d_off, (size_t)n_rec, (size_t)acc[kViewAccRecords] + 2, s);
         grow_keeping(d_len, (size_t)n_rec, (size_t)acc[kViewAccRecords] + 2, s);
         if (listed) {
@@ -337,8 +432,8 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
             grow_keeping(d_entry_rec, (size_t)n_ent, (size_t)acc[kViewAccEntries] + 2, s);
         }
         ViewEmitArgs b{};
-        b.s = a;
-        b.group_entry_base = d_group_entry_base.p; b.group_record_base = d_group_record_base.p;
+        b.s = pick.a;
+        b.group_entry_base = pick.d_group_entry_base.p; b.group_record_base = pick.d_group_record_base.p;
         b.store_delta = store_delta;
         b.record_base = n_rec; b.entry_base = n_ent;
         b.off = d_off.p; b.len = d_len.p;
@@ -346,18 +441,17 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
         t_b.start(s);
         launch_view_emit(b, s);
         t_b.stop(s);
-        // (the next batch's K1 / K2 overwrite U and the descriptors: K12b and the copy end first)
+        // (the next batch's K1 / K2 overwrite U and the descriptors: K12b ends first)
         SBX_HIP(hipStreamSynchronize(s));
-        if (nrec) st.ms_emit += t_b.ms();
-        n_rec = acc[kViewAccRecords];
-        n_ent = acc[kViewAccEntries];
+        if (vb.nrec) st.ms_emit += t_b.ms();
         return true;
     });
-    if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
-    if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 output records");
-    if (!listed && n_ent != n_rec) throw Error(SBX_EFORMAT, "internal error: " + std::to_string(n_ent) + " entries for " + std::to_string(n_rec) + " records");
-    c.reset();                                       // the batch buffers make room for the sort and the output pieces
-    d_count.release(); d_group_entries.release(); d_group_records.release(); d_group_entry_base.release(); d_group_record_base.release();
+    pick.refuse_bad();
+    pick.refuse_output(!listed);
+    const uint64_t n_ent = acc[kViewAccEntries];
+    job.c.reset();                                   // the batch buffers make room for the sort and the output pieces
+    pick.d_count.release(); pick.d_group_entries.release(); pick.d_group_records.release();
+    pick.d_group_entry_base.release(); pick.d_group_record_base.release();
 
     // ---- the order of the entries ----
     stream.create();
@@ -388,95 +482,10 @@ void select_resident(Standalone& c, const sbx_view_opts* opts, uint64_t threshol
     d_off.ensure(2);
     out->n = n;
     out->record_bytes = acc[kViewAccBytes];
-    st.n_records_in = n_in; st.n_records_selected = n_rec; st.n_entries_out = n;
-    st.inflated_bytes = inflated;
-    st.n_regions = sel.given(); st.n_batches = n_batches;
+    pick.fill(&st);
 }
 
 // ---- the streamed BAM sink: no store; K12a per batch, then K21 into the staging window (engine_streamout.hpp) ----
-// The output order is the file order when no region orders it: no region, one listed region, or the merged list of a BED file.
-bool in_file_order(const ViewRegions& sel) { return sel.merged || sel.list.size() <= 1; }
-
-// does the resident store of select_resident fit?  (its refusal is SBX_ENOMEM; anything else is passed on)
-bool resident_store_fits(sbx_ctx* c, const IndexedRead& rd, uint64_t hlen, uint64_t per_record) {
-    try {
-        if (rd.on) plan_store_bytes(rd.store_bytes, hlen, per_record, "selecting records of", "the blocks the index names for the regions do");
-        else plan_record_store(c, hlen, per_record, "selecting records of");
-    } catch (const Error& e) {
-        if (e.code != SBX_ENOMEM) throw;
-        return false;
-    }
-    return true;
-}
-
-// What the two streamed sinks share: per batch K19 and K12a (for the SAM sink with the group sums and their scans, which K12b
-// needs), the accumulators read back, the checks the resident path makes, raised when the batch that trips them is met; at the end
-// the errors and the counts of the stats.
-struct StreamedSelect {
-    const sbx_view_opts* opts;
-    uint64_t threshold;
-    const ViewRegions& sel;
-    bool groups;
-    DevBuf<sbx_region> d_regions;
-    DevBuf<uint32_t> d_count, d_group_entries, d_group_records;
-    DevBuf<uint64_t> d_group_entry_base, d_group_record_base;
-    DevBuf<unsigned long long> d_acc;
-    ValidPass valid;
-    EventTimer t_a;
-    unsigned long long acc[kViewAccWords] = {0}, before[kViewAccWords] = {0};       // after / in front of the last batch
-    uint64_t n_in = 0, inflated = 0;
-    uint32_t n_batches = 0;
-    bool too_many = false;
-    ViewSelectArgs a{};                                 // K12a's arguments for the last batch
-
-    StreamedSelect(const sbx_view_opts* o, uint64_t thr, const ViewRegions& regions, bool valid_only, bool with_groups, hipStream_t s)
-        : opts(o), threshold(thr), sel(regions), groups(with_groups), d_acc(kViewAccWords) {
-        upload_regions(sel, &d_regions, s);
-        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kViewAccWords * sizeof(unsigned long long), s));
-        SBX_HIP(hipStreamSynchronize(s));
-        valid.init(valid_only, s);
-    }
-    // false: the pass stops here (finish() says why)
-    bool run(sbx_ctx* c, const ViewBatch& vb, hipStream_t s, sbx_view_stats* st) {
-        const uint64_t nrec = vb.nrec;
-        const uint32_t n_groups = view_groups(nrec);
-        memcpy(before, acc, sizeof acc);
-        d_count.ensure((size_t)nrec + 2);
-        if (groups) {
-            d_group_entries.ensure(n_groups + 4); d_group_records.ensure(n_groups + 4);
-            d_group_entry_base.ensure(n_groups + 4); d_group_record_base.ensure(n_groups + 4);
-        }
-        t_a.start(s);
-        const uint16_t* d_invalid = valid.run(c, nrec, vb.u_end, s);
-        a = select_args(c, opts, threshold, sel, d_regions.p, nrec, vb.u_end, d_acc.p, d_invalid);
-        a.with_lengths = 1;
-        a.count = d_count.p;
-        if (groups) { a.group_entries = d_group_entries.p; a.group_records = d_group_records.p; }
-        launch_view_select(a, s);
-        if (groups && nrec) {
-            launch_count_scan(d_group_entries.p, n_groups, d_group_entry_base.p, s);
-            launch_count_scan(d_group_records.p, n_groups, d_group_record_base.p, s);
-        }
-        t_a.stop(s);
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        st->ms_inflate += c->stats.ms_inflate; st->ms_index += c->stats.ms_index; st->ms_select += t_a.ms();
-        n_in += nrec;
-        if (acc[kViewAccBad]) return false;
-        if (acc[kViewAccEntries] > 0xFFFFFFF0ull) { too_many = true; return false; }
-        return true;
-    }
-    void finish(sbx_view_stats* st) const {
-        if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
-        if (too_many) throw Error(SBX_EUNSUPPORTED, "more than 2^32 output records");
-        if (acc[kViewAccEntries] != acc[kViewAccRecords])
-            throw Error(SBX_EFORMAT, "internal error: " + std::to_string(acc[kViewAccEntries]) + " entries for " + std::to_string(acc[kViewAccRecords]) + " records");
-        st->n_records_in = n_in; st->n_records_selected = acc[kViewAccRecords]; st->n_entries_out = acc[kViewAccEntries];
-        st->inflated_bytes = inflated;
-        st->n_regions = sel.given(); st->n_batches = n_batches;
-    }
-};
-
 // no more record bytes than this reach the output of a pass
 uint64_t record_bytes_max(const sbx_ctx* c, const IndexedRead& rd) {
     const uint64_t u_total = c->blocks.out_off.back(), u_first = std::min<uint64_t>(c->hdr.first_record_off, u_total);
@@ -484,24 +493,25 @@ uint64_t record_bytes_max(const sbx_ctx* c, const IndexedRead& rd) {
 }
 const char* iview_hint(const IndexedRead& rd) { return rd.on ? "" : "; sbx-iview reads only the blocks the index names for a region"; }
 
-void view_bam_streamed(Standalone& c, OutputGuard& out_file, const std::vector<uint8_t>& header, const sbx_view_opts* opts, uint64_t threshold,
-                       const ViewRegions& sel, const IndexedRead& rd, bool valid_only, uint64_t hook, int level, sbx_view_stats* st,
-                       sbx_stream_stats* stream_stats) {
-    const uint64_t stream_max = header.size() + record_bytes_max(c.get(), rd);
-    const StreamBudget budget(stream_max, hook, 18, "selecting records of", "18 bytes per record of it", iview_hint(rd));
+void view_bam_streamed(ViewJob& job, const std::vector<uint8_t>& header, uint64_t hook, sbx_view_stats* st, sbx_stream_stats* stream_stats) {
+    sbx_ctx* c = job.c.get();
+    const uint64_t stream_max = header.size() + record_bytes_max(c, job.rd);
+    const StreamBudget budget(stream_max, hook, 18, "selecting records of", "18 bytes per record of it", iview_hint(job.rd));
     hipStream_t s = c->stream.get();
-    StreamedOutput out(out_file, header, stream_max, budget, level, s);
-    StreamedSelect pick(opts, threshold, sel, valid_only, false, s);
-    read_batches(c.get(), rd, budget.batch_u, &pick.n_batches, &pick.inflated, [&](const ViewBatch& vb) -> bool {
-        if (!pick.run(c.get(), vb, s, st)) return false;
+    StreamedOutput out(job.out_file, header, stream_max, budget, job.q.level, s);
+    SelectStep pick(job, SelectWants{true, true, false}, s);
+    read_batches(c, job.rd, budget.batch_u, &pick.n_batches, &pick.inflated, [&](const ViewBatch& vb) -> bool {
+        if (!pick.run(vb, nullptr, s)) return false;
         PackArgs p{};
         p.U = c->U(); p.desc = c->d_desc.p; p.n = vb.nrec; p.u_end = vb.u_end;
         p.count = pick.d_count.p;
         // (the next batch's K1 / K2 overwrite U and the descriptors: add_batch returns when K21 has read them)
-        out.add_batch(p, pick.acc[kViewAccBytes] - pick.before[kViewAccBytes]);
+        out.add_batch(p, pick.books.acc[kViewAccBytes] - pick.before[kViewAccBytes]);
         return true;
     });
-    pick.finish(st);
+    pick.refuse_bad();
+    pick.refuse_output(true);
+    pick.fill(st);
     out.finish();
     st->stream_bytes = out.stream_bytes(); st->compressed_bytes = out.compressed_bytes();
     st->ms_deflate = out.ms_deflate();
@@ -607,25 +617,25 @@ struct SamText {
 
 
 // ---- the streamed SAM sink: no store and no new kernel; per batch K12a, K12b with offsets into U, K13a, the offsets, K13b ----
-void view_sam_streamed(Standalone& c, OutputGuard& out_file, const std::string& text, const sbx_view_opts* opts, uint64_t threshold,
-                       const ViewRegions& sel, const IndexedRead& rd, bool valid_only, sbx_view_stats* st, sbx_stream_stats* stream_stats) {
+void view_sam_streamed(ViewJob& job, sbx_view_stats* st, sbx_stream_stats* stream_stats) {
+    sbx_ctx* c = job.c.get();
     SamText sam;
     // next to a batch: 34 bytes per record of it (count, off, len, perm, line length and offset, the mask of -v) and the two device
     // pieces of the text -- no encoder and no window
-    const uint64_t pieces = 2 * std::min<uint64_t>(sam.budget, 4 * record_bytes_max(c.get(), rd) + (1ull << 20)) + (8ull << 20);
-    const StreamBudget budget(pieces, 34, "selecting records of", "34 bytes per record of it and two pieces of text", iview_hint(rd));
+    const uint64_t pieces = 2 * std::min<uint64_t>(sam.budget, 4 * record_bytes_max(c, job.rd) + (1ull << 20)) + (8ull << 20);
+    const StreamBudget budget(pieces, 34, "selecting records of", "34 bytes per record of it and two pieces of text", iview_hint(job.rd));
     hipStream_t s = c->stream.get();
     DeviceRefNames names;
     upload_ref_names(c->hdr.refs, s, &names);
-    StreamedSelect pick(opts, threshold, sel, valid_only, true, s);
+    SelectStep pick(job, SelectWants{true, true, true}, s);
     DevBuf<uint64_t> d_off;
     DevBuf<uint32_t> d_len, d_perm;
-    OutputFile f(out_file);                             // `out_file` is armed from here to the end
-    f.write(text.data(), text.size());
+    OutputFile f(job.out_file);                         // the output is armed from here to the end
+    f.write(job.text.data(), job.text.size());
     EventTimer t_b;
-    read_batches(c.get(), rd, budget.batch_u, &pick.n_batches, &pick.inflated, [&](const ViewBatch& vb) -> bool {
-        if (!pick.run(c.get(), vb, s, st)) return false;
-        const uint64_t n_sel = pick.acc[kViewAccRecords] - pick.before[kViewAccRecords];
+    read_batches(c, job.rd, budget.batch_u, &pick.n_batches, &pick.inflated, [&](const ViewBatch& vb) -> bool {
+        if (!pick.run(vb, nullptr, s)) return false;
+        const uint64_t n_sel = pick.books.acc[kViewAccRecords] - pick.before[kViewAccRecords];
         if (!n_sel) return true;
         // K12b with batch-local ordinals and offsets of U: the batch is the store
         d_off.ensure((size_t)n_sel + 2); d_len.ensure((size_t)n_sel + 2); d_perm.ensure((size_t)n_sel + 2);
@@ -646,7 +656,9 @@ void view_sam_streamed(Standalone& c, OutputGuard& out_file, const std::string& 
         sam.emit(e, s, f);
         return true;
     });
-    pick.finish(st);
+    pick.refuse_bad();
+    pick.refuse_output(true);
+    pick.fill(st);
     f.finish(false);
     st->stream_bytes = sam.text_bytes;
     st->ms_gather = sam.ms;
@@ -683,162 +695,97 @@ int sbx_view_reference_info(sbx_ctx* c, char* out, size_t cap, size_t* out_len) 
 
 namespace {
 
-// ---- the three sinks: the bodies behind sbx_view_run ----
-int view_count(const char* in_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions, size_t n_regions,
-               const char* bed_path, int device, int valid_only, int index_mode, sbx_view_index_stats* ix, uint64_t* count, sbx_view_stats* stats,
-               char* err, size_t errlen) {
+// ---- the three sinks: the bodies behind sbx_view_run.  q: the validated request ----
+int view_count(const sbx_view_request& q, int index_mode, sbx_view_index_stats* ix, uint64_t* count, sbx_view_stats* stats, char* err,
+               size_t errlen) {
     return run_entry(err, errlen, [&] {
-        if (!in_path || !count) throw Error(SBX_EINVAL, "null argument");
-        uint64_t threshold = 0;
-        check_opts(filter, opts, &threshold);
-        const double w0 = wall_now();
-        Standalone c = open_record_pass(in_path, device, filter, true);
-        const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
-        const IndexedRead rd = plan_indexed_read(c.get(), in_path, sel, index_mode, ix);
-        hipStream_t s = c->stream.get();
-        DevBuf<sbx_region> d_regions;
-        upload_regions(sel, &d_regions, s);
-        DevBuf<unsigned long long> d_acc(kViewAccWords);
-        SBX_HIP(hipMemsetAsync(d_acc.p, 0, kViewAccWords * sizeof(unsigned long long), s));
-        sbx_view_stats st{};
-        ValidPass valid;
-        valid.init(valid_only != 0, s);
-        EventTimer t_k;
-        uint64_t n_in = 0, inflated = 0;
-        uint32_t n_batches = 0;
-        read_batches(c.get(), rd, index_batch_bytes(), &n_batches, &inflated, [&](const ViewBatch& vb) -> bool {
-            const uint64_t nrec = vb.nrec;
-            t_k.start(s);
-            const uint16_t* d_invalid = valid.run(c.get(), nrec, vb.u_end, s);
-            launch_view_select(select_args(c.get(), opts, threshold, sel, d_regions.p, nrec, vb.u_end, d_acc.p, d_invalid), s);
-            t_k.stop(s);
-            // (the next batch's K2 overwrites these descriptors, and may reallocate them, from the host side: K12a ends first)
-            SBX_HIP(hipStreamSynchronize(s));
-            st.ms_inflate += c->stats.ms_inflate; st.ms_index += c->stats.ms_index;
-            if (nrec) st.ms_select += t_k.ms();
-            n_in += nrec;
-            return true;
+        if (!q.in_path || !count) throw Error(SBX_EINVAL, "null argument");
+        ViewJob job(q);
+        job.open(index_mode, false, ix);
+        hipStream_t s = job.c->stream.get();
+        SelectStep pick(job, SelectWants{false, false, false}, s);
+        read_batches(job.c.get(), job.rd, index_batch_bytes(), &pick.n_batches, &pick.inflated, [&](const ViewBatch& vb) -> bool {
+            pick.run(vb, nullptr, s);
+            return true;                // (nothing is written: the pass goes on, and the refusal counts the bad records of the whole file)
         });
-        unsigned long long acc[kViewAccWords] = {0};
-        SBX_HIP(hipMemcpyAsync(acc, d_acc.p, sizeof acc, hipMemcpyDeviceToHost, s));
-        SBX_HIP(hipStreamSynchronize(s));
-        if (acc[kViewAccBad]) throw Error(SBX_EFORMAT, malformed_records_message(acc[kViewAccBad]));
-        st.n_records_in = n_in; st.n_records_selected = acc[kViewAccRecords]; st.n_entries_out = acc[kViewAccEntries];
-        st.inflated_bytes = inflated;
-        st.n_regions = sel.given(); st.n_batches = n_batches;
-        st.ms_total_wall = (wall_now() - w0) * 1e3;
-        print_timing(st, "count");
-        *count = acc[kViewAccEntries];
-        if (stats) *stats = st;
+        pick.refuse_bad();
+        sbx_view_stats st{};
+        pick.fill(&st);
+        *count = st.n_entries_out;
+        job.finish(st, "count", stats);
     });
 }
 
-int view_bam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
-             size_t n_regions, const char* bed_path, const char* pg_command_line, int level, int with_index, int device, int valid_only,
-             int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, sbx_stream_stats* stream_stats, char* err, size_t errlen) {
-    const bool to_stdout = !out_path || !strcmp(out_path, "-");
-    const char* const path = to_stdout ? "/dev/stdout" : out_path;
+int view_bam(const sbx_view_request& q, int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, sbx_stream_stats* stream_stats,
+             char* err, size_t errlen) {
     const int rc = run_entry(err, errlen, [&] {
-        if (!in_path) throw Error(SBX_EINVAL, "null argument");
-        check_level(level);
-        if (to_stdout && with_index) throw Error(SBX_EINVAL, "an output on stdout cannot be indexed");
-        if (!to_stdout) refuse_overwrite(in_path, path);
-        uint64_t threshold = 0;
-        check_opts(filter, opts, &threshold);
-        const double w0 = wall_now();
-        Standalone c = open_record_pass(in_path, device, filter, true);
-        OutputGuard out_file(path, to_stdout);
-        const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
-        const IndexedRead rd = plan_indexed_read(c.get(), in_path, sel, index_mode, ix);
-        std::string text, why;
-        if (!mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why)) throw Error(SBX_EFORMAT, "SAM header: " + why);
-        const std::vector<uint8_t> header = bam_header_bytes(text, c->hdr.refs);
-        const uint64_t hlen = header.size();
-
+        if (!q.in_path) throw Error(SBX_EINVAL, "null argument");
+        ViewJob job(q);
+        check_level(q.level);
+        if (job.to_stdout && q.with_index) throw Error(SBX_EINVAL, "an output on stdout cannot be indexed");
+        if (!job.to_stdout) refuse_overwrite(q.in_path, job.path);
+        job.open(index_mode, true, ix);
+        const std::vector<uint8_t> header = bam_header_bytes(job.text, job.c->hdr.refs);
         sbx_view_stats st{};
-        // in file order: the stream when the hook asks for it or the store does not fit (two or more listed regions: the store, and its refusal)
         const uint64_t hook = stream_window_hook();
-        if (in_file_order(sel) && (hook || !resident_store_fits(c.get(), rd, hlen, 48))) {
-            view_bam_streamed(c, out_file, header, opts, threshold, sel, rd, valid_only != 0, hook, level, &st, stream_stats);
-            out_file.disarm();
-            st.ms_total_wall = (wall_now() - w0) * 1e3;
-            print_timing(st, "bam");
-            if (stats) *stats = st;
+        const std::optional<StorePlan> fits = job.plan_store(header.size(), 48, hook);
+        if (!fits) {
+            view_bam_streamed(job, header, hook, &st, stream_stats);
+            job.out_file.disarm();
+            job.finish(st, "bam", stats);
             return;
         }
         SelectedRecords r;
-        select_resident(c, opts, threshold, sel, rd, valid_only != 0, hlen, 48, &r, &st);
-        const uint64_t n = r.n;
-        hipStream_t s = r.stream.get();
-        DevBuf<uint64_t> d_out_off((size_t)n + 2);
-        const WrittenBam w = write_store_output(out_file, header, r.store.p, r.off.p, r.len, r.perm.p, n, d_out_off.p, level,
-                                                &r.record_bytes, "selected records", s, &st.ms_gather);
-        out_file.disarm();
+        select_resident(job, *fits, &r, &st);
+        DevBuf<uint64_t> d_out_off((size_t)r.n + 2);
+        const WrittenBam w = write_store_output(job.out_file, header, r.store.p, r.off.p, r.len, r.perm.p, r.n, d_out_off.p, q.level,
+                                                &r.record_bytes, "selected records", r.stream.get(), &st.ms_gather);
+        job.out_file.disarm();
         st.stream_bytes = w.stream_bytes; st.compressed_bytes = w.compressed_bytes;
         st.ms_deflate = w.ms_deflate;
-        st.ms_total_wall = (wall_now() - w0) * 1e3;
-        print_timing(st, "bam");
-        if (stats) *stats = st;
+        job.finish(st, "bam", stats);
     });
     // (the index is a pass of its own and not part of the figures)
-    return rc != SBX_OK ? rc : index_written_bam(path, with_index, device, err, errlen);
+    return rc != SBX_OK ? rc : index_written_bam(ViewJob::path_of(q), q.with_index, q.device, err, errlen);
 }
 
-int view_sam(const char* in_path, const char* out_path, const sbx_filter* filter, const sbx_view_opts* opts, const char* const* regions,
-             size_t n_regions, const char* bed_path, const char* pg_command_line, int with_header, int device, int valid_only,
-             int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, sbx_stream_stats* stream_stats, char* err, size_t errlen) {
-    const bool to_stdout = !out_path || !strcmp(out_path, "-");
-    const char* const path = to_stdout ? "/dev/stdout" : out_path;
+int view_sam(const sbx_view_request& q, int index_mode, sbx_view_index_stats* ix, sbx_view_stats* stats, sbx_stream_stats* stream_stats,
+             char* err, size_t errlen) {
     return run_entry(err, errlen, [&] {
-        if (!in_path) throw Error(SBX_EINVAL, "null argument");
-        if (!to_stdout) refuse_overwrite(in_path, path);
-        uint64_t threshold = 0;
-        check_opts(filter, opts, &threshold);
-        const double w0 = wall_now();
-        Standalone c = open_record_pass(in_path, device, filter, true);
-        OutputGuard out_file(path, to_stdout);
-        const ViewRegions sel = resolve_regions(c.get(), regions, n_regions, bed_path);
-        const IndexedRead rd = plan_indexed_read(c.get(), in_path, sel, index_mode, ix);
-        std::string text, why;
-        if (with_header && !mdc::markdup_header_text(c->hdr.text.data(), c->hdr.text.size(), pg_command_line, &text, &why))
-            throw Error(SBX_EFORMAT, "SAM header: " + why);
-        const std::vector<RefSeq> refs = c->hdr.refs;       // (select_resident lets go of the context)
+        if (!q.in_path) throw Error(SBX_EINVAL, "null argument");
+        ViewJob job(q);
+        if (!job.to_stdout) refuse_overwrite(q.in_path, job.path);
+        job.open(index_mode, q.with_header != 0, ix);
         sbx_view_stats st{};
-        // in file order: the stream when the hook asks for it or the store does not fit (two or more listed regions: the store, and its refusal)
-        if (in_file_order(sel) && (stream_window_hook() || !resident_store_fits(c.get(), rd, text.size(), 48 + 12))) {
-            view_sam_streamed(c, out_file, text, opts, threshold, sel, rd, valid_only != 0, &st, stream_stats);
-            out_file.disarm();
-            st.ms_total_wall = (wall_now() - w0) * 1e3;
-            print_timing(st, "sam");
-            if (stats) *stats = st;
+        const std::optional<StorePlan> fits = job.plan_store(job.text.size(), 48 + 12, stream_window_hook());      // (+ length and offset of every line)
+        if (!fits) {
+            view_sam_streamed(job, &st, stream_stats);
+            job.out_file.disarm();
+            job.finish(st, "sam", stats);
             return;
         }
+        const std::vector<RefSeq> refs = job.c->hdr.refs;   // (select_resident lets go of the context)
         SelectedRecords r;
-        select_resident(c, opts, threshold, sel, rd, valid_only != 0, text.size(), 48 + 12, &r, &st);       // (+ length and offset of every line)
-        const uint64_t n = r.n;
+        select_resident(job, *fits, &r, &st);
         hipStream_t s = r.stream.get();
         DeviceRefNames names;
         upload_ref_names(refs, s, &names);
-        const SamEntries e{r.store.p, r.off.p, r.len.p, r.perm.p, n, samc::RefNames{names.off.p, names.bytes.p, names.n()}};
+        const SamEntries e{r.store.p, r.off.p, r.len.p, r.perm.p, r.n, samc::RefNames{names.off.p, names.bytes.p, names.n()}};
 
         // ---- K13a over all entries; then K13b piece by piece into the file, the header first ----
         SamText sam;
         sam.measure(e, s);                              // (a malformed selected record: SBX_EFORMAT before a byte is written)
-        OutputFile f(out_file);
-        f.write(text.data(), text.size());
+        OutputFile f(job.out_file);
+        f.write(job.text.data(), job.text.size());
         sam.emit(e, s, f);
         st.ms_gather += sam.ms;
-        const uint32_t n_pieces = sam.n_pieces;
-        const uint64_t budget = sam.budget;
         f.finish(false);
-        out_file.disarm();
+        job.out_file.disarm();
         st.stream_bytes = sam.text_bytes;
-        st.ms_total_wall = (wall_now() - w0) * 1e3;
-        print_timing(st, "sam");
+        job.finish(st, "sam", stats);
         if (getenv("SBX_TIMING"))
-            fprintf(stderr, "[sbx] output: text_bytes=%llu n_pieces=%u piece_bytes=%llu\n", (unsigned long long)st.stream_bytes, n_pieces,
-                    (unsigned long long)budget);
-        if (stats) *stats = st;
+            fprintf(stderr, "[sbx] output: text_bytes=%llu n_pieces=%u piece_bytes=%llu\n", (unsigned long long)st.stream_bytes, sam.n_pieces,
+                    (unsigned long long)sam.budget);
     });
 }
 
@@ -870,14 +817,9 @@ int sbx_view_run_streamed(const sbx_view_request* request, int index_mode, uint6
             throw Error(SBX_EINVAL, "sbx_view_request: unknown sink " + std::to_string(q.sink));
     });
     if (rc != SBX_OK) return rc;
-    if (q.sink == SBX_VIEW_SINK_COUNT)
-        return view_count(q.in_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.device, q.valid_only, index_mode, ix, count, stats, err,
-                          errlen);
-    if (q.sink == SBX_VIEW_SINK_BAM)
-        return view_bam(q.in_path, q.out_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.pg_command_line, q.level, q.with_index,
-                        q.device, q.valid_only, index_mode, ix, stats, stream_stats, err, errlen);
-    return view_sam(q.in_path, q.out_path, q.filter, q.opts, q.regions, q.n_regions, q.bed_path, q.pg_command_line, q.with_header, q.device,
-                    q.valid_only, index_mode, ix, stats, stream_stats, err, errlen);
+    if (q.sink == SBX_VIEW_SINK_COUNT) return view_count(q, index_mode, ix, count, stats, err, errlen);
+    if (q.sink == SBX_VIEW_SINK_BAM) return view_bam(q, index_mode, ix, stats, stream_stats, err, errlen);
+    return view_sam(q, index_mode, ix, stats, stream_stats, err, errlen);
 }
 
 int sbx_view_run_indexed(const sbx_view_request* request, int index_mode, uint64_t* count, sbx_view_stats* stats, sbx_view_index_stats* ix,
