@@ -955,12 +955,22 @@ __device__ __forceinline__ void wave_copy(uint8_t* d, const uint8_t* s, uint32_t
 // copied -- instead of a second Short16 step: 3.16 -> 3.05 ms at 40 Mbp, profiles/round6/call_j_k1b_tail16_40Mbp.jsonl; false: the A/B partner)
 // (kCarry: phase C writes aligned 16-byte groups and carries the < 16 bytes behind the last one into the next batch -- round 7,
 // profiles/round7/README.md; false: the write-out of rounds 1-6, the A/B partner and what kAblate 128 / 256 take apart)
-template <uint32_t kHist, uint32_t kSpanMax, bool kOwn32, bool kExact, uint32_t kAblate = 0, bool kTail16 = true, bool kCarry = true>
+// (kAblate, round 8 -- phase B taken apart: 512 no searches, the frontier rule instead (valid bytes); 1024 / 2048 / 4096 / 8192 a round without
+// its cooperative copy / permute path / byte-loop periodic path / long periodic loop)
+// (kGuard: ONE wave-uniform test around the four rare paths of a round -- cooperative copy, byte permutes, byte loop, doubling loop; three
+// rounds in four of a BAM stream have no taker for any of them (tools/token_stats.cpp) and each path paid its own ballot or branch:
+// 16.87 -> 16.51 ms in the lab, profiles/round8/README.md; false: the A/B partner)
+// (kFast: the one-round fast path -- when every pending lane passes the frontier test, lz::frontier_blocked, the range store, the two
+// searches and the mask are skipped and one round finishes the batch.  Same bytes; 0.2 % of the batches of a BAM stream qualify and the
+// test costs every batch a ballot: 16.87 -> 17.10 ms, profiles/round8/README.md.  Off; kept as the A/B partner the tests describe.)
+template <uint32_t kHist, uint32_t kSpanMax, bool kOwn32, bool kExactArg, uint32_t kAblate = 0, bool kTail16 = true, bool kCarry = true,
+          bool kGuard = true, bool kFast = false>
 __device__ __forceinline__ void lz77_resolve_body(
     const uint8_t* __restrict__ lit_stream, const uint32_t* __restrict__ ent_stream, const uint32_t* __restrict__ n_entries,
     const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ isize, uint32_t n_blocks, uint32_t block0,
     uint8_t* out, const uint32_t* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    constexpr bool kExact = kExactArg && !(kAblate & 512u);
     // (measured, profiles/round3: fewer instructions do not make this kernel faster -- telling the compiler that the wave index is
     // uniform (readfirstlane: the block's state and the batch loop in scalar registers, 879 -> 791 vector instructions) costs 6 %,
     // copy offsets as min(4 k, n - 4) instead of compare + select (772 instructions, 15 instead of 73 s_nop) cost 3.5 %, per-batch
@@ -1069,7 +1079,15 @@ __device__ __forceinline__ void lz77_resolve_body(
         // instructions -22 %, vector instructions -4 % (a round is ~25 vector and ~55 scalar instructions; the two searches cost 36 vector
         // instructions per batch), kernel time -2.5 % (22.2 -> 21.7 ms on config 2): the kernel follows its VECTOR instruction count.
         uint32_t dep_lo = 0, dep_hi = 0;
-        if (kExact) {
+        bool searches = kExact;
+        if (kExact && kFast) {
+            // one ballot: does any pending lane fail the frontier test?  (wave-uniform: a scalar branch.)  No pending lane at all: the
+            // same answer, and the loop of rounds below does not run either.
+            const uint64_t pm0 = __ballot(pending);
+            const uint32_t F = __builtin_amdgcn_readlane(dst, pm0 ? __builtin_ctzll(pm0) : 0);
+            searches = __ballot(lz::frontier_blocked(pending, s_hi, F)) != 0;      // false: dep_lo = dep_hi = 0, every pending lane is ready in round 1
+        }
+        if (searches) {
             uint32_t* rng = (uint32_t*)(smem + (kResThreads / 64) * kWaveLds + 128u) + wv * 64u;
             // (a lane without a match: start = end = where its match would be -- the arrays stay monotone, the lane is never pending)
             rng[lane] = dsto | ((dsto + len) << 16);
@@ -1112,13 +1130,15 @@ __device__ __forceinline__ void lz77_resolve_body(
                     __builtin_memcpy(&ts, buf + srco + own_s - 16u, 16);
                     __builtin_memcpy(buf + dsto + own_s - 16u, &ts, 16);
                 }
-                coop_copy(__ballot(plain && len > kOwn), buf, srco, buf, dsto, len, lane);
             }
+            // (kGuard: the four paths below have a taker in one round in four of a BAM stream)
+            if (kGuard && !__any(ready && (dist < len || len > (kOwn32 ? 32u : 16u)))) continue;
+            if (!(kAblate & 1024u)) coop_copy(__ballot(plain && len > (kOwn32 ? 32u : 16u)), buf, srco, buf, dsto, len, lane);
             // self-overlapping matches: byte k is src[k mod dist].  Short ones in their own lane (all
             // loads first: the bytes read lie in [src, dst)), long ones by doubling: the period, then
             // 1, 2, 4 ... periods copied from the match's own output.
             const bool per = ready && dist < len;
-            const bool per_perm = kOwn32 && per && len <= 16 && dist <= 8;
+            const bool perm_ok = kOwn32 && per && len <= 16 && dist <= 8, per_perm = perm_ok && !(kAblate & 2048u);
             if (kOwn32 && __any(per_perm)) {
                 // output byte k = period[k mod dist]: the period sits in the first (<= 8) bytes at src, output dword j is one byte
                 // permute of them; the tail words are cut out of neighbouring dwords
@@ -1132,7 +1152,7 @@ __device__ __forceinline__ void lz77_resolve_body(
                 }
                 ws.store(buf + dsto, n_p);
             }
-            if (per && len <= 16 && !per_perm) {
+            if (!(kAblate & 4096u) && per && len <= 16 && !perm_ok) {
                 uint32_t lo = 0, hi = 0, m = 0;      // 16 bytes in two 64-bit halves would need 4 regs; len <= 16
                 uint32_t w[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -1147,7 +1167,7 @@ __device__ __forceinline__ void lz77_resolve_body(
                 for (uint32_t k = 0; k < 16; ++k)
                     if (k < len) buf[dsto + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
             }
-            for (uint64_t lm = __ballot(per && len > 16); lm; lm &= lm - 1) {
+            for (uint64_t lm = (kAblate & 8192u) ? 0ull : __ballot(per && len > 16); lm; lm &= lm - 1) {
                 const int q = __builtin_ctzll(lm);
                 const uint32_t D = __builtin_amdgcn_readlane(dsto, q), P = __builtin_amdgcn_readlane(dist, q), N = __builtin_amdgcn_readlane(len, q);
                 wave_copy(buf + D, buf + D - P, P, lane);

@@ -96,6 +96,13 @@ SBX_LZ_HD void periodic16(uint32_t x0, uint32_t x1, uint32_t len, uint32_t s0, u
     }
 }
 
+// The frontier test of K1b's phase B, per lane: a pending near match whose source [src, s_hi) does not end at or below `frontier` -- the
+// start of the batch's first pending match -- may read bytes that a pending match of the batch has yet to write.  No such lane in the
+// wave: every source lies below every pending destination (entries are in position order), all of them are final after phase A, and ONE
+// round resolves the batch -- the exact rule's ranges and searches are not needed (lz77_resolve_body's kFast;
+// tests/cpp/lz77_rounds_host.cpp runs it inside the lock-step model of the rounds).  Lane k's source inside lane k - 1's destination: blocked.
+SBX_LZ_HD bool frontier_blocked(bool pending, uint32_t s_hi, uint32_t frontier) { return pending && s_hi > frontier; }
+
 // The write-out of K1b (phase C of a batch): which bytes of the block go from the LDS window to HBM now, and how.  Positions are
 // block-relative; `a` is the byte address of the block's first output byte mod 16, `wpos` the position up to which the block is in HBM,
 // [opos, opos + span) what the batch just finished.  Everything up to the last position at which the ABSOLUTE address is a multiple of 16

@@ -1,7 +1,7 @@
 // k1_lab -- development tool (not part of the product library): times the inflate kernels of csrc/inflate.hip on the BGZF blocks
 // of a BAM, kernel by kernel with HIP events, and K1b with parts of its batch loop compiled out (lz77_resolve_body's kAblate bits:
 // results of those launches are INVALID by construction; the point is what each part of the loop costs the kernel -- `ablate`) or
-// with other window geometries (`geo`).  The default kernels run first and their output is compared with zlib's on the host, so a
+// with other window geometries (`geo`); `rounds` takes phase B apart and times the body with lz77_resolve_body's kFast / kGuard.  The default kernels run first and their output is compared with zlib's on the host, so a
 // lab build that broke the real path says so.  (Round 6's A/Bs -- the copy primitive, 8-byte cooperative copies, one-step 32-byte
 // copies -- were run from earlier versions of this file: profiles/round6/call_[a-f]_*.jsonl.)
 //
@@ -35,6 +35,12 @@ __global__ __launch_bounds__(kResThreads) __attribute__((amdgpu_waves_per_eu(8, 
 template <uint32_t kAblate>
 __global__ __launch_bounds__(kResThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_lab_k1b_r6(SBX_LZ77_ARGS) {
     lz77_resolve_body<kHistDefault, kSpanDefault, true, true, kAblate, true, false>(SBX_LZ77_PASS);
+}
+
+// round 8: the product body with the one-round fast path (kFast) and / or the wave-uniform guard around the rare paths of a round (kGuard)
+template <uint32_t kAblate, bool kFast, bool kGuard>
+__global__ __launch_bounds__(kResThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_lab_k1b_opt(SBX_LZ77_ARGS) {
+    lz77_resolve_body<kHistDefault, kSpanDefault, true, true, kAblate, true, true, kGuard, kFast>(SBX_LZ77_PASS);
 }
 
 // window geometry variants of the product body
@@ -98,6 +104,19 @@ struct Lab {
             hipLaunchKernelGGL((k_lab_k1b_r6<kAblate>), grid, block, lds, stream, a.lit, a.ent, a.nent, a.out_off, a.isize, a.n_blocks, a.block0, a.out, a.status);
         });
         printf("{\"kernel\": \"k1b\", \"writeout\": \"round 6\", \"ablate\": %u, \"what\": \"%s\", \"ms_best\": %.4f, \"ms_mean\": %.4f}\n", kAblate, what, ms, last_mean);
+        if (verify) check();
+        fflush(stdout);
+    }
+    template <bool kFast, bool kGuard, uint32_t kAblate = 0>
+    void k1b_opt(const char* what, bool verify = false) {
+        const uint32_t per = kResThreads / 64;
+        dim3 grid((a.n_blocks + per - 1) / per), block(kResThreads);
+        const size_t lds = (size_t)per * (kHistDefault + 1024u + kSpanDefault + 16u) + 128 + (size_t)per * 256;
+        const double ms = time([&] {
+            hipLaunchKernelGGL((k_lab_k1b_opt<kAblate, kFast, kGuard>), grid, block, lds, stream, a.lit, a.ent, a.nent, a.out_off, a.isize, a.n_blocks, a.block0, a.out, a.status);
+        });
+        printf("{\"kernel\": \"k1b\", \"ablate\": %u, \"fast\": %s, \"guard\": %s, \"what\": \"%s\", \"ms_best\": %.4f, \"ms_mean\": %.4f}\n", kAblate, kFast ? "true" : "false",
+               kGuard ? "true" : "false", what, ms, last_mean);
         if (verify) check();
         fflush(stdout);
     }
@@ -194,6 +213,23 @@ int main(int argc, char** argv) {
             lab.k1b<8>("the product body, no phase C");
             lab.k1b_r6<0>("round 6's write-out, again");
             lab.k1b<0>("the product body, a third time", true);
+        }
+        if (argc > 3 && std::string(argv[3]) == "rounds") {
+            // round 8: phase B of round 7's body (no guard, no fast path) taken apart -- 512 yields valid bytes, the four path bits do not --,
+            // and the two candidates.  (profiles/round8/k1b_rounds_lab_config2_run*.jsonl were written when round 7's body was the
+            // product body: its rows read "the product body" there.)
+            lab.k1b_opt<false, false>("round 7's body", true);
+            lab.k1b_opt<false, false, 512>("no searches: the frontier rule", true);
+            lab.k1b_opt<false, false, 1024>("rounds without the cooperative copy");
+            lab.k1b_opt<false, false, 2048>("rounds without the permute path");
+            lab.k1b_opt<false, false, 4096>("rounds without the byte-loop periodic path");
+            lab.k1b_opt<false, false, 8192>("rounds without the long periodic loop");
+            lab.k1b_opt<false, false, 1024 | 2048 | 4096 | 8192>("rounds without the four rare paths");
+            lab.k1b_opt<false, false, 4>("no phase B (near matches)");
+            lab.k1b_opt<true, false>("one-round fast path", true);
+            lab.k1b_opt<false, true>("one guard around the four rare paths", true);
+            lab.k1b_opt<true, true>("fast path and guard", true);
+            lab.k1b_opt<false, false>("round 7's body, again", true);
         }
         if (argc > 3 && std::string(argv[3]) == "ablate") {
             lab.k1b<1>("no literal copies (own + coop)");

@@ -7,6 +7,10 @@
 //   (a) under K1b's rule: a match may start once everything below its source end is final, "final" being everything
 //       below the start of the first unfinished match (one readlane per round);
 //   (b) under the exact rule: a match may start once no unfinished match writes into its source range.
+// Round 8: the share of batches that need no phase B at all (no near match), that a single round under rule (a) finishes (every near
+// match's source ends at or below the first near match's start: K1b's one-round fast path), and in which (b) saves a round over (a);
+// which of the five paths of a round of k_lz77_resolve_exact has a taker, per round of rule (b); and how many entries a batch holds
+// (what the two binary searches of rule (b) have to cover).
 // Host-only, no device code; g++ -O2 -o token_stats token_stats.cpp.  Numbers quoted in DESIGN.md sections 3 (K1a, K1b) and 10.
 #include <algorithm>
 #include <cstdint>
@@ -146,6 +150,13 @@ int main(int argc, char** argv) {
     uint64_t rb_per_short_d124 = 0, per_short_n = 0, per_short_d1 = 0, per_short_d124 = 0, per_short_d8 = 0, rb_per_short_gt8 = 0;
     uint64_t plain_long_hist[4] = {0, 0, 0, 0};      // 17-32, 33-64, 65-128, 129+
     uint64_t rb_plain_gt32 = 0;
+    // round 8 (see the head of the file)
+    uint64_t b_no_near = 0, b_one_round = 0, b_exact_saves = 0, b_exact_saves_rounds = 0, b_take_le[4] = {0, 0, 0, 0};   // <= 8, 16, 32 entries, < 64
+    uint64_t b_slow = 0, b_slow_take_le[4] = {0, 0, 0, 0}, slow_rounds = 0;
+    enum { P_OWN, P_COOP, P_PERM, P_BYTES, P_LONGPER, P_N };
+    static const char* const path_name[P_N] = {"own-lane copy (plain, <= 32)", "coop_copy (plain, > 32)", "permute (periodic, len <= 16, dist <= 8)",
+                                               "byte loop (periodic, len <= 16, dist > 8)", "long periodic (len > 16)"};
+    uint64_t rx_rounds = 0, rx_path[P_N] = {0}, rx_path_slow[P_N] = {0}, rx_by_round[8][P_N] = {{0}}, rx_n_by_round[8] = {0}, rx_only_own = 0;
     size_t off = 0;
     while (off + 18 <= file.size() && blocks < max_blocks + 1) {
         const uint8_t* p = file.data() + off;
@@ -186,6 +197,7 @@ int main(int argc, char** argv) {
                 for (auto& m : ms) if (!m.near_ && m.len > 16) ++fl;
                 pa_lit_long += ll != 0; pa_far_long += fl != 0; pa_lit_long_tasks += ll; pa_far_long_tasks += fl;
             }
+            uint32_t r_frontier = 0;
             // (a) frontier rule
             {
                 std::vector<char> pend(ms.size());
@@ -220,6 +232,7 @@ int main(int argc, char** argv) {
                 }
                 rounds_a += r;
                 hist_a[std::min<uint32_t>(r, 39)]++;
+                r_frontier = r;
             }
             // (b) exact rule: ready when no pending match's destination intersects the source range
             {
@@ -236,11 +249,27 @@ int main(int argc, char** argv) {
                             if (pend[j] && ms[j].dst < ms[i].shi && ms[j].dst + ms[j].len > ms[i].src) ok = false;
                         ready[i] = ok;
                     }
-                    for (size_t i = 0; i < ms.size(); ++i) if (ready[i]) { pend[i] = 0; --np; }
+                    bool path[P_N] = {false, false, false, false, false};
+                    for (size_t i = 0; i < ms.size(); ++i) if (ready[i]) {
+                        pend[i] = 0; --np;
+                        const bool per = ms[i].dist < ms[i].len;
+                        path[!per ? (ms[i].len <= 32 ? P_OWN : P_COOP) : ms[i].len > 16 ? P_LONGPER : ms[i].dist <= 8 ? P_PERM : P_BYTES] = true;
+                    }
+                    ++rx_rounds;
+                    ++rx_n_by_round[std::min<uint32_t>(r, 7)];
+                    for (int k = 0; k < P_N; ++k) { rx_path[k] += path[k]; rx_by_round[std::min<uint32_t>(r, 7)][k] += path[k]; if (r_frontier > 1) rx_path_slow[k] += path[k]; }
+                    rx_only_own += path[P_OWN] && !path[P_COOP] && !path[P_PERM] && !path[P_BYTES] && !path[P_LONGPER];
                     ++r;
                 }
                 rounds_b += r;
                 hist_b[std::min<uint32_t>(r, 39)]++;
+                const size_t take = e1 - e0;
+                const int tk = take <= 8 ? 0 : take <= 16 ? 1 : take <= 32 ? 2 : 3;
+                ++b_take_le[tk];
+                b_no_near += r_frontier == 0;
+                b_one_round += r_frontier == 1;
+                if (r_frontier > 1) { ++b_slow; ++b_slow_take_le[tk]; slow_rounds += r; }
+                if (r < r_frontier) { ++b_exact_saves; b_exact_saves_rounds += r_frontier - r; }
             }
             entries += e1 - e0;
             out_bytes += span;
@@ -269,6 +298,25 @@ int main(int argc, char** argv) {
            100.0 * plain_long_hist[0] / std::max<uint64_t>(1, rb_plain_long_tasks), 100.0 * plain_long_hist[1] / std::max<uint64_t>(1, rb_plain_long_tasks),
            100.0 * plain_long_hist[2] / std::max<uint64_t>(1, rb_plain_long_tasks), 100.0 * plain_long_hist[3] / std::max<uint64_t>(1, rb_plain_long_tasks),
            (double)rb_plain_gt32 / batches);
+    printf("batches %llu: no near match %.2f %%; every near match ready in round 1 under the frontier test %.2f %%; the rest %.2f %% "
+           "(%.2f exact rounds each); the exact rule saves a round or more in %.2f %% (%.2f rounds where it does)\n", (unsigned long long)batches,
+           100.0 * b_no_near / batches, 100.0 * b_one_round / batches, 100.0 * b_slow / batches, (double)slow_rounds / std::max<uint64_t>(1, b_slow),
+           100.0 * b_exact_saves / batches, (double)b_exact_saves_rounds / std::max<uint64_t>(1, b_exact_saves));
+    printf("entries per batch: <= 8 %.2f %%, 9-16 %.2f %%, 17-32 %.2f %%, 33-64 %.2f %%; of the batches that need the searches: %.2f %%, %.2f %%, %.2f %%, %.2f %%\n",
+           100.0 * b_take_le[0] / batches, 100.0 * b_take_le[1] / batches, 100.0 * b_take_le[2] / batches, 100.0 * b_take_le[3] / batches,
+           100.0 * b_slow_take_le[0] / std::max<uint64_t>(1, b_slow), 100.0 * b_slow_take_le[1] / std::max<uint64_t>(1, b_slow),
+           100.0 * b_slow_take_le[2] / std::max<uint64_t>(1, b_slow), 100.0 * b_slow_take_le[3] / std::max<uint64_t>(1, b_slow));
+    printf("paths of a round under the exact rule (%llu rounds, %.2f per batch): share of rounds with a taker | of the rounds of batches that need the searches\n",
+           (unsigned long long)rx_rounds, (double)rx_rounds / batches);
+    for (int k = 0; k < P_N; ++k)
+        printf("  %-44s %6.2f %%  %6.2f %%\n", path_name[k], 100.0 * rx_path[k] / std::max<uint64_t>(1, rx_rounds), 100.0 * rx_path_slow[k] / std::max<uint64_t>(1, slow_rounds));
+    printf("  rounds whose only taker is the own-lane copy: %.2f %%\n", 100.0 * rx_only_own / std::max<uint64_t>(1, rx_rounds));
+    printf("  by round (1 .. 8+): rounds | own | coop | permute | bytes | long periodic\n");
+    for (int r = 0; r < 8; ++r)
+        printf("  %d  %9llu  %6.2f %%  %6.2f %%  %6.2f %%  %6.2f %%  %6.2f %%\n", r + 1, (unsigned long long)rx_n_by_round[r],
+               100.0 * rx_by_round[r][0] / std::max<uint64_t>(1, rx_n_by_round[r]), 100.0 * rx_by_round[r][1] / std::max<uint64_t>(1, rx_n_by_round[r]),
+               100.0 * rx_by_round[r][2] / std::max<uint64_t>(1, rx_n_by_round[r]), 100.0 * rx_by_round[r][3] / std::max<uint64_t>(1, rx_n_by_round[r]),
+               100.0 * rx_by_round[r][4] / std::max<uint64_t>(1, rx_n_by_round[r]));
     printf("code lengths (K1a): longest literal/length code per block | longest distance code per block | decoded literal/length codes | decoded distance codes\n");
     {
         uint64_t tb = 0, tl = 0, td = 0;
