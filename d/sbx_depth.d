@@ -121,6 +121,15 @@ extern (C) nothrow @nogc {
     }
     int sbx_merge_bam(const(char)* out_path, const(char*)* in_paths, int n_inputs, const(sbx_filter)* filter, int level, int with_index,
                       int device, sbx_merge_stats* stats, char* err, size_t errlen);
+    // the windowed path of sbx_merge_bam (inputs larger than the device, or SBX_MERGE_WINDOW_BYTES); n_windows == 0: the resident path.
+    // struct_size: sbx_merge_window_stats.sizeof, set by the caller
+    struct sbx_merge_window_stats {
+        uint struct_size; uint n_windows; uint n_batch_runs; uint n_batches_skipped; uint n_input_opens;
+        ulong window_bytes;
+        double ms_dest; double ms_scatter; double ms_inflate_replay; double ms_index_replay;
+    }
+    int sbx_merge_bam_run(const(char)* out_path, const(char*)* in_paths, int n_inputs, const(sbx_filter)* filter, int level, int with_index,
+                          int device, sbx_merge_stats* stats, sbx_merge_window_stats* window_stats, char* err, size_t errlen);
     int sbx_merge_header_text(const(char*)* texts, const(size_t)* lens, int n, char* out_, size_t cap, size_t* out_len);
     enum SBX_VIEW_MAX_REGIONS = 1024;
     struct sbx_view_opts {

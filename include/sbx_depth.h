@@ -48,7 +48,7 @@ typedef struct sbx_ctx sbx_ctx;
 
 /* sizeof() of the named struct of this header as the library was compiled ("sbx_filter", "sbx_regex",
  * "sbx_filter_op", "sbx_region", "sbx_region_stats", "sbx_header_info", "sbx_batch", "sbx_run_stats",
- * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_markdup_stream_stats", "sbx_merge_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats", "sbx_stream_stats", "sbx_subsample_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
+ * "sbx_regex_state", "sbx_shard", "sbx_flagstat_counts", "sbx_sort_stats", "sbx_markdup_stats", "sbx_markdup_stream_stats", "sbx_merge_stats", "sbx_merge_window_stats", "sbx_view_opts", "sbx_view_stats", "sbx_import_stats", "sbx_fixbins_stats", "sbx_fasta_stats", "sbx_slice_stats", "sbx_view_request", "sbx_validate_report", "sbx_validate_stats", "sbx_view_index_stats", "sbx_stream_stats", "sbx_subsample_stats"); 0 for an unknown name.  Lets a foreign-language binding (d/sbx_depth.d, the ctypes
  * binding) verify its struct layouts against the library it loaded. */
 size_t sbx_abi_sizeof(const char* type_name);
 
@@ -209,9 +209,10 @@ int sbx_format_flagstat(const sbx_flagstat_counts* f, int tabular, char* buf, si
  *             not the one its key was taken with -- the call fails with SBX_EIO ("the input changed while it was being sorted") and
  *             the output file is removed.  SBX_ENOMEM only when not even the keys, one minimal read batch and a window of one piece
  *             fit.
- * sbx_sort_bam_by_name, sbx_merge_bam and view with two or more listed regions have
+ * sbx_sort_bam_by_name and view with two or more listed regions have
  * the resident path only and refuse what does not fit with SBX_ENOMEM (a name order needs the names next to the keys: not built);
- * sbx_fixbins, sbx_import_sam and both sinks of view in file order stream such a file (sbx_stream_stats).
+ * sbx_markdup and sbx_merge_bam have a windowed path of their own (below); sbx_fixbins, sbx_import_sam and both sinks of view in
+ * file order stream such a file (sbx_stream_stats).
  * Milliseconds are device time of the kernels (inflate = K1, index = K2, keys = K9a + the copy into the record store, sort = K9b,
  * gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of the call without the index.
  * On the windowed path inflate and index are those of the key pass alone (SBX_TIMING=1 reports the replays in a `[sbx] sort-windows:`
@@ -311,13 +312,32 @@ int sbx_markdup_header_text(const char* text, size_t n, const char* pg_command_l
  * ref_id -- and the value of its RG:Z / PG:Z tag replaced when the merged header renamed that id, and the records of all inputs are
  * sorted by coordinate with sbx_sort_bam's stable sort: ties (same reference, position and strand) come out lower input first, then
  * in file order.  The inputs are not assumed to BE sorted: the output is sorted whatever the records say.  filter is applied to the
- * records as they are in their input.  All inputs are resident on the device: what does not fit next to one batch of the read pass is
- * refused with SBX_ENOMEM, more than 2^32 records and inputs sorted by read name with SBX_EUNSUPPORTED, fewer than two inputs, more
- * than SBX_MERGE_MAX_INPUTS, or an output that is one of the inputs with SBX_EINVAL.  n_records_rewritten: records in which a
+ * records as they are in their input.  More than 2^32 records and inputs sorted by read name are refused with SBX_EUNSUPPORTED,
+ * fewer than two inputs, more than SBX_MERGE_MAX_INPUTS, or an output that is one of the inputs with SBX_EINVAL.  The merge runs on
+ * one of two paths that write the same file byte for byte:
+ *   resident  the inflated records of ALL inputs fit the device next to one batch of the read pass: they stay there (the record
+ *             store), the keys are sorted and the records gathered in order.  sbx_merge_window_stats is all zeros.
+ *   windowed  they do not fit (or SBX_MERGE_WINDOW_BYTES=<n> is set: tests and measurements, windows of n bytes rounded up to whole
+ *             pieces of the output stream; anything but a positive decimal number counts as unset; the file written does not depend
+ *             on n): the key pass visits every input in turn and keeps only key and NEW length of every record -- 36 bytes per
+ *             record during the sort, 12 afterwards; every malformed-record refusal and the 2^32 cap are met in this pass, before the
+ *             output file receives a byte.  The order becomes one destination per record, and the merged stream is written window
+ *             by window: per window the inputs that have a batch with a byte in it are opened again in input order, ONE AT A TIME,
+ *             those batches are inflated and described again (K1 + K2), and K9d (an input nothing changes in) or K11a + K11c (a
+ *             rewritten one: the record's pieces -- fixed part, source stretches, new ids -- each clipped to the window) put the
+ *             bytes in place.  Coordinate-sorted inputs go to ascending, disjoint stretches of the output, so a batch is run again
+ *             at most once per window it touches, n_batch_runs <= n_batches + n_inputs * (n_windows - 1), and every input is
+ *             inflated about twice in all; inputs that are not sorted cost up to one pass per window.  No temporary file.  If an
+ *             input is not the same in both passes the call fails with SBX_EIO ("the input changed while it was being merged") and
+ *             the output file is removed.  SBX_ENOMEM only when the keys, K11's scratch of one batch, one minimal read batch, the
+ *             encoder and a window of one piece do not fit together; the message states the bytes needed, part by part, and free.
+ *             No set of inputs larger than the device has been merged: the path is exercised only through the hook.
+ * n_records_rewritten: records in which a
  * reference id or a tag value changed; bytes_grown: bytes of the records written minus bytes of the same records as read.
  * Milliseconds are device time (inflate = K1, index = K2, rewrite = K11 or, for an input nothing changes in, K9a + the copy into
  * the record store, sort = K9b, gather = output offsets + K9c, deflate = the BGZF encoder + packing), ms_total_wall the wall clock of
- * the call without the index.
+ * the call without the index.  On the windowed path inflate and index are those of the key pass alone (the replays:
+ * sbx_merge_window_stats), rewrite = K9a alone or K11a + the key-only emit, gather = output offsets + K9d-1/2 + the scatters.
  * How closely a record is checked depends on whether its input is rewritten.  An input with a renumbered reference or a renamed id
  * goes through K11, which checks the fixed part and every aux field against block_size and refuses the call with SBX_EFORMAT.  An
  * input nothing changes in is copied and checked as sbx_sort_bam checks a record: block_size against the batch, ref_id against the
@@ -335,6 +355,21 @@ typedef struct {
 /* filter, level, with_index, stats as sbx_sort_bam.  On failure no output file is left behind. */
 int sbx_merge_bam(const char* out_path, const char* const* in_paths, int n_inputs, const sbx_filter* filter, int level, int with_index,
                   int device, sbx_merge_stats* stats, char* err, size_t errlen);
+/* What the windowed path of sbx_merge_bam did.  n_windows == 0: the resident path, and every other figure is 0.  struct_size: set
+ * by the caller to sizeof(sbx_merge_window_stats) and left as it is (a smaller value is SBX_EINVAL).  window_bytes: bytes of the
+ * merged stream per window; n_batch_runs / n_batches_skipped: batches run again / not run, summed over the windows and inputs;
+ * n_input_opens: times an input was opened again for a window (an input that serves consecutive windows alone stays open).
+ * Milliseconds are device time: dest = K9d-1 + K9d-2, scatter = K9d-3 and K11a + K11c, inflate_replay / index_replay = K1 / K2 of the
+ * batches run again.  With SBX_TIMING=1 the same figures are printed in a `[sbx] merge-windows:` line. */
+typedef struct {
+    uint32_t struct_size;
+    uint32_t n_windows, n_batch_runs, n_batches_skipped, n_input_opens;
+    uint64_t window_bytes;
+    double ms_dest, ms_scatter, ms_inflate_replay, ms_index_replay;
+} sbx_merge_window_stats;
+/* sbx_merge_bam with the figures of the windowed path: window_stats may be NULL, and sbx_merge_bam is this call with NULL. */
+int sbx_merge_bam_run(const char* out_path, const char* const* in_paths, int n_inputs, const sbx_filter* filter, int level, int with_index,
+                      int device, sbx_merge_stats* stats, sbx_merge_window_stats* window_stats, char* err, size_t errlen);
 /* The merged header text for n header texts in input order (host only).  Lengths as sbx_sort_header_text; SBX_EFORMAT for a text the
  * reference's parser throws on, SBX_EINVAL when the sorting orders forbid the merge or one reference name has two lengths,
  * SBX_EUNSUPPORTED for queryname.  The message of a refusal is written to out when it fits. */

@@ -117,6 +117,11 @@ class MergeStats(C.Structure):
                 [(k, C.c_uint32) for k in ("n_inputs", "key_bits", "n_sort_passes", "n_batches")] +
                 [(k, C.c_double) for k in ("ms_inflate", "ms_index", "ms_rewrite", "ms_sort", "ms_gather", "ms_deflate", "ms_total_wall")])
 
+class MergeWindowStats(C.Structure):
+    _fields_ = ([(k, C.c_uint32) for k in ("struct_size", "n_windows", "n_batch_runs", "n_batches_skipped", "n_input_opens")] +
+                [("window_bytes", C.c_uint64)] +
+                [(k, C.c_double) for k in ("ms_dest", "ms_scatter", "ms_inflate_replay", "ms_index_replay")])
+
 class ViewOpts(C.Structure):
     _fields_ = [("flags_set", C.c_uint16), ("flags_unset", C.c_uint16), ("subsample", C.c_int32), ("fraction", C.c_double), ("seed", C.c_uint64)]
 
@@ -196,7 +201,7 @@ EXPORTS = [
     "sbx_format_base_rows", "sbx_stream_base_rows", "sbx_plan_batches", "sbx_run_batch", "sbx_last_run_stats", "sbx_tile_info", "sbx_next_active_range", "sbx_preload",
     "sbx_device_count", "sbx_plan_shards", "sbx_format_base_rows_device", "sbx_flagstat", "sbx_format_flagstat",
     "sbx_sort_bam", "sbx_sort_bam_by_name", "sbx_sort_header_text", "sbx_markdup", "sbx_markdup_run", "sbx_markdup_header_text",
-    "sbx_merge_bam", "sbx_merge_header_text",
+    "sbx_merge_bam", "sbx_merge_bam_run", "sbx_merge_header_text",
     "sbx_view_count", "sbx_view_bam", "sbx_view_sam", "sbx_view_run", "sbx_view_run_indexed", "sbx_view_run_streamed", "sbx_view_num_filter", "sbx_view_reference_info",
     "sbx_validate_bam", "sbx_format_validate_report",
     "sbx_slice_bam",
@@ -338,6 +343,8 @@ def lib():
     L.sbx_markdup_header_text.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_merge_bam.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.POINTER(MergeStats),
                                 C.c_char_p, C.c_size_t]
+    L.sbx_merge_bam_run.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Filter), C.c_int, C.c_int, C.c_int, C.POINTER(MergeStats),
+                                    C.POINTER(MergeWindowStats), C.c_char_p, C.c_size_t]
     L.sbx_merge_header_text.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.sbx_view_count.argtypes = [C.c_char_p, C.POINTER(Filter), C.POINTER(ViewOpts), C.POINTER(C.c_char_p), C.c_size_t, C.c_char_p, C.c_int,
                                  C.POINTER(C.c_uint64), C.POINTER(ViewStats), C.c_char_p, C.c_size_t]
@@ -381,7 +388,7 @@ def lib():
                      ("sbx_filter_op", FilterOp), ("sbx_regex_state", RegexState), ("sbx_regex", Regex), ("sbx_filter", Filter),
                      ("sbx_run_stats", RunStats), ("sbx_batch", Batch), ("sbx_flagstat_counts", Flagstat),
                      ("sbx_sort_stats", SortStats), ("sbx_markdup_stats", MarkdupStats), ("sbx_markdup_stream_stats", MarkdupStreamStats),
-                     ("sbx_merge_stats", MergeStats),
+                     ("sbx_merge_stats", MergeStats), ("sbx_merge_window_stats", MergeWindowStats),
                      ("sbx_view_opts", ViewOpts), ("sbx_view_stats", ViewStats), ("sbx_import_stats", ImportStats),
                      ("sbx_fixbins_stats", FixbinsStats), ("sbx_fasta_stats", FastaStats), ("sbx_slice_stats", SliceStats),
                      ("sbx_view_request", ViewRequest), ("sbx_validate_report", ValidateReport), ("sbx_validate_stats", ValidateStats),
@@ -828,17 +835,24 @@ class Depth:
 
 def merge(out_path, inputs, filter=None, level=-1, index=False, device=-1):
     """sbx_merge_bam (`sambamba merge`): merges the coordinate-sorted BAMs `inputs` into out_path on the device; filter is a -F query
-    string (None: every record); index=True also writes out_path + ".bai".  Returns the fields of sbx_merge_stats as a dict."""
+    string (None: every record); index=True also writes out_path + ".bai".  Returns the fields of sbx_merge_stats as a dict, plus
+    those of sbx_merge_window_stats but struct_size (n_windows, n_batch_runs, n_batches_skipped, n_input_opens, window_bytes and
+    the four times): zeros when the records of all inputs stayed on the device, the figures of the windowed path when they did not
+    fit (or SBX_MERGE_WINDOW_BYTES is set)."""
     L = lib()
     f = compile_filter(filter) if filter else None
     st = MergeStats()
+    ws = MergeWindowStats()
+    ws.struct_size = C.sizeof(MergeWindowStats)
     err = C.create_string_buffer(512)
     paths = (C.c_char_p * max(1, len(inputs)))(*[p.encode() for p in inputs])
-    rc = L.sbx_merge_bam(out_path.encode(), paths, len(inputs), C.byref(f) if f is not None else None, int(level), int(index), device,
-                         C.byref(st), err, 512)
+    rc = L.sbx_merge_bam_run(out_path.encode(), paths, len(inputs), C.byref(f) if f is not None else None, int(level), int(index), device,
+                             C.byref(st), C.byref(ws), err, 512)
     if rc != 0:
         raise SbxError(rc, err.value.decode())
-    return {k: getattr(st, k) for k, _ in MergeStats._fields_}
+    out = {k: getattr(st, k) for k, _ in MergeStats._fields_}
+    out.update({k: getattr(ws, k) for k, _ in MergeWindowStats._fields_ if k != "struct_size"})
+    return out
 
 
 def merge_header_text(texts):

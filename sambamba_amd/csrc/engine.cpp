@@ -59,6 +59,7 @@ size_t sbx_abi_sizeof(const char* name) {
     if (n == "sbx_markdup_stats") return sizeof(sbx_markdup_stats);
     if (n == "sbx_markdup_stream_stats") return sizeof(sbx_markdup_stream_stats);
     if (n == "sbx_merge_stats") return sizeof(sbx_merge_stats);
+    if (n == "sbx_merge_window_stats") return sizeof(sbx_merge_window_stats);
     if (n == "sbx_view_opts") return sizeof(sbx_view_opts);
     if (n == "sbx_view_stats") return sizeof(sbx_view_stats);
     if (n == "sbx_slice_stats") return sizeof(sbx_slice_stats);

@@ -353,10 +353,11 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
     DevBuf<uint8_t> d_hi((size_t)n + 2);
     DevBuf<uint32_t> d_out_len((size_t)n + 2);
     DevBuf<uint64_t> d_dest((size_t)n + 2);
+    const std::vector<WindowSource> sources = one_open_source(c.get(), saved, n);
     BatchSpans spans;
     uint64_t total = hlen;
     {
-        spans.upload(saved, n, s);
+        spans.upload(sources, n, s);
         d_tile_sum.ensure(len_tiles(n) + 2);
         EventTimer t;
         t.start(s);
@@ -374,8 +375,8 @@ void markdup_streamed(Standalone& c, OutputGuard& out_file, MdJob& job, bool rem
     if (!remove && (n_out != n || total != hlen + acc[kMdAccBytes])) throw Error(SBX_EFORMAT, "internal error: the offsets of the records do not add up");
 
     // ---- the windows: K10f for every saved batch that meets one ----
-    const WindowedOutput w = write_windows(c.get(), out_file, header, total, budget, spans, level, [&](const SavedBatch& sb, const RecordBatch& rb,
-                                           const sortc::Window& win, uint8_t* d_win, unsigned long long* d_wacc, hipStream_t ws) {
+    const WindowedOutput w = write_windows(sources, s, out_file, header, total, budget, spans, level, [&](size_t, sbx_ctx*, const SavedBatch& sb,
+                                           const RecordBatch& rb, const sortc::Window& win, uint8_t* d_win, unsigned long long* d_wacc, hipStream_t ws) {
         MdScatterArgs a{};
         a.U = c->U(); a.desc = c->d_desc.p; a.n = rb.nrec; a.u_end = rb.next - rb.base; a.first = sb.first_kept;
         a.dest = d_dest.p; a.len = pass.d_len.p; a.out_len = d_out_len.p; a.hi = d_hi.p;

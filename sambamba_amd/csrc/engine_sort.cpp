@@ -18,8 +18,8 @@
 // into the window, which goes through the same encoder to the file.  No temporary file and no merge; the file is the resident
 // path's byte for byte.  The budget of device memory, the spans, the choice of the window and the loop over windows and batches are
 // engine_windows.hpp, shared with sbx_markdup (whose output is in input order); what is here is the key pass, the order and the
-// callback that launches K9d-3.  The name orders and sbx_merge_bam stay resident and refuse with
-// SBX_ENOMEM what does not fit; sbx_fixbins, sbx_import_sam and view in file order, BAM and SAM sink, stream it (engine_streamout.hpp).
+// callback that launches K9d-3.  The name orders stay resident and refuse with
+// SBX_ENOMEM what does not fit (sbx_merge_bam has a windowed path of its own, engine_merge.cpp); sbx_fixbins, sbx_import_sam and view in file order, BAM and SAM sink, stream it (engine_streamout.hpp).
 //
 // sbx_sort_bam_by_name (`sambamba sort -n / -N`, with or without -M) is the same call with another order: next to K9a, K14a
 // (namesort.hip) builds the key of every kept record's name in a key store of 64-bit words, and the order is an LSD sort over those
@@ -233,6 +233,7 @@ void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<
     // ---- K9b, the offsets, K9d-1 and K9d-2 ----
     double ms_dest = 0;
     DevBuf<uint64_t> d_dest((size_t)n + 2);
+    const std::vector<WindowSource> sources = one_open_source(c.get(), saved, n);
     BatchSpans spans;
     uint64_t total = hlen;
     {
@@ -243,7 +244,7 @@ void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<
         const OutputPlan plan = plan_output(keys.d_len.p, order.perm, n, hlen, order.key2.p, s, &st.ms_gather);
         total = plan.total;
         if (total != hlen + acc[kSortAccBytes]) throw Error(SBX_EFORMAT, "internal error: the offsets of the sorted records do not add up");
-        spans.upload(saved, n, s);
+        spans.upload(sources, n, s);
         EventTimer t;
         t.start(s);
         launch_window_dest(order.perm, order.key2.p, n, d_dest.p, s);
@@ -256,8 +257,8 @@ void sort_file_windowed(Standalone& c, OutputGuard& out_file, const std::vector<
     }
 
     // ---- the windows: K9d-3 for every saved batch that meets one ----
-    const WindowedOutput w = write_windows(c.get(), out_file, header, total, budget, spans, level, [&](const SavedBatch& sb, const RecordBatch& rb,
-                                           const sortc::Window& win, uint8_t* d_win, unsigned long long* d_wacc, hipStream_t ws) {
+    const WindowedOutput w = write_windows(sources, s, out_file, header, total, budget, spans, level, [&](size_t, sbx_ctx*, const SavedBatch& sb,
+                                           const RecordBatch& rb, const sortc::Window& win, uint8_t* d_win, unsigned long long* d_wacc, hipStream_t ws) {
         if (use_filter) {
             keys.d_group_count.ensure(sort_keys_groups(rb.nrec) + 4);
             keys.d_group_base.ensure(sort_keys_groups(rb.nrec) + 4);

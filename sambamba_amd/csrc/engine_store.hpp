@@ -8,7 +8,7 @@
 // of a permutation" into a BGZF file piece by piece (offsets, piece bounds, K9c gather, deflate) and hands back the figures every
 // stats struct takes.  The permutation is a list of record numbers: it may leave records out (a filter) or name one several times
 // (sbx_view_bam with listed regions).  The stream written never exists as a whole.  What the kernels share is wave_prims.hpp.  A file
-// that does not fit the store goes, for sort and markdup, through engine_windows.hpp instead (the same reading order, a key pass for
+// that does not fit the store goes, for sort, markdup and merge, through engine_windows.hpp instead (the same reading order, a key pass for
 // the plan, the windowed writer for the tail), for fixbins and view in file order through engine_streamout.hpp.
 #pragma once
 #include "engine_ctx.hpp"
@@ -85,7 +85,7 @@ inline StorePlan plan_record_store(sbx_ctx* c, uint64_t hlen, uint64_t per_recor
 }
 
 // The resident-or-not decision: the plan, or nothing when the store does not fit the device.  Only SBX_ENOMEM means that; every
-// other error passes through.  A command that has no other path (sort -n / -N / -M, merge) calls plan_* itself and keeps the refusal.
+// other error passes through.  A command that has no other path (sort -n / -N / -M) calls plan_* itself and keeps the refusal.
 template <class Plan>
 std::optional<StorePlan> plan_if_fits(Plan&& plan) {
     try {

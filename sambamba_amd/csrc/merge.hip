@@ -18,11 +18,25 @@
 //                          is); the stretches between the patches move as K9c moves a record (copy_span16, wave_prims.hpp); the
 //                          new ids are written byte by byte.  Plain C++ vector stores.  The host has compared the scanned size of
 //                          the batch with what is left of the store before the launch: no lane writes behind store_at + len_base[n].
+//        k_merge_emit_keys the key pass of the windowed merge (launch_merge_rewrite without a store): one lane per record, key and
+//                          NEW length to the record's ordinal, no byte moved.
+//   K11c k_merge_window_scatter  the windowed merge (engine_merge.cpp: inputs that do not stay on the device): sixteen lanes per
+//                          described record of a REPLAYED batch that K11a has described again, the shape of K11b and of K9d-3
+//                          (sort.hip).  The record's ordinal is the batch's saved first ordinal + keep_base[i], its place in the
+//                          merged stream dest[ordinal]; the stretches K11b writes -- fixed part, source, new id, source, new id,
+//                          tail -- are each clipped to the window [w0, w1) (mergewin_core.hpp: for_each_stretch) and go to
+//                          window + (dest - w0): source stretches with copy_span16, the fixed part and the ids byte by byte.  The
+//                          clip is what bounds the stores; the frame K11a checked in THIS pass bounds the loads.  Every wave adds
+//                          the bytes it wrote to one 64-bit counter and the records that are not the ones of the key pass (another
+//                          new length; a batch that keeps another number of records) to a second (sort.hpp WindowAcc).
 //
 // Bytes moved (n records, b bytes): K11a reads 32 n of descriptors and the fixed part + aux fields of every record, writes 36 n;
-// the scans read and write 24 n; K11b reads and writes b.
+// the scans read and write 24 n; K11b reads and writes b; the emit reads 24 n and writes 12 n.  K11c, for a window of w bytes filled
+// from batches of r records: K11a and the scans over the r records again, then 48 r (keep, keep_base, new_len, saved length, dest,
+// descriptor, patches) + w read and w written.
 #include "common.hpp"
 #include "merge.hpp"
+#include "mergewin_core.hpp"
 #include "sort_core.hpp"
 #include "wave_prims.hpp"
 
@@ -182,6 +196,68 @@ __global__ __launch_bounds__(kMergeThreads) void k_merge_rewrite(MergeArgs a) {
     }
 }
 
+// the key pass of the windowed merge: what K11b's lane 0 writes, without the bytes and without an offset
+__global__ __launch_bounds__(kMergeThreads) void k_merge_emit_keys(MergeArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * kMergeThreads + threadIdx.x;
+    if (i >= a.n || !a.b.keep[i]) return;
+    const uint64_t r = a.out_base + a.b.keep_base[i];
+    a.key[r] = a.b.key[i];
+    a.len[r] = a.b.new_len[i];
+}
+
+// ---- K11c ----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMergeThreads) void k_merge_window_scatter(MergeArgs a, MergeWindowArgs w) {
+    const uint32_t l = threadIdx.x % kRewriteGroup;
+    const uint64_t i = (uint64_t)blockIdx.x * kRewriteRecs + threadIdx.x / kRewriteGroup;
+    bool bad = false;
+    unsigned long long wrote = 0;
+    if (i < a.n && a.b.keep[i]) {
+        const uint64_t k = a.b.keep_base[i];                       // among the records of the batch that take part
+        bad = a.b.keep_base[a.n] != w.n_kept || k >= w.n_kept;
+        if (!bad) {
+            const uint64_t ord = w.first_kept + k;
+            const uint32_t nl = a.b.new_len[i];
+            bad = nl != w.len[ord];
+            const uint64_t d = w.dest[ord];
+            if (!bad && d < w.w1 && d + nl > w.w0) {
+                // the record as K11a found it in THIS pass: its frame and its patches bound the loads, the clips the stores
+                const uint8_t* src = a.U + a.desc[i].rec_off;
+                const uint32_t old_len = ld32(src) + 4u;
+                const uint32_t new_ref = (uint32_t)map_ref(a, (int32_t)ld32(src + 4)), new_next = (uint32_t)map_ref(a, (int32_t)ld32(src + 24));
+                mergewin::Patch patch[mergewin::kMaxPatches];
+                uint32_t np = 0;
+                for (uint32_t q = 0; q < mergewin::kMaxPatches; ++q) {
+                    const uint32_t en = a.b.patch_entry[2 * i + q];
+                    if (en == kMergeNone) break;
+                    const RenameEntry x = a.table.entry[en];
+                    patch[np++] = mergewin::Patch{a.b.patch_at[2 * i + q], x.old_len, x.new_len, x.new_off};
+                }
+                mergewin::for_each_stretch(old_len, nl, patch, np, d, w.w0, w.w1, [&](uint32_t kind, uint64_t s, uint64_t at, uint64_t len) {
+                    uint8_t* out = w.window + at;
+                    if (kind == mergewin::kStretchSource) {
+                        copy_span16(out, src + s, len, l);
+                    } else if (kind == mergewin::kStretchBlob) {
+                        for (uint64_t b = l; b < len; b += kRewriteGroup) out[b] = (uint8_t)a.table.blob[s + b];
+                    } else {
+                        for (uint64_t b = l; b < len; b += kRewriteGroup) {
+                            const uint32_t fb = (uint32_t)(s + b);
+                            out[b] = mergewin::fixed_byte(fb, nl - 4u, new_ref, new_next, ld32(src + 4 * (fb >> 2)));
+                        }
+                    }
+                    wrote += len;
+                });
+                if (l != 0) wrote = 0;
+            }
+        }
+    }
+    const unsigned long long mb = __ballot(bad && l == 0);
+    wrote = wave_sum(wrote);
+    if ((threadIdx.x & 63u) == 0) {
+        if (wrote) atomicAdd(w.acc + kWindowAccBytes, wrote);
+        if (mb) atomicAdd(w.acc + kWindowAccMismatch, (unsigned long long)__popcll(mb));
+    }
+}
+
 }  // namespace
 
 void launch_merge_describe(const MergeArgs& a, hipStream_t stream) {
@@ -194,7 +270,18 @@ void launch_merge_describe(const MergeArgs& a, hipStream_t stream) {
 
 void launch_merge_rewrite(const MergeArgs& a, hipStream_t stream) {
     if (!a.n) return;
+    if (!a.store) {
+        hipLaunchKernelGGL(k_merge_emit_keys, dim3((uint32_t)((a.n + kMergeThreads - 1) / kMergeThreads)), dim3(kMergeThreads), 0, stream, a);
+        SBX_HIP(hipGetLastError());
+        return;
+    }
     hipLaunchKernelGGL(k_merge_rewrite, dim3((uint32_t)((a.n + kRewriteRecs - 1) / kRewriteRecs)), dim3(kMergeThreads), 0, stream, a);
+    SBX_HIP(hipGetLastError());
+}
+
+void launch_merge_window_scatter(const MergeArgs& a, const MergeWindowArgs& w, hipStream_t stream) {
+    if (!a.n || w.w1 <= w.w0) return;
+    hipLaunchKernelGGL(k_merge_window_scatter, dim3((uint32_t)((a.n + kRewriteRecs - 1) / kRewriteRecs)), dim3(kMergeThreads), 0, stream, a, w);
     SBX_HIP(hipGetLastError());
 }
 

@@ -58,7 +58,25 @@ constexpr uint32_t kMergeThreads = 256;
 // K11a: every record of the batch checked and described, then the two scans (MergeBatch::len_base, keep_base)
 void launch_merge_describe(const MergeArgs& a, hipStream_t stream);
 // K11b: the records that take part go to store + store_at + len_base[i], rewritten.  The caller has compared len_base[n] with what
-// is left of the store.
+// is left of the store.  store == nullptr (the key pass of the windowed merge): no byte is moved; key[r] and len[r] -- the NEW
+// length -- of the records that take part are written at their ordinals out_base + keep_base[i], one lane per record, and `off`
+// is not touched.
 void launch_merge_rewrite(const MergeArgs& a, hipStream_t stream);
+
+// K11c: the windowed merge (no record store).  The batch has gone through launch_merge_describe again in THIS pass (a.b is this
+// pass's; a.store, a.key, a.off, a.len are not used).  The record i that takes part has the ordinal first_kept + keep_base[i]; the
+// bytes of the rewritten record that lie in [w0, w1) of the merged stream go to window + (dest[ordinal] - w0) (mergewin_core.hpp).
+// acc: the words of K9d-3 (sort.hpp WindowAcc) -- bytes written; records whose new length is not len[ordinal], or every record
+// that takes part in THIS pass when the batch keeps another number of records than n_kept (a batch that keeps none now counts
+// no record: the bytes the window then misses report it).
+struct MergeWindowArgs {
+    uint64_t first_kept, n_kept;    // ordinals the key pass gave the batch's records that take part: [first_kept, first_kept + n_kept)
+    const uint64_t* dest;           // [ordinal] offset in the merged stream (K9d-1)
+    const uint32_t* len;            // [ordinal] the new length as the key pass computed it
+    uint64_t w0, w1;                // the window of the merged stream
+    uint8_t* window;                // [w1 - w0]
+    unsigned long long* acc;        // [kWindowAccWords]
+};
+void launch_merge_window_scatter(const MergeArgs& a, const MergeWindowArgs& w, hipStream_t stream);
 
 }  // namespace sbx

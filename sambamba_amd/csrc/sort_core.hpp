@@ -142,22 +142,26 @@ inline std::vector<Window> plan_windows(uint64_t total_stream_bytes, uint64_t pi
     return w;
 }
 
-// The windowed writer (engine_windows.hpp) serves two commands; the phrases of its refusals that differ between them:
+// The windowed writer (engine_windows.hpp) serves three commands; the phrases of its refusals that differ between them:
 struct WindowWords {
     const char* task;           // "... does not fit the device: <task> in windows needs ..."
     const char* window_needs;   // what the window itself needs, for that refusal
     const char* doing;          // "the input changed while <doing>"
     const char* stream;         // "bytes [w0, w1) of the <stream>"
     const char* source;         // "record(s) are not the ones <source>"
+    const char* what = "the file does";         // "<what> not fit the device"
 };
 constexpr WindowWords kSortWindowWords{"sorting it", "one window of one piece and the encoder, next to the read batch and 12 bytes per record",
                                        "it was being sorted", "sorted stream", "the keys were taken from"};
 constexpr WindowWords kMarkdupWindowWords{"marking its duplicates", "a window of one piece and the encoder, next to the read batch and 17 bytes per record",
                                           "its duplicates were being marked", "output stream", "the key pass read"};
 
+constexpr WindowWords kMergeWindowWords{"merging them", "a window of one piece and the encoder, next to the read batch and 12 bytes per record",
+                                        "it was being merged", "merged stream", "the key pass read", "the files do"};
+
 // the SBX_ENOMEM refusal of a file that does not even go through in windows; parts: what the `need` bytes are for
 inline std::string windows_do_not_fit(const WindowWords& words, uint64_t need, uint64_t free_bytes, const std::string& parts) {
-    return std::string("the file does not fit the device: ") + words.task + " in windows needs " + std::to_string(need) +
+    return std::string(words.what) + " not fit the device: " + words.task + " in windows needs " + std::to_string(need) +
            " bytes of device memory (" + parts + "), " + std::to_string(free_bytes) + " are free";
 }
 // the SBX_EIO refusal of a batch that came out of the read pass differently the second time
